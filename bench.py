@@ -21,15 +21,28 @@ default --disk-threads), at the per-GPU CPU share (16) and at one thread per
 CPU of the affinity mask; the host record names the cgroup CPU quota.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--loader api|glds|direct]
+        (the headline figure alone: set-up, W warmup steps, K timed steps, one
+        JSON line with value and ms_per_step; the roofline's fields that the
+        timed steps' own events give)
+    python bench.py ... --full
+        (what else the line carries: the parity checks -- golden digests and
+        step-to-step identity, sampled oracle digests at N>1 --, the CPU
+        baseline, the roofline's VALU ceiling timed live, at N=1 config5,
+        config3, config2host and config1 as `secondary` records, at N>1
+        devices_seen; without it `parity` says that nothing was checked)
+    python bench.py ... --dump-outputs DIR
+        (the digests the last timed step left in the caller's buffer, as
+        DIR/digests.npy: float32, one row of 32 byte values per block, all
+        blocks or a fixed seeded sample with its indices in
+        DIR/digests_blocks.npy; the inputs are the same in every run)
     python bench.py --workload config3|config5|config1|config2host|config2sha
-        (one secondary config on its own; the default N=1 line also carries
-        config5, config3, config2host and config1 as `secondary` records)
+        (one secondary config on its own)
     python bench.py --gpus N   (N > 1: launches N ranks itself through
         torch.distributed.run unless WORLD_SIZE is already set)
     python bench.py --gpus 1 --force-dist   (the N>1 code path -- process
         group, config 4, job-wide parity -- on one rank, launched the same way)
 
-The N>1 line also carries devices_seen: every rank's PCI bus id, UUID and
+With --full the N>1 line also carries devices_seen: every rank's PCI bus id, UUID and
 device clocks (cir_debug_device_identity), gathered over the process group;
 under RCCL two ranks on one device fail the line.  Config 1's CLI is timed
 before this process touches the GPU; config 5 adds a cold scan of the tree
@@ -54,6 +67,7 @@ METRIC = "GiB/s block-hashed (device-resident, blocks in HBM) at 1/2/4/8 MI355X"
 HBM_PEAK_GBS = 8000.0  # MI355X_MICROARCH.md: HBM3E 8.0 TB/s spec
 SEED_C2 = 0x5EED0002
 SEED_C4 = 0x5EED0004
+PARITY_NOT_CHECKED = "not checked (--full checks it)"
 
 
 def log(*a):
@@ -109,6 +123,15 @@ def parse():
     p.add_argument("--cpu-seconds", type=float, default=2.5,
                    help="wall seconds of the 4-thread CPU-baseline measurement (all cores: "
                         "the same CPU work)")
+    p.add_argument("--full", action="store_true",
+                   help="everything beyond the headline figure: the parity checks, the CPU "
+                        "baseline, the secondary configs (1, 3, 5, 2-from-host), the live VALU "
+                        "ceiling of the roofline and, at N>1, the ranks' device identities")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed steps, write the digests the last timed step returned "
+                        "as DIR/digests.npy (float32, one row of 32 byte values per block; a "
+                        "fixed seeded sample of the blocks when there are too many, their "
+                        "indices in DIR/digests_blocks.npy)")
     return p.parse_args()
 
 
@@ -121,6 +144,40 @@ def fill_config2(ca, data, bs, stream):
     if nspecial > 16:
         pat = torch.arange(256, dtype=torch.int32, device=data.device).to(torch.uint8)
         data[16 * bs:nspecial * bs].copy_(pat.repeat((nspecial - 16) * bs // 256))
+
+
+DUMP_MAX_BYTES = 48 << 20  # of digests.npy; with the block indices, under 64 MB
+DUMP_SEED = 0x5EEDD0
+
+
+def dump_blocks(nblk):
+    """The blocks --dump-outputs keeps: all of them while their digests fit
+    DUMP_MAX_BYTES as float32, else the first and last 64 (the special
+    blocks, the launch's edges) and a seeded draw of the rest -- the same
+    blocks in every run of the same shape."""
+    import numpy as np
+    keep = DUMP_MAX_BYTES // (32 * 4)
+    if nblk <= keep:
+        return np.arange(nblk, dtype=np.int64)
+    edge = 64
+    rng = np.random.default_rng(DUMP_SEED)
+    mid = rng.choice(nblk - 2 * edge, size=keep - 2 * edge, replace=False) + edge
+    return np.concatenate([np.arange(edge), np.sort(mid),
+                           np.arange(nblk - edge, nblk)]).astype(np.int64)
+
+
+def dump_outputs(dirname, name, out):
+    """What the caller of the timed path holds after its last step: `out`,
+    the device buffer of 32-byte digests, as DIR/<name>.npy (float32, one
+    row of 32 byte values per kept block) and the kept blocks' indices as
+    DIR/<name>_blocks.npy (float64)."""
+    import numpy as np
+    import torch
+    idx = dump_blocks(out.numel() // 32)
+    rows = out.view(-1, 32)[torch.from_numpy(idx).to(out.device)].cpu().numpy()
+    os.makedirs(dirname, exist_ok=True)
+    np.save(os.path.join(dirname, name + ".npy"), rows.astype(np.float32))
+    np.save(os.path.join(dirname, name + "_blocks.npy"), idx.astype(np.float64))
 
 
 def load_traffic(cfg_key, field="hbm_bytes_per_launch"):
@@ -1227,13 +1284,17 @@ def main():
     local = int(os.environ.get("LOCAL_RANK", "0"))
     if args.gpus != world and world > 1:
         log("warning: --gpus %d but WORLD_SIZE %d; using WORLD_SIZE" % (args.gpus, world))
+    if args.dump_outputs and (args.dry_run or args.workload != "auto"):
+        raise SystemExit("bench: --dump-outputs writes the headline workload's digests "
+                         "(not with --dry-run or --workload)")
     if args.dry_run:
         return dry_run(args, rank, world)
     # config 1's one-shot CLI, timed while no process of this job holds the
     # GPU (this process has made no GPU call yet and opens no context until
     # after it)
     if world == 1 and not args.force_dist and (
-            args.workload == "config1" or (args.workload == "auto" and not args.no_secondary)):
+            args.workload == "config1" or (args.workload == "auto" and args.full
+                                           and not args.no_secondary)):
         try:
             args.cli_pre = time_cli_config1()
         except Exception as e:  # noqa: BLE001 - reported in the config-1 record
@@ -1326,7 +1387,7 @@ def main():
     for _ in range(args.warmup):
         step()
     torch.cuda.synchronize()
-    ref_out = out.clone()
+    ref_out = out.clone() if args.full else None
 
     ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
           for _ in range(args.steps)]
@@ -1339,14 +1400,16 @@ def main():
                           dist.barrier if distributed else None)
     kern_ms = [a.elapsed_time(b) for a, b in ev]
     elapsed_max = max_over_ranks(elapsed, coll_dev)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, "digests" if world == 1 else "digests_rank%d" % rank, out)
 
-    # parity, per rank (no oracle on the config-2 path: golden digests +
-    # step-to-step identity; config 4: sampled shard blocks vs the oracle),
+    # parity (--full), per rank (no oracle on the config-2 path: golden digests
+    # + step-to-step identity; config 4: sampled shard blocks vs the oracle),
     # then reduced over the job so the line describes every rank
     failed, reasons, nbad, checked = 0, [], 0, 0
-    if not torch.equal(out, ref_out):
+    if args.full and not torch.equal(out, ref_out):
         failed, reasons = 1, ["digests differ between steps"]
-    if workload == "config2" and nblk >= 32:
+    if args.full and workload == "config2" and nblk >= 32:
         with open(os.path.join(ROOT, "tests", "golden", "blake2b256_vectors.json")) as f:
             gold = json.load(f)["config2"]
         if bs == gold["block_size"]:
@@ -1356,7 +1419,7 @@ def main():
             checked = 32
             if nbad:
                 reasons.append("golden config-2 blocks differ")
-    if workload == "config4":
+    if args.full and workload == "config4":
         oracle_lib = load_oracle()
         nbad, checked = config4_check(oracle_lib, out.cpu().numpy(), nbytes, bs, first)
         if nbad:
@@ -1366,9 +1429,11 @@ def main():
     rows = job_summary([nbad, checked, failed, sum(kern_ms) / len(kern_ms), min(kern_ms)],
                        coll_dev)
     parity, checked_all = job_parity(rows, "; ".join(reasons) if rank == 0 else None)
+    if not args.full:
+        parity = PARITY_NOT_CHECKED
     # which GPU each rank ran on, as its driver and its own clocks see it
     devices = distinct = devices_problem = None
-    if distributed:
+    if distributed and args.full:
         try:  # every rank must reach the gather, whatever its probe did
             ident = device_identity(ca, local % ndev)
         except Exception as e:  # noqa: BLE001 - reported in the line
@@ -1377,7 +1442,7 @@ def main():
         distinct, devices_problem = devices_check(devices, args.dist_backend == "nccl")
         if devices_problem and devices_problem.startswith("FAIL"):
             parity = devices_problem if parity == "ok" else parity + "; " + devices_problem
-    valu_ms = valu_ceiling(ca, nblk, bs, stream)
+    valu_ms = valu_ceiling(ca, nblk, bs, stream) if args.full else None
 
     if rank == 0:
         # the roofline of the job's slowest rank: its average launch time
@@ -1446,14 +1511,15 @@ def main():
             # the process group's own count: every rank of the job took part
             rec["ranks_seen"] = dist.get_world_size()
             rec["dist_backend"] = args.dist_backend
+        if devices is not None:
             rec["devices_seen"] = [dict(d, rank=i) for i, d in enumerate(devices)]
             rec["devices_distinct"] = distinct
             rec["devices_note"] = devices_problem
         if ranks_per_gpu > 1:
             rec["config"]["ranks_per_gpu"] = ranks_per_gpu
-        if not distributed and not args.no_cpu_baseline:
+        if args.full and not distributed and not args.no_cpu_baseline:
             rec["cpu_baseline"] = cpu_baseline(bs, args.cpu_seconds)
-        if not distributed and not args.no_secondary:
+        if args.full and not distributed and not args.no_secondary:
             del data, out, ref_out
             torch.cuda.empty_cache()
             rec["secondary"] = run_secondary(args, ca, ctx, dev, stream)
@@ -1464,7 +1530,7 @@ def main():
         print(json.dumps(rec), flush=True)
     if distributed:
         dist.destroy_process_group()
-    return 0 if parity == "ok" else 1
+    return 0 if parity in ("ok", PARITY_NOT_CHECKED) else 1
 
 
 if __name__ == "__main__":

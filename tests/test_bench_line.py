@@ -124,6 +124,32 @@ def test_config5_leg_tree_write_failure_is_a_skip(tmp_path, monkeypatch):
     assert "No space left" in rec["skipped"] and rec["matches_oracle"] is None
 
 
+def test_plain_run_is_the_default_and_full_is_an_option(monkeypatch):
+    """Without --full the line is the headline figure alone; the checks, the
+    CPU baseline and the secondary configs wait for --full."""
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "7", "--warmup", "2"])
+    a = bench.parse()
+    assert a.full is False and a.dump_outputs is None and (a.steps, a.warmup) == (7, 2)
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--dump-outputs", "d"])
+    a = bench.parse()
+    assert a.full is True and a.dump_outputs == "d"
+
+
+def test_dump_blocks_is_a_fixed_sample_within_the_size_limit():
+    """--dump-outputs keeps every block of a small run and the same seeded
+    sample (both ends included) of a large one; digests as float32 plus the
+    indices as float64 stay under 64 MB."""
+    import numpy as np
+    assert bench.dump_blocks(1000).tolist() == list(range(1000))
+    n = 1 << 20
+    a, b = bench.dump_blocks(n), bench.dump_blocks(n)
+    assert np.array_equal(a, b)
+    assert np.all(np.diff(a) > 0) and a[0] == 0 and a[-1] == n - 1
+    assert a[:64].tolist() == list(range(64)) and a[-64:].tolist() == list(range(n - 64, n))
+    assert a.size >= n // 4
+    assert a.size * (32 * 4 + 8) + 2 * 128 <= 64 * 10 ** 6
+
+
 def test_make_tree_replaces_a_tree_of_another_size(tmp_path):
     """A tree of another size left at --tree-dir (an earlier run with another
     --tree-gib) is removed before the new one is written, so the scan indexes

@@ -60,18 +60,22 @@ for s in "$@"; do
       tail -3 gpurun_out/pytest_gpu.log ;;
     dist2)  # bench.py launching two ranks itself (gloo: they share the one GPU)
       step dist2 600 python bench.py --gpus 2 --dist-backend gloo --steps 5 --warmup 1 \
+        --full \
         --blocks "${DIST_BLOCKS:-262144}" > gpurun_out/dist2.json 2> gpurun_out/dist2.err
       cat gpurun_out/dist2.json ;;
     dist4)  # bench.py launching four ranks itself (gloo: they share the one GPU)
       step dist4 600 python bench.py --gpus 4 --dist-backend gloo --steps 5 --warmup 1 \
+        --full \
         --blocks "${DIST_BLOCKS:-262144}" > gpurun_out/dist4.json 2> gpurun_out/dist4.err
       cat gpurun_out/dist4.json ;;
     bench)  # the driver's command
       step bench 600 python3 bench.py --gpus 1 --steps 20 --warmup 5 > gpurun_out/bench.json \
+        --full \
         2> gpurun_out/bench.err
       cat gpurun_out/bench.json ;;
     forcedist)  # the N>1 code path (process group over RCCL, config 4) on one self-launched rank
       step forcedist 600 python3 bench.py --gpus 1 --force-dist --steps 20 --warmup 3 \
+        --full \
         > gpurun_out/forcedist.json 2> gpurun_out/forcedist.err
       cat gpurun_out/forcedist.json ;;
     cfg5footer)  # config 5 with the footer on the host thread and on the GPU chain, alternating
@@ -126,6 +130,7 @@ for s in "$@"; do
       # the driver's own bench command, under the profiler
       step prof 600 rocprofv3 --kernel-trace --stats --output-format csv \
         -d gpurun_out/prof -o run -- python3 bench.py --gpus 1 --steps 20 --warmup 5 \
+        --full \
         > gpurun_out/prof.log 2>&1
       find gpurun_out/prof -name '*stats*' | head ;;
     pmc)
@@ -248,6 +253,7 @@ stdout=subprocess.DEVNULL); print('cli wall %.3f s' % (time.time() - t), file=sy
     dist1)
       step dist1 600 python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 \
         --master-addr 127.0.0.1 --master-port 29511 bench.py --gpus 1 --steps 5 --warmup 1 --force-dist \
+        --full \
         --no-cpu-baseline > gpurun_out/dist1.json 2> gpurun_out/dist1.err
       cat gpurun_out/dist1.json ;;
     asmg)
