@@ -23,6 +23,10 @@ Context.verify_blocks[_dev]     FetchBlock::poll's `hash_bytes(..) == blk.hash`
 Context.verify_submit / poll /  the same check per block, batched by the library,
   wait / forget / limits        bounded (CIR_EAGAIN backpressure, forgotten tickets)
 Context.check_file              Hashes::check_file (src/daemon/disk/commit.rs:104)
+Context.check_index,            commit_image's re-hash loop over a whole image, batched
+  check_index                   (src/daemon/disk/commit.rs:51-117)
+Context.verify_first_dev        the same compare on the device, answering only "which
+                                block first" (src/daemon/disk/commit.rs:51-117)
 =============================  ==============================================
 
 All hashing runs on gfx950 through the library; there is no CPU fallback.
@@ -38,6 +42,7 @@ __all__ = [
     "BlockHash", "ImageId", "HashType", "Hashes", "ScannerConfig", "v1", "get_hash",
     "InMemoryIndexes", "ThreadedBlockReader", "BlockHint", "Context", "default_context",
     "IndexError_", "DirError", "ReadError", "CiruelaError", "NoDevice", "sha512_256",
+    "check_index", "CheckResult",
 ]
 
 DEFAULT_BLOCK_SIZE = 32768
@@ -232,6 +237,16 @@ class Context:
                                                       d_len, nblk, d_expected, d_digests, d_ok,
                                                       d_nbad, stream))
 
+    def verify_first_dev(self, d_arena, arena_bytes, d_off, d_len, nblk, d_expected, d_digests,
+                         d_first, d_nbad=0, stream=0, hash_type=None):
+        """verify_blocks_dev_bounded answering only "which block first":
+        *d_first (device u64) = the smallest mismatching or out-of-range b,
+        2^64-1 when none; *d_nbad (device u32, optional) = how many.  Both
+        are written by the call.  arena_bytes = 2^64-1: trusted descriptors."""
+        ht = (hash_type or HashType.blake2b_256()).code
+        _n.check(_n.lib.cir_verify_first_dev(self._h, ht, d_arena, arena_bytes, d_off, d_len,
+                                             nblk, d_expected, d_digests, d_first, d_nbad, stream))
+
     # ---- asynchronous per-block verify (FetchBlock::poll, fetch_blocks.rs:77)
     def verify_submit(self, data, expected, hash_type=None):
         """Queue one block with its expected digest; returns a ticket."""
@@ -288,6 +303,33 @@ class Context:
         ok = ctypes.c_int()
         _n.check(_n.lib.cir_check_file(self._h, ht, fd, block_size, exp, n, ctypes.byref(ok)))
         return ok.value == 1
+
+    CHECK_STATS_FIELDS = ("files", "blocks", "bytes", "batches", "empty_entries", "peak_fds",
+                          "errno", "first_bad_block")
+
+    def check_index(self, root, index, threads=0, dir_fd=None):
+        """commit_image's re-hash loop (src/daemon/disk/commit.rs:51-117) over
+        the image at `root` (relative to dir_fd when given; root=None: dir_fd
+        itself) against `index`, in one call: a CheckResult with the first
+        failing entry in index order, or ok."""
+        if len(index):
+            ptr, keep = _buf(index)
+        else:  # (an empty index is a parse error, not a null argument)
+            keep = ctypes.create_string_buffer(1)
+            ptr = ctypes.cast(keep, ctypes.c_void_p)
+        kind = ctypes.c_int()
+        path = ctypes.c_void_p()
+        plen = ctypes.c_size_t()
+        stats = (ctypes.c_uint64 * _n.CIR_CHECK_STATS_FIELDS)()
+        if root is None and dir_fd is None:
+            raise ValueError("check_index needs a root path or a directory fd")
+        fd = -100 if dir_fd is None else dir_fd  # AT_FDCWD
+        _n.check(_n.lib.cir_check_index(self._h, fd, None if root is None else os.fsencode(root),
+                                        ptr, len(index), threads, ctypes.byref(kind),
+                                        ctypes.byref(path), ctypes.byref(plen), stats))
+        del keep
+        raw = _n.take_buffer(path.value, plen.value) if path.value else None
+        return CheckResult(kind.value, raw, dict(zip(self.CHECK_STATS_FIELDS, list(stats))))
 
     def scan(self, config):
         dirs = [os.fsencode(d) for d, _ in config._dirs]
@@ -373,6 +415,31 @@ class Context:
                                           ctypes.byref(ln)))
         del keep
         return _n.take_buffer(out.value, ln.value)
+
+
+class CheckResult:
+    """Verdict of check_index: ok, or the first failing entry in index order
+    -- kind "checksum" (Error::Checksum) or "read" (Error::ReadFile, with
+    errno), path as the index's raw bytes -- and the call's stats."""
+
+    __slots__ = ("kind", "path", "errno", "stats")
+    KINDS = {_n.CIR_CHECK_OK: "ok", _n.CIR_CHECK_CHECKSUM: "checksum", _n.CIR_CHECK_READ: "read"}
+
+    def __init__(self, kind, path, stats):
+        self.kind = self.KINDS[kind]
+        self.path = path
+        self.errno = stats["errno"]
+        self.stats = stats
+
+    @property
+    def ok(self):
+        return self.kind == "ok"
+
+    def __bool__(self):
+        return self.ok
+
+    def __repr__(self):
+        return "CheckResult(%s%s)" % (self.kind, "" if self.ok else ", %r" % (self.path,))
 
 
 _default = None
@@ -594,6 +661,11 @@ def sha512_256(data):
     _n.check(_n.lib.cir_sha512_256(ptr, len(data), out))
     del keep
     return out.raw
+
+
+def check_index(root, index, threads=0, dir_fd=None, context=None):
+    """Context.check_index on the default context."""
+    return (context or default_context()).check_index(root, index, threads, dir_fd)
 
 
 def get_hash(index):

@@ -46,6 +46,10 @@ CIR_EUNSUPPORTED = -9
 CIR_EAGAIN = -10
 CIR_VERIFY_NONBLOCK = 1
 CIR_VERIFY_STATS_FIELDS = 8
+CIR_CHECK_OK = 0
+CIR_CHECK_CHECKSUM = 1
+CIR_CHECK_READ = 2
+CIR_CHECK_STATS_FIELDS = 8
 CIR_INIT_ONE_SHOT = 1  # cir_init_n: one stream and one staging slot per device
 CIR_STAGING_LAZY = (1 << 64) - 1  # cir_init: no staging slots until a host path needs them
 
@@ -125,6 +129,11 @@ _SIGS = {
                                                      c_vp, c_vp]),
     "cir_check_file": (ctypes.c_int, [c_vp, ctypes.c_int, ctypes.c_int, ctypes.c_uint64, c_vp,
                                       ctypes.c_size_t, ctypes.POINTER(ctypes.c_int)]),
+    "cir_verify_first_dev": (ctypes.c_int, [c_vp, ctypes.c_int, c_vp, ctypes.c_uint64, c_vp, c_vp,
+                                            ctypes.c_size_t, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    "cir_check_index": (ctypes.c_int, [c_vp, ctypes.c_int, ctypes.c_char_p, c_vp, ctypes.c_size_t,
+                                       ctypes.c_uint32, ctypes.POINTER(ctypes.c_int),
+                                       ctypes.POINTER(c_vp), c_sizep, c_u64p]),
     "cir_debug_compress_only_dev": (ctypes.c_int, [ctypes.c_uint64, ctypes.c_uint32, c_vp, c_vp]),
     "cir_debug_relay_blocks": (ctypes.c_uint64, [ctypes.c_uint64, ctypes.c_uint64]),
     "cir_debug_device_identity": (ctypes.c_int, [ctypes.c_int, ctypes.c_char_p, ctypes.c_size_t,

@@ -1,0 +1,651 @@
+// cir_check_index: the re-hash loop of commit_image over a whole image.
+//
+// Reference: commit_image (src/daemon/disk/commit.rs:51-117) walks the
+// index's entries in order, re-hashes every non-empty file
+// (Hashes::check_file, :104) and fails with Error::Checksum(path) at the
+// first file that does not match (:108-111), at an "empty" file that is not
+// empty (:79-81), or with Error::ReadFile at one it cannot open or read
+// (:98-106).  Here the whole image goes through the scan's staging pipeline
+// (scan.cpp hash_range: file segments packed into pinned slots by reader
+// threads, three slots in flight) in a check mode: a batch's expected digests
+// travel up with its descriptors, the batch is hashed and compared on the
+// device (kernels.hip k_first_bad) and 16 bytes come back per batch.
+//
+// Order.  Every file entry has a place in the index's order and every block
+// of a non-empty file a global index g (blocks counted in index order, from
+// the index alone).  A failure's key is (entry, g): for a bad block its file
+// and its g, for a failure met on the host (a file that cannot be opened, a
+// length that differs, a non-empty "empty" file) the entry and the g at
+// which the packer met it.  The verdict is the smallest key.  One device
+// packs in index order and retires batches in submission order, so when it
+// meets a host-side failure every earlier block is packed: it stops packing,
+// drains what is in flight, and the smallest key reported wins.  With several
+// devices (stripes of the global block order dealt round-robin, as
+// hash_files deals them) each device does the same over its stripes and may
+// stop early only when a failure already known lies below everything it has
+// yet to pack -- so whatever the timing, nothing below the final minimum is
+// ever skipped and the verdict does not depend on it.
+//
+// Descriptors.  A batch may hold thousands of one-block files, so no fd is
+// kept per packed file: the packer opens each file (openat in its directory,
+// O_NOFOLLOW), fstats it, remembers (st_dev, st_ino, st_size) and closes it;
+// a reader thread opens it again the same way -- every directory component
+// with openat(O_DIRECTORY | O_NOFOLLOW) below the root fd, never by a path
+// -- and reads only if fstat shows the same file.  Each packer holds one
+// directory fd and each reader one directory and one file fd.
+#include <errno.h>
+#include <fcntl.h>
+#include <limits.h>
+#include <stdlib.h>
+#include <string.h>
+#include <sys/stat.h>
+#include <unistd.h>
+
+#include <algorithm>
+#include <atomic>
+#include <mutex>
+#include <string>
+#include <vector>
+
+#include "dirsig.hpp"
+#include "runtime.hpp"
+#include "stripes.hpp"
+
+namespace cir {
+namespace {
+
+constexpr uint64_t kNone = ~0ull;
+// (scan.cpp's read piece: `threads` readers stay busy on large files)
+constexpr uint64_t kReadPiece = 4ull << 20;
+
+// The fds the check itself holds, and their peak (stats[5]).
+struct FdCount {
+  std::atomic<uint64_t> cur{0}, peak{0};
+  int took(int fd) {
+    if (fd >= 0) {
+      const uint64_t c = cur.fetch_add(1) + 1;
+      uint64_t p = peak.load();
+      while (c > p && !peak.compare_exchange_weak(p, c)) {
+      }
+    }
+    return fd;
+  }
+  void close(int fd) {
+    if (fd < 0) return;
+    ::close(fd);
+    cur.fetch_sub(1);
+  }
+};
+
+// One file entry of the index, in index order.
+struct Item {
+  size_t entry = 0;        // index into Index::entries
+  size_t dir = 0;          // index into Image::dirs
+  std::string name;        // the entry's name in its directory
+  uint64_t size = 0;
+  uint64_t nblk = 0;
+  uint64_t first_blk = 0;  // global index of block 0 (an empty file: the next file's)
+};
+
+struct Failure {
+  size_t item = SIZE_MAX;
+  uint64_t blk = kNone;  // second half of the key
+  int kind = CIR_CHECK_OK;
+  int err = 0;
+  uint64_t bad_blk = kNone;  // the first bad block, when that is what failed
+  bool before(size_t it, uint64_t b) const { return item < it || (item == it && blk < b); }
+};
+
+struct Image {
+  const dirsig::Index* idx = nullptr;
+  uint64_t bs = 0;
+  int ht = CIR_HASH_BLAKE2B_256;
+  int root = -1;
+  std::vector<std::vector<std::string>> dirs;  // a directory line's components below the root
+  std::vector<Item> items;
+  uint64_t nblk_total = 0;
+  FdCount fds;
+  // the smallest failure reported so far
+  std::mutex mu;
+  Failure best;
+  std::atomic<uint64_t> n_files{0}, n_blocks{0}, n_bytes{0}, n_batches{0}, n_empty{0};
+
+  void report(const Failure& f) {
+    std::lock_guard<std::mutex> lk(mu);
+    if (f.before(best.item, best.blk)) best = f;
+  }
+  // a failure is known below (it, b): nothing from there on can be the verdict
+  bool decided_before(size_t it, uint64_t b) {
+    std::lock_guard<std::mutex> lk(mu);
+    return best.before(it, b);
+  }
+  // the non-empty file that holds global block g
+  size_t item_of(uint64_t g) const {
+    size_t i = std::upper_bound(items.begin(), items.end(), g,
+                                [](uint64_t b, const Item& x) { return b < x.first_blk; }) -
+               items.begin();
+    // (empty files share the next file's first_blk and sort before it: the
+    // last item whose first_blk <= g is the file itself)
+    return i - 1;
+  }
+};
+
+// A directory below the root, opened one component at a time, never through
+// a symlink.  No components: the root fd itself (not ours to close).
+struct DirFd {
+  int fd = -1;
+  bool own = false;
+  int err = 0;  // errno when fd < 0
+};
+
+DirFd open_dir(Image& im, const std::vector<std::string>& comps) {
+  DirFd d;
+  d.fd = im.root;
+  for (const std::string& c : comps) {
+    const int nfd = im.fds.took(
+        ::openat(d.fd, c.c_str(), O_RDONLY | O_DIRECTORY | O_NOFOLLOW | O_CLOEXEC));
+    const int e = errno;
+    if (d.own) im.fds.close(d.fd);
+    if (nfd < 0) {
+      d.fd = -1;
+      d.own = false;
+      d.err = e;
+      return d;
+    }
+    d.fd = nfd;
+    d.own = true;
+  }
+  return d;
+}
+
+void close_dir(Image& im, DirFd& d) {
+  if (d.own) im.fds.close(d.fd);
+  d = DirFd();
+}
+
+// What the packer saw of a file it is about to pack.
+struct Seen {
+  dev_t dev = 0;
+  ino_t ino = 0;
+};
+
+// openat + fstat of a listed non-empty file: 0 with *fd_out open, or the
+// failure's kind with *err.  (O_NONBLOCK: a fifo in the file's place fails
+// the fstat test below instead of blocking the open.)
+int open_listed(Image& im, const DirFd& d, const Item& it, int* fd_out, struct stat* st, int* err) {
+  *fd_out = -1;
+  *err = 0;
+  if (d.fd < 0) {
+    *err = d.err;
+    return CIR_CHECK_READ;
+  }
+  const int fd = im.fds.took(
+      ::openat(d.fd, it.name.c_str(), O_RDONLY | O_NOFOLLOW | O_CLOEXEC | O_NONBLOCK));
+  if (fd < 0) {
+    *err = errno;
+    return CIR_CHECK_READ;
+  }
+  if (::fstat(fd, st) != 0) {
+    *err = errno;
+    im.fds.close(fd);
+    return CIR_CHECK_READ;
+  }
+  if (!S_ISREG(st->st_mode)) {
+    *err = S_ISDIR(st->st_mode) ? EISDIR : EINVAL;
+    im.fds.close(fd);
+    return CIR_CHECK_READ;
+  }
+  *fd_out = fd;
+  return CIR_CHECK_OK;
+}
+
+// A size-0 entry (commit.rs:57-90): absent passes (the caller creates it),
+// present it must be an empty regular file.
+int examine_empty(const DirFd& d, const Item& it, int* err) {
+  *err = 0;
+  if (d.fd < 0) {
+    if (d.err == ENOENT) return CIR_CHECK_OK;
+    *err = d.err;
+    return CIR_CHECK_READ;
+  }
+  struct stat st;
+  if (::fstatat(d.fd, it.name.c_str(), &st, AT_SYMLINK_NOFOLLOW) != 0) {
+    if (errno == ENOENT) return CIR_CHECK_OK;
+    *err = errno;
+    return CIR_CHECK_READ;
+  }
+  return S_ISREG(st.st_mode) && st.st_size == 0 ? CIR_CHECK_OK : CIR_CHECK_CHECKSUM;
+}
+
+// A non-empty entry before it is packed: READ, CHECKSUM on a length that is
+// not the index's (the verdict cir_check_file gives: wrong block count, or a
+// last block that cannot match), else what identifies the file to the readers.
+int examine_file(Image& im, const DirFd& d, const Item& it, Seen* seen, int* err) {
+  int fd = -1;
+  struct stat st;
+  const int kind = open_listed(im, d, it, &fd, &st, err);
+  if (kind) return kind;
+  im.fds.close(fd);
+  if ((uint64_t)st.st_size != it.size) return CIR_CHECK_CHECKSUM;
+  seen->dev = st.st_dev;
+  seen->ino = st.st_ino;
+  return CIR_CHECK_OK;
+}
+
+struct ReadJob {
+  size_t item;
+  Seen seen;
+  uint64_t file_off, len;
+  uint8_t* dst;
+  uint64_t seg_blk;  // the batch's block index where this item's segment starts
+  uint64_t seg_pos;  // and its byte offset in the slot
+};
+
+// Read the batch's jobs on `threads` readers.  Returns the index of the first
+// job (in job order, whatever the timing: a reader skips only jobs after a
+// failed one) that failed, with its errno, or jobs.size().
+size_t run_reads(Image& im, const std::vector<ReadJob>& jobs, unsigned threads, int* err_out) {
+  std::atomic<size_t> next{0}, first_bad{jobs.size()};
+  std::mutex mu;
+  int first_err = 0;
+  const bool nt = stage_copy_nt();
+  auto worker = [&] {
+    DirFd d;  // this reader's directory, kept across the jobs that share it
+    size_t d_dir = SIZE_MAX;
+    for (;;) {
+      const size_t i = next.fetch_add(1);
+      if (i >= jobs.size() || i > first_bad.load()) break;
+      const ReadJob& j = jobs[i];
+      const Item& it = im.items[j.item];
+      if (d_dir != it.dir) {
+        close_dir(im, d);
+        d = open_dir(im, im.dirs[it.dir]);
+        d_dir = it.dir;
+      }
+      int fd = -1, e = 0;
+      struct stat st;
+      bool ok = open_listed(im, d, it, &fd, &st, &e) == CIR_CHECK_OK;
+      if (ok && (st.st_dev != j.seen.dev || st.st_ino != j.seen.ino ||
+                 (uint64_t)st.st_size != it.size)) {
+        ok = false;  // not the file that was packed
+        e = ESTALE;
+      }
+      uint64_t got = 0;
+      while (ok && got < j.len) {
+        const ssize_t r =
+            pread_staged(fd, j.dst + got, j.len - got, (off_t)(j.file_off + got), nt);
+        if (r < 0 && errno == EINTR) continue;
+        if (r <= 0) {
+          ok = false;
+          e = r == 0 ? ENODATA : errno;  // the file shrank under the read
+          break;
+        }
+        got += (uint64_t)r;
+      }
+      im.fds.close(fd);
+      if (!ok) {
+        std::lock_guard<std::mutex> lk(mu);
+        if (i < first_bad.load()) {
+          first_bad.store(i);
+          first_err = e;
+        }
+      }
+    }
+    close_dir(im, d);
+  };
+  parallel_run(std::max(1u, std::min<unsigned>(threads, (unsigned)jobs.size())), worker);
+  *err_out = first_err;
+  return first_bad.load();
+}
+
+using BlockRanges = std::vector<std::pair<uint64_t, uint64_t>>;
+
+// hash_range (scan.cpp) in check mode: the block ranges `ranges` (increasing)
+// on device d, with the entries each range owns -- those whose first block
+// lies in it, the trailing empty files with the last range -- examined in
+// order as the packer reaches them.  Every failure goes to im.report().
+int check_range(cir_ctx* ctx, Device& d, Image& im, unsigned threads, const BlockRanges& ranges) {
+  if (ranges.empty()) return CIR_OK;
+  std::lock_guard<std::mutex> lk(d.mu);
+  DeviceGuard guard;
+  CIR_HIP(hipSetDevice(d.id));
+  SlotDrain drain{d};  // an early return leaves no slot busy
+  const std::vector<Item>& items = im.items;
+  const uint64_t bs = im.bs;
+  uint64_t seg = 0;
+  for (const Item& it : items) seg = std::max(seg, std::min<uint64_t>(it.size, bs));
+  const uint64_t cap = (std::max<uint64_t>(ctx->staging, seg + 16) + 15) & ~15ull;
+  const uint64_t cap_blk = std::max<uint64_t>(cap / 512, 4096);
+  uint64_t fill = scan_ramp() ? std::max<uint64_t>(seg + 16, cap >> 3) : cap;
+
+  size_t ri = 0;
+  uint64_t b0 = 0, b1 = 0;
+  size_t ii = 0;           // the item being packed
+  uint64_t fblk = 0;       // its next block
+  size_t examined = SIZE_MAX;  // the item whose host-side look passed (in this range)
+  Seen seen;
+  bool stopped = false;    // nothing further is packed
+  DirFd cur;               // the packer's directory
+  size_t cur_dir = SIZE_MAX;
+  struct CloseCur {
+    Image& im;
+    DirFd& d;
+    ~CloseCur() { close_dir(im, d); }
+  } close_cur{im, cur};
+  auto dir_of = [&](const Item& it) -> const DirFd& {
+    if (cur_dir != it.dir) {
+      close_dir(im, cur);
+      cur = open_dir(im, im.dirs[it.dir]);
+      cur_dir = it.dir;
+    }
+    return cur;
+  };
+  auto start_range = [&](size_t r) {
+    ri = r;
+    b0 = ranges[r].first;
+    b1 = ranges[r].second;
+    // the first item at or past b0, or the file b0 falls inside
+    ii = std::lower_bound(items.begin(), items.end(), b0,
+                          [](const Item& x, uint64_t b) { return x.first_blk < b; }) -
+         items.begin();
+    fblk = 0;
+    if (ii > 0 && items[ii - 1].first_blk + items[ii - 1].nblk > b0) {
+      --ii;
+      fblk = b0 - items[ii].first_blk;
+    }
+    examined = SIZE_MAX;
+  };
+  // is items[ii] (from block fblk on) this range's to look at?
+  auto here = [&] {
+    if (ii >= items.size()) return false;
+    const uint64_t at = items[ii].first_blk + fblk;
+    return at < b1 || (b1 == im.nblk_total && at == b1 && items[ii].nblk == 0);
+  };
+  auto more = [&] {
+    if (stopped) return false;
+    while (!here()) {
+      if (ri + 1 >= ranges.size()) return false;
+      start_range(ri + 1);
+    }
+    return true;
+  };
+  auto busy = [&] {
+    for (const Slot& s : d.slot)
+      if (s.busy) return true;
+    return false;
+  };
+  auto fail_here = [&](int kind, int err) {
+    Failure f;
+    f.item = ii;
+    f.blk = items[ii].first_blk + fblk;
+    f.kind = kind;
+    f.err = err;
+    im.report(f);
+    stopped = true;
+  };
+  start_range(0);
+  constexpr int kS = Device::kSlots;
+  int k = 0;
+  while (more() || busy()) {
+    Slot& s = d.slot[k];
+    if (s.busy) {
+      int rc = slot_wait(d, s);
+      if (rc) return rc;
+      const uint64_t first = s.h_cell[0];
+      if (first != kNone) {
+        Failure f;
+        f.item = im.item_of(first);
+        f.blk = first;
+        f.kind = CIR_CHECK_CHECKSUM;
+        f.bad_blk = first;
+        im.report(f);
+        stopped = true;  // what is still in flight lies above it and is only drained
+      }
+    }
+    // (another device's failure below everything left here ends this one)
+    if (more() && im.decided_before(ii, items[ii].first_blk + fblk)) stopped = true;
+    if (more()) {
+      int rc = d.ensure_slot(s, cap, cap_blk);
+      if (rc) return rc;
+      rc = d.ensure_check(s);
+      if (rc) return rc;
+      std::vector<ReadJob> jobs;
+      uint64_t pos = 0, n = 0, used = 0;
+      const uint64_t first = items[ii].first_blk + fblk;
+      uint64_t new_files = 0, file_bytes = 0;
+      while (!stopped && here() && n < cap_blk) {
+        const Item& it = items[ii];
+        const DirFd& dfd = dir_of(it);
+        if (it.nblk == 0) {
+          int err = 0;
+          const int kind = examine_empty(dfd, it, &err);
+          if (kind) {
+            fail_here(kind, err);
+            break;
+          }
+          im.n_empty.fetch_add(1);
+          ++ii;
+          continue;
+        }
+        if (examined != ii) {
+          int err = 0;
+          const int kind = examine_file(im, dfd, it, &seen, &err);
+          if (kind) {
+            fail_here(kind, err);
+            break;
+          }
+          examined = ii;
+        }
+        const uint64_t left_blk = std::min<uint64_t>(it.nblk - fblk, b1 - (it.first_blk + fblk));
+        pos = (pos + 15) & ~15ull;
+        if (pos + std::min<uint64_t>(bs, it.size - fblk * bs) > fill) break;
+        uint64_t take = std::min<uint64_t>(left_blk, cap_blk - n);
+        take = std::min<uint64_t>(take, std::max<uint64_t>((fill - pos) / bs, 1));
+        const uint64_t off0 = fblk * bs;
+        const uint64_t bytes = std::min<uint64_t>(take * bs, it.size - off0);
+        if (pos + bytes > fill) break;
+        for (uint64_t j = 0; j < take; ++j) {
+          s.h_off[n + j] = pos + j * bs;
+          s.h_len[n + j] = (uint32_t)std::min<uint64_t>(bs, it.size - off0 - j * bs);
+        }
+        // the index's digests of these blocks, in block order (nothing comes
+        // back through h_out in this mode: it carries them up)
+        memcpy(s.h_out + 32 * n, im.idx->entries[it.entry].hashes.data() + 32 * fblk, 32 * take);
+        for (uint64_t piece = 0; piece < bytes; piece += kReadPiece)
+          jobs.push_back({ii, seen, off0 + piece, std::min<uint64_t>(kReadPiece, bytes - piece),
+                          s.h_data + pos + piece, n, pos});
+        if (fblk == 0) ++new_files;
+        file_bytes += bytes;
+        pos += bytes;
+        used = pos;
+        n += take;
+        fblk += take;
+        if (fblk == it.nblk) {
+          ++ii;
+          fblk = 0;
+        }
+      }
+      fill = std::min(cap, fill * 2);
+      if (n > 0) {
+        int rerr = 0;
+        const size_t bad = run_reads(im, jobs, threads, &rerr);
+        if (bad < jobs.size()) {
+          // READ at that file: the batch keeps the blocks before its segment
+          // (any of them may still be the verdict), nothing further is packed
+          const ReadJob& j = jobs[bad];
+          Failure f;
+          f.item = j.item;
+          f.blk = first + j.seg_blk;
+          f.kind = CIR_CHECK_READ;
+          f.err = rerr;
+          im.report(f);
+          stopped = true;
+          n = j.seg_blk;
+          used = j.seg_pos;
+        }
+      }
+      if (n > 0) {
+        rc = slot_submit_check(d, s, std::max<uint64_t>(used, 16), n, im.ht, first);
+        if (rc) return rc;
+        im.n_files.fetch_add(new_files);
+        im.n_blocks.fetch_add(n);
+        im.n_bytes.fetch_add(file_bytes);
+        im.n_batches.fetch_add(1);
+      }
+    }
+    k = (k + 1) % kS;
+  }
+  return CIR_OK;
+}
+
+int check_impl(cir_ctx* ctx, int dirfd, const char* dir, const uint8_t* index, size_t len,
+               uint32_t threads, int* kind_out, uint8_t** path_out, size_t* path_len,
+               uint64_t* stats) {
+  if (!ctx || !index || !kind_out || !path_out || !path_len || !stats)
+    return fail(CIR_EINVAL, "null pointer");
+  *kind_out = CIR_CHECK_OK;
+  *path_out = nullptr;
+  *path_len = 0;
+  for (int i = 0; i < CIR_CHECK_STATS_FIELDS; ++i) stats[i] = 0;
+  stats[7] = kNone;
+  dirsig::Index idx;
+  std::string err;
+  if (!dirsig::parse(index, len, &idx, &err))
+    return idx.bad_hash_size ? fail(CIR_EHASHSIZE, "hash size is unsupported: " + err)
+                             : fail(CIR_EPARSE, "error parsing index: " + err);
+  if (dirsig::digest_len(idx.header.hash) != 32)
+    return fail(CIR_EHASHSIZE, "hash size is unsupported");
+  if (idx.header.block_size > 0xffffffffull)
+    return fail(CIR_EINVAL, "block_size must be in 1 .. 2^32-1");
+  Image im;
+  im.idx = &idx;
+  im.bs = idx.header.block_size;
+  im.ht = idx.header.hash == dirsig::HashType::kSha512_256 ? CIR_HASH_SHA512_256
+                                                            : CIR_HASH_BLAKE2B_256;
+  // the entries' places: directory lines as components, files with the
+  // global index of their first block
+  for (size_t e = 0; e < idx.entries.size(); ++e) {
+    const dirsig::Entry& en = idx.entries[e];
+    if (en.kind == dirsig::EntryKind::kDir) {
+      std::vector<std::string> comps;
+      size_t i = 0;
+      while (i < en.path.size()) {
+        size_t j = en.path.find('/', i);
+        if (j == std::string::npos) j = en.path.size();
+        if (j > i) comps.push_back(en.path.substr(i, j - i));
+        i = j + 1;
+      }
+      im.dirs.push_back(std::move(comps));
+    } else if (en.kind == dirsig::EntryKind::kFile) {
+      if (im.dirs.empty()) return fail(CIR_EPARSE, "error parsing index: entry before a directory");
+      Item it;
+      it.entry = e;
+      it.dir = im.dirs.size() - 1;
+      it.name = en.path.substr(en.path.rfind('/') + 1);
+      it.size = en.size;
+      it.nblk = en.hashes.size() / 32;
+      it.first_blk = im.nblk_total;
+      im.nblk_total += it.nblk;
+      im.items.push_back(std::move(it));
+    }
+    // symlink entries are the caller's to create (commit.rs:118-126)
+  }
+  struct CloseRoot {
+    Image& im;
+    bool own = false;
+    ~CloseRoot() {
+      if (own) im.fds.close(im.root);
+    }
+  } close_root{im};
+  if (dir) {
+    im.root = im.fds.took(::openat(dirfd, dir, O_RDONLY | O_DIRECTORY | O_CLOEXEC));
+    if (im.root < 0)
+      return fail(CIR_EIO, std::string("error opening image ") + dir + ": " + strerror(errno));
+    close_root.own = true;
+  } else {
+    struct stat st;
+    if (::fstat(dirfd, &st) != 0 || !S_ISDIR(st.st_mode))
+      return fail(CIR_EIO, "image root fd is not a directory");
+    im.root = dirfd;
+  }
+  if (threads == 0) threads = host_copy_threads(ctx->devs.size());
+
+  int rc = CIR_OK;
+  const size_t nd = std::min<size_t>(ctx->devs.size(), (size_t)std::max<uint64_t>(im.nblk_total, 1));
+  if (im.nblk_total == 0) {
+    // only size-0 entries (or none): nothing for a device
+    DirFd cur;
+    size_t cur_dir = SIZE_MAX;
+    for (size_t i = 0; i < im.items.size(); ++i) {
+      const Item& it = im.items[i];
+      if (cur_dir != it.dir) {
+        close_dir(im, cur);
+        cur = open_dir(im, im.dirs[it.dir]);
+        cur_dir = it.dir;
+      }
+      int e = 0;
+      const int kind = examine_empty(cur, it, &e);
+      if (kind) {
+        Failure f;
+        f.item = i;
+        f.blk = 0;
+        f.kind = kind;
+        f.err = e;
+        im.report(f);
+        break;
+      }
+      im.n_empty.fetch_add(1);
+    }
+    close_dir(im, cur);
+  } else if (nd <= 1) {
+    rc = check_range(ctx, *ctx->devs[0], im, threads, {{0, im.nblk_total}});
+  } else {
+    uint64_t stripe = std::max<uint64_t>(1, ctx->staging / im.bs);
+    if (const char* e = getenv("CIR_DEBUG_STRIPE_BLOCKS"))  // tests: stripes of a few blocks
+      if (atoll(e) > 0) stripe = (uint64_t)atoll(e);
+    const StripePrefix order(im.nblk_total, stripe);
+    std::vector<BlockRanges> dev_ranges(nd);
+    for (size_t st = 0; st < order.stripes(); ++st)
+      dev_ranges[st % nd].push_back({st * stripe, st * stripe + order.stripe_len(st)});
+    const unsigned per = std::max(1u, threads / (unsigned)nd);
+    std::vector<int> rcs(nd, 0);
+    std::vector<std::string> errs(nd);
+    fan_out(nd, [&](size_t i) {
+      rcs[i] = check_range(ctx, *ctx->devs[i], im, per, dev_ranges[i]);
+      if (rcs[i]) errs[i] = cir_last_error();
+    });
+    for (size_t i = 0; i < nd && !rc; ++i)
+      if (rcs[i]) rc = fail(rcs[i], errs[i]);
+  }
+  stats[5] = im.fds.peak.load();
+  if (rc) return rc;
+  const Failure& f = im.best;
+  if (f.kind != CIR_CHECK_OK) {
+    const std::string& p = idx.entries[im.items[f.item].entry].path;
+    uint8_t* out = (uint8_t*)malloc(p.size() + 1);
+    if (!out) return fail(CIR_ENOMEM, "malloc");
+    memcpy(out, p.data(), p.size());
+    out[p.size()] = 0;
+    *path_out = out;
+    *path_len = p.size();
+    *kind_out = f.kind;
+    stats[6] = f.kind == CIR_CHECK_READ ? (uint64_t)f.err : 0;
+    stats[7] = f.bad_blk;
+    return CIR_OK;
+  }
+  stats[0] = im.n_files.load();
+  stats[1] = im.n_blocks.load();
+  stats[2] = im.n_bytes.load();
+  stats[3] = im.n_batches.load();
+  stats[4] = im.n_empty.load();
+  return CIR_OK;
+}
+
+}  // namespace
+}  // namespace cir
+
+extern "C" int cir_check_index(cir_ctx* ctx, int dirfd, const char* dir, const uint8_t* index,
+                               size_t len, uint32_t threads, int* kind_out, uint8_t** path_out,
+                               size_t* path_len, uint64_t stats[CIR_CHECK_STATS_FIELDS]) try {
+  return cir::check_impl(ctx, dirfd, dir, index, len, threads, kind_out, path_out, path_len, stats);
+} CIR_CATCH_BOUNDARY

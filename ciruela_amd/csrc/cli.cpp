@@ -14,6 +14,11 @@
 //                      --append SRC:/DEST [--append-weak SRC:/DEST]
 //                      [--replace SRC:/DEST[:OLD_IMAGE_ID]] ...
 //   ciruela-index hash [--block-size N] FILE...   (per-block BlockHash list)
+//   ciruela-index check DIR INDEX_FILE [--disk-threads N]
+//       the daemon's commit-time re-hash (commit_image, src/daemon/disk/
+//       commit.rs:51-117) of the image in DIR against INDEX_FILE: silent and
+//       exit 0 when every listed file matches, else exit 1 with one line,
+//       `checksum: <path>` or `read: <path>: <strerror>`
 #include <dirent.h>
 #include <errno.h>
 #include <fcntl.h>
@@ -34,7 +39,8 @@ static void usage() {
   fprintf(stderr,
           "usage: ciruela-index sync [--disk-threads N] [--block-size N] [--index-dir D]\n"
           "                          (--append|--append-weak|--replace) SRC:/DEST ...\n"
-          "       ciruela-index hash [--block-size N] FILE...\n");
+          "       ciruela-index hash [--block-size N] FILE...\n"
+          "       ciruela-index check DIR INDEX_FILE [--disk-threads N]\n");
 }
 
 static std::string hex(const uint8_t* p, size_t n) {
@@ -193,14 +199,38 @@ int main(int argc, char** argv) {
         return 2;
       }
       jobs.push_back(j);
-    } else if (cmd == "hash" && a.size() && a[0] != '-') {
+    } else if ((cmd == "hash" || cmd == "check") && a.size() && a[0] != '-') {
       files.push_back(a);
     } else {
       usage();
       return 2;
     }
   }
+  if (cmd == "check" && files.size() != 2) {
+    usage();
+    return 2;
+  }
   std::vector<std::string> inputs = files;
+  std::vector<uint8_t> check_index;
+  if (cmd == "check") {
+    // the index is read (and a missing one reported) before any device is
+    // opened; the staging slots are sized from the image alone
+    inputs.pop_back();
+    FILE* f = fopen(files[1].c_str(), "rb");
+    if (!f) {
+      perror(files[1].c_str());
+      return 2;
+    }
+    uint8_t buf[65536];
+    size_t r;
+    while ((r = fread(buf, 1, sizeof buf, f)) > 0) check_index.insert(check_index.end(), buf, buf + r);
+    const bool bad = ferror(f) != 0;
+    fclose(f);
+    if (bad) {
+      fprintf(stderr, "%s: read error\n", files[1].c_str());
+      return 2;
+    }
+  }
   for (const Job& j : jobs) inputs.push_back(j.src);
   cir_ctx* ctx = nullptr;
   const uint64_t total = input_bytes(inputs);
@@ -266,6 +296,28 @@ int main(int argc, char** argv) {
       for (size_t k = 0; k < n; ++k) printf(" %s", hex(h + 32 * k, 32).c_str());
       printf("\n");
       cir_free(h);
+    }
+  } else if (cmd == "check") {
+    int kind = CIR_CHECK_OK;
+    uint8_t* path = nullptr;
+    size_t plen = 0;
+    uint64_t st[CIR_CHECK_STATS_FIELDS];
+    static const uint8_t none = 0;
+    rc = cir_check_index(ctx, AT_FDCWD, files[0].c_str(),
+                         check_index.empty() ? &none : check_index.data(), check_index.size(),
+                         threads, &kind, &path, &plen, st);
+    if (rc) {
+      die(rc, files[0].c_str());
+      return 2;
+    }
+    if (kind != CIR_CHECK_OK) {
+      const std::string p(reinterpret_cast<const char*>(path), plen);
+      if (kind == CIR_CHECK_CHECKSUM)
+        printf("checksum: %s\n", p.c_str());
+      else
+        printf("read: %s: %s\n", p.c_str(), strerror((int)st[6]));
+      fflush(stdout);
+      return 1;
     }
   } else if (cmd == "sync") {
     if (jobs.empty()) {

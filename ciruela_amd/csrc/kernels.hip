@@ -21,6 +21,8 @@
 //   k_general        : ragged / misaligned blocks, chunk or descriptor form.
 //   k_sha_desc       : SHA-512/256 descriptors (dir-signature's 2nd hash).
 //   k_verify         : digest compare of the daemon-side batch verify.
+//   k_first_bad      : the same compare for the commit-time check of a whole
+//                      image: only the first bad digest's index and a count.
 //   k_compress_only  : register-only compressions (live VALU ceiling).
 //   k_fill_splitmix64: synthetic test data (bench / tests only).
 //
@@ -1077,6 +1079,53 @@ hipError_t launch_verify(const uint8_t* got, const uint8_t* want, uint64_t n, ui
   if (n == 0) return hipSuccess;
   hipLaunchKernelGGL(k_verify, dim3(grid_for(n, kThreads)), dim3(kThreads), 0, s, got, want, n,
                      ok, nbad, flag);
+  return hipGetLastError();
+}
+
+// Commit-time check (commit_image's loop, src/daemon/disk/commit.rs:51-117:
+// the first file that does not match fails the image): which digest is the
+// first bad one, and how many are.  One lane per digest as in k_verify; a
+// wave with a mismatch issues one atomicMin (base + its first bad lane's
+// index) and one atomicAdd, a clean wave touches no atomic, and no per-block
+// result is written.  The cell is initialised by k_cell_init on the same
+// stream (launch_first_bad).
+__global__ void k_cell_init(unsigned long long* __restrict__ first, uint32_t* __restrict__ nbad) {
+  if (threadIdx.x == 0) {
+    *first = ~0ull;
+    if (nbad) *nbad = 0;
+  }
+}
+
+__global__ void k_first_bad(const uint8_t* __restrict__ got, const uint8_t* __restrict__ want,
+                            uint64_t n, uint64_t base, unsigned long long* __restrict__ first,
+                            uint32_t* __restrict__ nbad, const uint8_t* __restrict__ flag) {
+  const uint64_t b = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  bool bad = false;
+  if (b < n) {
+    const uint4* g = reinterpret_cast<const uint4*>(got + 32 * b);
+    const uint4* w = reinterpret_cast<const uint4*>(want + 32 * b);
+    const uint4 g0 = g[0], g1 = g[1], w0 = w[0], w1 = w[1];
+    const uint32_t diff = (g0.x ^ w0.x) | (g0.y ^ w0.y) | (g0.z ^ w0.z) | (g0.w ^ w0.w) |
+                          (g1.x ^ w1.x) | (g1.y ^ w1.y) | (g1.z ^ w1.z) | (g1.w ^ w1.w);
+    bad = diff != 0 || (flag && flag[b]);
+  }
+  const uint64_t mask = __ballot(bad);
+  // (kThreads is a multiple of the wave size: lane 0's b is the wave's first index)
+  if (mask && (threadIdx.x & 63) == 0) {
+    atomicMin(first, (unsigned long long)(base + b + (uint64_t)__builtin_ctzll(mask)));
+    if (nbad) atomicAdd(nbad, (uint32_t)__popcll(mask));
+  }
+}
+
+hipError_t launch_first_bad(const uint8_t* got, const uint8_t* want, uint64_t n, uint64_t base,
+                            uint64_t* first, uint32_t* nbad, hipStream_t s, const uint8_t* flag) {
+  static_assert(kThreads % 64 == 0, "whole waves per workgroup");
+  hipLaunchKernelGGL(k_cell_init, dim3(1), dim3(64), 0, s,
+                     reinterpret_cast<unsigned long long*>(first), nbad);
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess || n == 0) return e;
+  hipLaunchKernelGGL(k_first_bad, dim3(grid_for(n, kThreads)), dim3(kThreads), 0, s, got, want, n,
+                     base, reinterpret_cast<unsigned long long*>(first), nbad, flag);
   return hipGetLastError();
 }
 

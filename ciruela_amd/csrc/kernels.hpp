@@ -140,6 +140,14 @@ hipError_t launch_single(const uint8_t* h_src, uint32_t n, uint8_t* d_scratch, u
 hipError_t launch_verify(const uint8_t* got, const uint8_t* want, uint64_t n, uint8_t* ok,
                          uint32_t* nbad, hipStream_t s, const uint8_t* flag = nullptr);
 
+// The same compare, answering only "which digest first": *first (device u64)
+// = base + the smallest b whose digest differs (or whose flag is set),
+// UINT64_MAX when none; *nbad (device u32, nullable) = how many.  Both are
+// initialised here, on the same stream (also when n == 0).
+hipError_t launch_first_bad(const uint8_t* got, const uint8_t* want, uint64_t n, uint64_t base,
+                            uint64_t* first, uint32_t* nbad, hipStream_t s,
+                            const uint8_t* flag = nullptr);
+
 // nlanes x `lines` register-only compressions (diagnostic VALU ceiling).
 hipError_t launch_compress_only(uint64_t nlanes, uint32_t lines, uint8_t* out, hipStream_t s);
 

@@ -75,6 +75,9 @@ Device::~Device() {
     (void)hipFree(s.d_off);
     (void)hipFree(s.d_len);
     (void)hipFree(s.d_out);
+    (void)hipFree(s.d_want);
+    (void)hipFree(s.d_cell);
+    (void)hipHostFree(s.h_cell);
     if (s.copied) (void)hipEventDestroy(s.copied);
     if (s.done) (void)hipEventDestroy(s.done);
     for (hipEvent_t e : {s.t_copy0, s.t_copy1, s.t_hash0, s.t_done})
@@ -317,6 +320,19 @@ int Device::ensure_slot(Slot& s, uint64_t bytes, uint64_t nblk) {
   return CIR_OK;
 }
 
+int Device::ensure_check(Slot& s) {
+  if (!s.d_cell) CIR_HIP(hipMalloc((void**)&s.d_cell, 16));
+  if (!s.h_cell) CIR_HIP(hipHostMalloc((void**)&s.h_cell, 16, hipHostMallocDefault));
+  if (s.want_blk < s.cap_blk) {
+    (void)hipFree(s.d_want);
+    s.d_want = nullptr;
+    s.want_blk = 0;
+    CIR_HIP(hipMalloc((void**)&s.d_want, s.cap_blk * 32));
+    s.want_blk = s.cap_blk;
+  }
+  return CIR_OK;
+}
+
 int Device::ensure_timing(Slot& s) {
   for (hipEvent_t* e : {&s.t_copy0, &s.t_copy1, &s.t_hash0, &s.t_done})
     if (!*e) CIR_HIP(hipEventCreate(e));
@@ -445,7 +461,7 @@ int hash_desc_ordered(Device& d, const uint8_t* arena, const uint64_t* off, cons
 // (h_off/h_len, nblk blocks); otherwise the slot holds `bytes` consecutive
 // bytes of one file split into chunk_bs blocks (nblk = ceil(bytes / bs)).
 static int slot_submit_impl(Device& d, Slot& s, uint64_t bytes, uint64_t nblk,
-                            uint64_t chunk_bs, int ht) {
+                            uint64_t chunk_bs, int ht, const uint64_t* check_base = nullptr) {
   s.timed = d.record_times || trace_enabled();
   if (s.timed) {
     int rc = d.ensure_timing(s);
@@ -458,6 +474,8 @@ static int slot_submit_impl(Device& d, Slot& s, uint64_t bytes, uint64_t nblk,
     CIR_HIP(hipMemcpyAsync(s.d_off, s.h_off, nblk * 8, hipMemcpyHostToDevice, d.copy));
     CIR_HIP(hipMemcpyAsync(s.d_len, s.h_len, nblk * 4, hipMemcpyHostToDevice, d.copy));
   }
+  if (check_base)
+    CIR_HIP(hipMemcpyAsync(s.d_want, s.h_out, nblk * 32, hipMemcpyHostToDevice, d.copy));
   if (s.timed) CIR_HIP(hipEventRecord(s.t_copy1, d.copy));
   CIR_HIP(hipEventRecord(s.copied, d.copy));
   CIR_HIP(hipStreamWaitEvent(d.compute, s.copied, 0));
@@ -467,7 +485,13 @@ static int slot_submit_impl(Device& d, Slot& s, uint64_t bytes, uint64_t nblk,
     if (rc) return rc;
   } else
     CIR_HIP(dev::launch_chunks(src, bytes, chunk_bs, s.d_out, d.compute));
-  CIR_HIP(hipMemcpyAsync(s.h_out, s.d_out, nblk * 32, hipMemcpyDeviceToHost, d.compute));
+  if (check_base) {
+    CIR_HIP(dev::launch_first_bad(s.d_out, s.d_want, nblk, *check_base, s.d_cell,
+                                  reinterpret_cast<uint32_t*>(s.d_cell + 1), d.compute));
+    CIR_HIP(hipMemcpyAsync(s.h_cell, s.d_cell, 16, hipMemcpyDeviceToHost, d.compute));
+  } else {
+    CIR_HIP(hipMemcpyAsync(s.h_out, s.d_out, nblk * 32, hipMemcpyDeviceToHost, d.compute));
+  }
   // t_done before done: slot_wait's synchronize on done then covers it
   if (s.timed) CIR_HIP(hipEventRecord(s.t_done, d.compute));
   CIR_HIP(hipEventRecord(s.done, d.compute));
@@ -477,6 +501,12 @@ static int slot_submit_impl(Device& d, Slot& s, uint64_t bytes, uint64_t nblk,
 
 int slot_submit(Device& d, Slot& s, uint64_t bytes, uint64_t nblk, int ht) {
   return slot_submit_impl(d, s, bytes, nblk, 0, ht);
+}
+
+int slot_submit_check(Device& d, Slot& s, uint64_t bytes, uint64_t nblk, int ht, uint64_t base) {
+  if (!s.d_cell || !s.h_cell || s.want_blk < nblk)
+    return fail(CIR_EINVAL, "check-mode submit without ensure_check");
+  return slot_submit_impl(d, s, bytes, nblk, 0, ht, &base);
 }
 
 int slot_wait(Device& d, Slot& s) {
@@ -1100,7 +1130,7 @@ int cir_hash_blocks_dev(cir_ctx* ctx, const void* d_arena, const uint64_t* d_off
 static int bounded_run(cir_ctx* ctx, Device* d, int ht, const uint8_t* arena,
                        uint64_t arena_bytes, const uint64_t* off, const uint32_t* len, size_t n,
                        uint8_t* out, uint32_t* nrange, const uint8_t* expected, uint8_t* ok,
-                       uint32_t* nbad, void* scratch, hipStream_t s) {
+                       uint32_t* nbad, void* scratch, hipStream_t s, uint64_t* first = nullptr) {
   uint32_t* slen = nullptr;
   uint8_t* flag = nullptr;
   CIR_HIP(dev::launch_desc_bound(off, len, n, arena_bytes, scratch, nrange, &slen, &flag, s));
@@ -1113,14 +1143,18 @@ static int bounded_run(cir_ctx* ctx, Device* d, int ht, const uint8_t* arena,
     CIR_HIP(dev::launch_general_desc(arena, off, slen, nullptr, n, out, s));
   }
   CIR_HIP(dev::launch_desc_zero(flag, n, out, s));
-  if (expected) CIR_HIP(dev::launch_verify(out, expected, n, ok, nbad, s, flag));
+  if (expected && first)
+    CIR_HIP(dev::launch_first_bad(out, expected, n, 0, first, nbad, s, flag));
+  else if (expected)
+    CIR_HIP(dev::launch_verify(out, expected, n, ok, nbad, s, flag));
   return CIR_OK;
 }
 
 static int hash_desc_bounded(cir_ctx* ctx, int ht, const void* d_arena, uint64_t arena_bytes,
                              const uint64_t* d_off, const uint32_t* d_len, size_t n,
                              uint8_t* d_out, uint32_t* d_nrange, const uint8_t* d_expected,
-                             uint8_t* d_ok, uint32_t* d_nbad, hipStream_t s) {
+                             uint8_t* d_ok, uint32_t* d_nbad, hipStream_t s,
+                             uint64_t* d_first = nullptr) {
   if (!valid_hash_type(ht)) return fail(CIR_EINVAL, "unknown hash type");
   if (n && (!d_off || !d_len || !d_out)) return fail(CIR_EINVAL, "null device pointer");
   // (d_arena may be NULL with arena_bytes == 0: every non-empty block is then
@@ -1134,9 +1168,11 @@ static int hash_desc_bounded(cir_ctx* ctx, int ht, const void* d_arena, uint64_t
     d = stream_device(ctx, s);
     if (!d) return fail(CIR_EINVAL, "stream device is not part of the context");
   }
-  if (d_nbad) CIR_HIP(hipMemsetAsync(d_nbad, 0, 4, s));
+  // (with d_first the compare's launcher initialises both result cells)
+  if (d_nbad && !d_first) CIR_HIP(hipMemsetAsync(d_nbad, 0, 4, s));
   if (n == 0) {
     if (d_nrange) CIR_HIP(hipMemsetAsync(d_nrange, 0, 4, s));
+    if (d_first) CIR_HIP(dev::launch_first_bad(nullptr, nullptr, 0, 0, d_first, d_nbad, s));
     return CIR_OK;
   }
   const uint8_t* arena = static_cast<const uint8_t*>(d_arena);
@@ -1145,7 +1181,7 @@ static int hash_desc_bounded(cir_ctx* ctx, int ht, const void* d_arena, uint64_t
     void* scratch = nullptr;
     CIR_HIP(hipMallocAsync(&scratch, need, s));
     const int rc = bounded_run(ctx, d, ht, arena, arena_bytes, d_off, d_len, n, d_out, d_nrange,
-                               d_expected, d_ok, d_nbad, scratch, s);
+                               d_expected, d_ok, d_nbad, scratch, s, d_first);
     const hipError_t e = hipFreeAsync(scratch, s);
     if (rc) return rc;
     CIR_HIP(e);
@@ -1167,7 +1203,7 @@ static int hash_desc_bounded(cir_ctx* ctx, int ht, const void* d_arena, uint64_t
   }
   CIR_HIP(hipStreamWaitEvent(s, d->bound_free, 0));
   const int rc = bounded_run(ctx, d, ht, arena, arena_bytes, d_off, d_len, n, d_out, d_nrange,
-                             d_expected, d_ok, d_nbad, d->bound_scratch, s);
+                             d_expected, d_ok, d_nbad, d->bound_scratch, s, d_first);
   // recorded on every path: whatever of the batch was queued is ordered
   // before the scratch's next user
   const hipError_t e = hipEventRecord(d->bound_free, s);
@@ -1195,6 +1231,27 @@ int cir_verify_blocks_dev_bounded(cir_ctx* ctx, int hash_type, const void* d_are
   // (nblk == 0: *d_nbad = 0 and nothing else happens)
   return hash_desc_bounded(ctx, hash_type, d_arena, arena_bytes, d_off, d_len, nblk, d_digests,
                            nullptr, d_expected, d_ok, d_nbad, (hipStream_t)stream);
+} CIR_CATCH_BOUNDARY
+
+int cir_verify_first_dev(cir_ctx* ctx, int hash_type, const void* d_arena, uint64_t arena_bytes,
+                         const uint64_t* d_off, const uint32_t* d_len, size_t nblk,
+                         const uint8_t* d_expected, uint8_t* d_digests, uint64_t* d_first,
+                         uint32_t* d_nbad, void* stream) try {
+  if (!d_first || (nblk && (!d_expected || !d_digests)))
+    return fail(CIR_EINVAL, "null device pointer");
+  if ((reinterpret_cast<uintptr_t>(d_expected) | reinterpret_cast<uintptr_t>(d_digests)) & 15u)
+    return fail(CIR_EINVAL, "digest arrays must be 16-byte aligned");
+  if ((reinterpret_cast<uintptr_t>(d_first) & 7u) || (reinterpret_cast<uintptr_t>(d_nbad) & 3u))
+    return fail(CIR_EINVAL, "result cells must be naturally aligned");
+  hipStream_t s = (hipStream_t)stream;
+  if (arena_bytes != UINT64_MAX || nblk == 0)
+    return hash_desc_bounded(ctx, hash_type, d_arena, arena_bytes, d_off, d_len, nblk, d_digests,
+                             nullptr, d_expected, nullptr, d_nbad, s, d_first);
+  // trusted descriptors: no bounds pass, cir_verify_blocks_dev's batch
+  int rc = cir_hash_blocks_dev_ht(ctx, hash_type, d_arena, d_off, d_len, nblk, d_digests, stream);
+  if (rc) return rc;
+  CIR_HIP(dev::launch_first_bad(d_digests, d_expected, nblk, 0, d_first, d_nbad, s));
+  return CIR_OK;
 } CIR_CATCH_BOUNDARY
 
 int cir_hash_blocks_ht(cir_ctx* ctx, int hash_type, const uint8_t* h_arena, const uint64_t* off,

@@ -72,6 +72,14 @@ struct Slot {
   uint32_t* d_len = nullptr;
   uint8_t* d_out = nullptr;
   uint64_t cap_blk = 0;
+  // check mode (cir_check_index): the batch's expected digests on the device
+  // (32 B per block, allocated on the first check, freed with the slot) and
+  // the 16-byte result cell {u64 first bad block, u32 bad count} with its
+  // pinned host twin
+  uint8_t* d_want = nullptr;
+  uint64_t want_blk = 0;
+  uint64_t* d_cell = nullptr;
+  uint64_t* h_cell = nullptr;
   hipEvent_t copied = nullptr;  // H2D of this slot finished (copy stream)
   hipEvent_t done = nullptr;    // digests of this slot are back in h_out
   // timing events (created on first use, recorded only while the device's
@@ -197,6 +205,7 @@ struct Device {
   ~Device();
   int ensure_slot(Slot& s, uint64_t bytes, uint64_t nblk);
   int ensure_timing(Slot& s);
+  int ensure_check(Slot& s);  // the check-mode buffers, sized to s.cap_blk
 };
 
 // Every slot a staged loop submitted is waited for before the loop lets go
@@ -222,6 +231,13 @@ struct SlotDrain {
 // Staging engine: the caller packs a slot, submit() uploads and hashes it
 // asynchronously, wait() returns the digests in h_out.
 int slot_submit(Device& d, Slot& s, uint64_t bytes, uint64_t nblk, int ht = CIR_HASH_BLAKE2B_256);
+// Check mode: s.h_out holds the batch's expected digests (nothing comes back
+// through it); they are uploaded with the descriptors, the batch is hashed
+// into d_out, compared on the device (kernels.hpp launch_first_bad, block b
+// of the batch counted as base + b) and only the result cell is copied back:
+// after slot_wait, s.h_cell[0] = first bad block or UINT64_MAX, the low 32
+// bits of s.h_cell[1] = the number of bad blocks.
+int slot_submit_check(Device& d, Slot& s, uint64_t bytes, uint64_t nblk, int ht, uint64_t base);
 int hash_desc_ordered(Device& d, const uint8_t* arena, const uint64_t* off, const uint32_t* len,
                       uint64_t n, uint8_t* out, hipStream_t s, int ht = CIR_HASH_BLAKE2B_256,
                       bool warm_only = false);

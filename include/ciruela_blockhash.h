@@ -252,6 +252,18 @@ int cir_verify_blocks_dev_bounded(cir_ctx* ctx, int hash_type, const void* d_are
                                   uint8_t* d_digests, uint8_t* d_ok, uint32_t* d_nbad,
                                   void* stream);
 
+/* cir_verify_blocks_dev, answering only "which block first": *d_first (device u64) = smallest b
+ * whose digest differs from d_expected (or is out of range: pass arena_bytes = UINT64_MAX for
+ * trusted descriptors), UINT64_MAX when none; *d_nbad (device u32, may be NULL) = how many.
+ * Both are written on `stream` by the call itself (the caller initialises nothing; nblk == 0
+ * writes UINT64_MAX and 0), no per-block result is stored, and a batch without a mismatch
+ * issues no atomic.  Alignment and CIR_EINVAL cases as cir_verify_blocks_dev_bounded; d_first
+ * must not be NULL. */
+int cir_verify_first_dev(cir_ctx* ctx, int hash_type, const void* d_arena, uint64_t arena_bytes,
+                         const uint64_t* d_off, const uint32_t* d_len, size_t nblk,
+                         const uint8_t* d_expected, uint8_t* d_digests,
+                         uint64_t* d_first, uint32_t* d_nbad, void* stream);
+
 /* Host-memory batch of the same check; ok_out (nblk bytes) may be NULL. */
 int cir_verify_blocks(cir_ctx* ctx, int hash_type, const uint8_t* h_arena, const uint64_t* off,
                       const uint32_t* len, size_t nblk, const uint8_t* expected, uint8_t* ok_out,
@@ -315,6 +327,40 @@ int cir_verify_stats(cir_ctx* ctx, uint64_t out[CIR_VERIFY_STATS_FIELDS]);
  * blocks and every digest equals expected[32 i .. 32 i + 32]. */
 int cir_check_file(cir_ctx* ctx, int hash_type, int fd, uint64_t block_size,
                    const uint8_t* expected, size_t nhash, int* ok_out);
+
+/* The re-hash loop of commit_image (src/daemon/disk/commit.rs:51-117) over a whole image in
+ * one call: every file the index lists is read through the scan's staging pipeline, hashed and
+ * compared with the index's digests on the device, and only "which block first" comes back.
+ * The image root is `dir`, opened relative to dirfd (AT_FDCWD allowed; dir == NULL: dirfd
+ * itself); hash type and block size come from the index header; threads as in cir_scan_v1.
+ *
+ * Returns CIR_OK whenever the check ran to a verdict, "a file is bad" included: *kind_out =
+ * CIR_CHECK_OK (*path_out = NULL), CIR_CHECK_CHECKSUM (Error::Checksum, :81 / :110) or
+ * CIR_CHECK_READ (Error::ReadFile, :74-78 / :98-106) for the first failing entry in index
+ * order, as the reference's serial loop would meet it, with its path (the index's, unescaped
+ * raw bytes, no terminator) in *path_out / *path_len (malloc'd: cir_free).  CIR_EINVAL: null
+ * arguments; CIR_EPARSE / CIR_EHASHSIZE: the index does not parse; CIR_EIO: the root cannot
+ * be opened.
+ *
+ * Read-only: nothing is created, no mode or timestamp changes (those parts of commit_image
+ * stay the caller's).  Directories are opened one component at a time (O_DIRECTORY |
+ * O_NOFOLLOW) below the root fd and files with openat(O_NOFOLLOW) in theirs, so no entry is
+ * reached through a symlink.  Symlink entries, files the index does not list and the index's
+ * footer are not examined.  A size-0 entry passes when it does not exist (the caller creates
+ * it, :63) and is CHECKSUM when it is anything but an empty regular file; a file that cannot
+ * be opened, is not regular, fails to read or shrinks while read is READ (errno in stats[6]);
+ * one whose length differs from the index's is CHECKSUM without being read.
+ *
+ * stats ([0]-[4] defined for CIR_CHECK_OK only): [0] non-empty files hashed, [1] blocks
+ * hashed, [2] bytes read, [3] batches, [4] size-0 entries examined, [5] peak of the file
+ * descriptors the check held at once (O(reader threads), whatever the batch holds), [6]
+ * errno of a READ verdict else 0, [7] global index (in index order) of the first bad block,
+ * or UINT64_MAX. */
+enum cir_check_kind { CIR_CHECK_OK = 0, CIR_CHECK_CHECKSUM = 1, CIR_CHECK_READ = 2 };
+#define CIR_CHECK_STATS_FIELDS 8
+int cir_check_index(cir_ctx* ctx, int dirfd, const char* dir, const uint8_t* index, size_t len,
+                    uint32_t threads, int* kind_out, uint8_t** path_out, size_t* path_len,
+                    uint64_t stats[CIR_CHECK_STATS_FIELDS]);
 
 /* ---- index (DIRSIGNATURE.v1) ----------------------------------------- */
 
