@@ -27,6 +27,13 @@ Context.check_index,            commit_image's re-hash loop over a whole image, 
   check_index                   (src/daemon/disk/commit.rs:51-117)
 Context.verify_first_dev        the same compare on the device, answering only "which
                                 block first" (src/daemon/disk/commit.rs:51-117)
+link_candidates                 scan_links: which files of a new image older images
+                                hold (src/daemon/metadata/hardlink_sources.rs:107-153)
+Context.check_links,            check_and_hardlink's re-hash and mode test of every
+  check_links                   candidate, batched, one verdict per candidate
+                                (src/daemon/disk/public.rs:285-346)
+Context.verify_segments_dev     the same compare on the device, one flag per segment
+                                (src/daemon/disk/public.rs:285-346)
 =============================  ==============================================
 
 All hashing runs on gfx950 through the library; there is no CPU fallback.
@@ -42,7 +49,7 @@ __all__ = [
     "BlockHash", "ImageId", "HashType", "Hashes", "ScannerConfig", "v1", "get_hash",
     "InMemoryIndexes", "ThreadedBlockReader", "BlockHint", "Context", "default_context",
     "IndexError_", "DirError", "ReadError", "CiruelaError", "NoDevice", "sha512_256",
-    "check_index", "CheckResult",
+    "check_index", "CheckResult", "link_candidates", "check_links", "LinksResult",
 ]
 
 DEFAULT_BLOCK_SIZE = 32768
@@ -247,6 +254,18 @@ class Context:
         _n.check(_n.lib.cir_verify_first_dev(self._h, ht, d_arena, arena_bytes, d_off, d_len,
                                              nblk, d_expected, d_digests, d_first, d_nbad, stream))
 
+    def verify_segments_dev(self, d_arena, arena_bytes, d_off, d_len, nblk, d_expected, d_digests,
+                            d_seg_end, nseg, d_seg_bad, d_nbad_seg=0, stream=0, hash_type=None):
+        """verify_first_dev with one verdict per segment: segment s is the
+        blocks [d_seg_end[s-1], d_seg_end[s]) (device u32 x nseg, non-decreasing,
+        the last one nblk); d_seg_bad[s] (device bytes) = 1 when any block of
+        s mismatches or is out of range, else 0; *d_nbad_seg (device u32,
+        optional) = how many segments are bad.  All written by the call."""
+        ht = (hash_type or HashType.blake2b_256()).code
+        _n.check(_n.lib.cir_verify_segments_dev(self._h, ht, d_arena, arena_bytes, d_off, d_len,
+                                                nblk, d_expected, d_digests, d_seg_end, nseg,
+                                                d_seg_bad, d_nbad_seg, stream))
+
     # ---- asynchronous per-block verify (FetchBlock::poll, fetch_blocks.rs:77)
     def verify_submit(self, data, expected, hash_type=None):
         """Queue one block with its expected digest; returns a ticket."""
@@ -330,6 +349,43 @@ class Context:
         del keep
         raw = _n.take_buffer(path.value, plen.value) if path.value else None
         return CheckResult(kind.value, raw, dict(zip(self.CHECK_STATS_FIELDS, list(stats))))
+
+    LINKS_STATS_FIELDS = ("ok", "checksum", "read", "blocks", "bytes", "batches", "peak_fds",
+                          "empty_candidates")
+
+    def check_links(self, index, roots, links, threads=0):
+        """check_and_hardlink's verify (src/daemon/disk/public.rs:285-346) of
+        every candidate in one call.  `roots`: the source images' directories
+        -- a path, a directory fd (int) or a (dir_fd, path) pair each;
+        `links`: (file ordinal, source ordinal) pairs as link_candidates
+        returns them.  A LinksResult with one verdict per candidate; nothing
+        is linked."""
+        if len(index):
+            ptr, keep = _buf(index)
+        else:  # (an empty index is a parse error, not a null argument)
+            keep = ctypes.create_string_buffer(1)
+            ptr = ctypes.cast(keep, ctypes.c_void_p)
+        links = [(int(f), int(s)) for f, s in links]
+        nsrc, n = len(roots), len(links)
+        fds = (ctypes.c_int * max(nsrc, 1))()
+        dirs = (ctypes.c_char_p * max(nsrc, 1))()
+        for j, r in enumerate(roots):
+            if isinstance(r, int):
+                fds[j], dirs[j] = r, None
+            elif isinstance(r, tuple):
+                fds[j], dirs[j] = r[0], os.fsencode(r[1])
+            else:
+                fds[j], dirs[j] = -100, os.fsencode(r)  # AT_FDCWD
+        lf = (ctypes.c_uint64 * max(n, 1))(*[f for f, _ in links])
+        ls = (ctypes.c_uint32 * max(n, 1))(*[s for _, s in links])
+        kinds = (ctypes.c_uint8 * max(n, 1))()
+        errnos = (ctypes.c_int32 * max(n, 1))()
+        stats = (ctypes.c_uint64 * _n.CIR_LINKS_STATS_FIELDS)()
+        _n.check(_n.lib.cir_check_links(self._h, ptr, len(index), fds, dirs, nsrc, lf, ls, n,
+                                        threads, kinds, errnos, stats))
+        del keep
+        return LinksResult(index, links, list(kinds)[:n], list(errnos)[:n],
+                           dict(zip(self.LINKS_STATS_FIELDS, list(stats))))
 
     def scan(self, config):
         dirs = [os.fsencode(d) for d, _ in config._dirs]
@@ -440,6 +496,58 @@ class CheckResult:
 
     def __repr__(self):
         return "CheckResult(%s%s)" % (self.kind, "" if self.ok else ", %r" % (self.path,))
+
+
+def _unescape(name):
+    """An index's \\xNN escapes back to raw bytes."""
+    if b"\\" not in name:
+        return name
+    out = bytearray()
+    i = 0
+    while i < len(name):
+        if name[i:i + 2] == b"\\x" and i + 4 <= len(name):
+            out.append(int(name[i + 2:i + 4], 16))
+            i += 4
+        else:
+            out.append(name[i])
+            i += 1
+    return bytes(out)
+
+
+def _file_paths(index):
+    """The paths (raw bytes) of an index's file entries, in index order."""
+    paths = []
+    cur = b"/"
+    for line in bytes(index).split(b"\n")[1:]:
+        if line.startswith(b"/"):
+            cur = _unescape(line)
+        elif line.startswith(b"  "):
+            tok = line[2:].split(b" ")
+            if len(tok) >= 2 and tok[1] in (b"f", b"x"):
+                paths.append((b"" if cur == b"/" else cur) + b"/" + _unescape(tok[0]))
+    return paths
+
+
+class LinksResult:
+    """Verdicts of check_links, one per candidate in the order given: kinds
+    ("ok", "checksum" or "read"), errnos (of a "read", else 0), ok_paths --
+    the index paths (raw bytes) of the candidates that passed, which is
+    check_and_hardlink's HashSet<PathBuf> (src/daemon/disk/public.rs:285-305)
+    -- and the call's stats."""
+
+    __slots__ = ("links", "kinds", "errnos", "ok_paths", "stats")
+
+    def __init__(self, index, links, kinds, errnos, stats):
+        paths = _file_paths(index)
+        self.links = links
+        self.kinds = [CheckResult.KINDS[k] for k in kinds]
+        self.errnos = errnos
+        self.ok_paths = {paths[f] for (f, _), k in zip(links, kinds) if k == _n.CIR_CHECK_OK}
+        self.stats = stats
+
+    def __repr__(self):
+        return "LinksResult(%d ok, %d checksum, %d read)" % (
+            self.stats["ok"], self.stats["checksum"], self.stats["read"])
 
 
 _default = None
@@ -666,6 +774,43 @@ def sha512_256(data):
 def check_index(root, index, threads=0, dir_fd=None, context=None):
     """Context.check_index on the default context."""
     return (context or default_context()).check_index(root, index, threads, dir_fd)
+
+
+def check_links(index, roots, links, threads=0, context=None):
+    """Context.check_links on the default context."""
+    return (context or default_context()).check_links(index, roots, links, threads)
+
+
+def link_candidates(index, sources):
+    """scan_links (src/daemon/metadata/hardlink_sources.rs:107-153): for every
+    file entry of `index`, the first of `sources` (older images' indexes, best
+    first) that lists the same path with equal exe flag, size and digests.
+    Returns [(file ordinal, source ordinal)], file ordinals counting the
+    index's file entries from 0.  A source that does not parse or has another
+    hash type or block size takes no part.  Host only."""
+    if len(index):
+        ptr, keep = _buf(index)
+    else:
+        keep = ctypes.create_string_buffer(1)
+        ptr = ctypes.cast(keep, ctypes.c_void_p)
+    nsrc = len(sources)
+    bufs = [ctypes.create_string_buffer(bytes(s), max(len(s), 1)) for s in sources]
+    sp = (ctypes.c_void_p * max(nsrc, 1))(*[ctypes.cast(b, ctypes.c_void_p) for b in bufs])
+    sl = (ctypes.c_size_t * max(nsrc, 1))(*[len(s) for s in sources])
+    f = ctypes.c_void_p()
+    s = ctypes.c_void_p()
+    n = ctypes.c_size_t()
+    skipped = ctypes.c_size_t()
+    _n.check(_n.lib.cir_link_candidates(ptr, len(index), sp, sl, nsrc, ctypes.byref(f),
+                                        ctypes.byref(s), ctypes.byref(n), ctypes.byref(skipped)))
+    del keep
+    if not n.value:
+        return []
+    files = list((ctypes.c_uint64 * n.value).from_address(f.value))
+    srcs = list((ctypes.c_uint32 * n.value).from_address(s.value))
+    _n.lib.cir_free(f)
+    _n.lib.cir_free(s)
+    return list(zip(files, srcs))
 
 
 def get_hash(index):

@@ -50,6 +50,7 @@ CIR_CHECK_OK = 0
 CIR_CHECK_CHECKSUM = 1
 CIR_CHECK_READ = 2
 CIR_CHECK_STATS_FIELDS = 8
+CIR_LINKS_STATS_FIELDS = 8
 CIR_INIT_ONE_SHOT = 1  # cir_init_n: one stream and one staging slot per device
 CIR_STAGING_LAZY = (1 << 64) - 1  # cir_init: no staging slots until a host path needs them
 
@@ -134,6 +135,17 @@ _SIGS = {
     "cir_check_index": (ctypes.c_int, [c_vp, ctypes.c_int, ctypes.c_char_p, c_vp, ctypes.c_size_t,
                                        ctypes.c_uint32, ctypes.POINTER(ctypes.c_int),
                                        ctypes.POINTER(c_vp), c_sizep, c_u64p]),
+    "cir_verify_segments_dev": (ctypes.c_int, [c_vp, ctypes.c_int, c_vp, ctypes.c_uint64, c_vp,
+                                               c_vp, ctypes.c_size_t, c_vp, c_vp, c_vp,
+                                               ctypes.c_size_t, c_vp, c_vp, c_vp]),
+    "cir_link_candidates": (ctypes.c_int, [c_vp, ctypes.c_size_t, ctypes.POINTER(c_vp), c_sizep,
+                                           ctypes.c_size_t, ctypes.POINTER(c_vp),
+                                           ctypes.POINTER(c_vp), c_sizep, c_sizep]),
+    "cir_check_links": (ctypes.c_int, [c_vp, c_vp, ctypes.c_size_t,
+                                       ctypes.POINTER(ctypes.c_int),
+                                       ctypes.POINTER(ctypes.c_char_p), ctypes.c_size_t, c_u64p,
+                                       c_u32p, ctypes.c_size_t, ctypes.c_uint32, c_u8p,
+                                       ctypes.POINTER(ctypes.c_int32), c_u64p]),
     "cir_debug_compress_only_dev": (ctypes.c_int, [ctypes.c_uint64, ctypes.c_uint32, c_vp, c_vp]),
     "cir_debug_relay_blocks": (ctypes.c_uint64, [ctypes.c_uint64, ctypes.c_uint64]),
     "cir_debug_device_identity": (ctypes.c_int, [ctypes.c_int, ctypes.c_char_p, ctypes.c_size_t,

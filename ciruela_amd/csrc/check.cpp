@@ -1,4 +1,6 @@
-// cir_check_index: the re-hash loop of commit_image over a whole image.
+// cir_check_index: the re-hash loop of commit_image over a whole image
+// (and, below it, cir_check_links: the same pipeline with a verdict per file
+// for the hardlink candidates of check_and_hardlink).
 //
 // Reference: commit_image (src/daemon/disk/commit.rs:51-117) walks the
 // index's entries in order, re-hashes every non-empty file
@@ -43,6 +45,7 @@
 
 #include <algorithm>
 #include <atomic>
+#include <chrono>
 #include <mutex>
 #include <string>
 #include <vector>
@@ -138,14 +141,14 @@ struct DirFd {
   int err = 0;  // errno when fd < 0
 };
 
-DirFd open_dir(Image& im, const std::vector<std::string>& comps) {
+DirFd open_dir_at(FdCount& fds, int root, const std::vector<std::string>& comps) {
   DirFd d;
-  d.fd = im.root;
+  d.fd = root;
   for (const std::string& c : comps) {
-    const int nfd = im.fds.took(
-        ::openat(d.fd, c.c_str(), O_RDONLY | O_DIRECTORY | O_NOFOLLOW | O_CLOEXEC));
+    const int nfd =
+        fds.took(::openat(d.fd, c.c_str(), O_RDONLY | O_DIRECTORY | O_NOFOLLOW | O_CLOEXEC));
     const int e = errno;
-    if (d.own) im.fds.close(d.fd);
+    if (d.own) fds.close(d.fd);
     if (nfd < 0) {
       d.fd = -1;
       d.own = false;
@@ -158,10 +161,16 @@ DirFd open_dir(Image& im, const std::vector<std::string>& comps) {
   return d;
 }
 
-void close_dir(Image& im, DirFd& d) {
-  if (d.own) im.fds.close(d.fd);
+DirFd open_dir(Image& im, const std::vector<std::string>& comps) {
+  return open_dir_at(im.fds, im.root, comps);
+}
+
+void close_dir_at(FdCount& fds, DirFd& d) {
+  if (d.own) fds.close(d.fd);
   d = DirFd();
 }
+
+void close_dir(Image& im, DirFd& d) { close_dir_at(im.fds, d); }
 
 // What the packer saw of a file it is about to pack.
 struct Seen {
@@ -172,14 +181,15 @@ struct Seen {
 // openat + fstat of a listed non-empty file: 0 with *fd_out open, or the
 // failure's kind with *err.  (O_NONBLOCK: a fifo in the file's place fails
 // the fstat test below instead of blocking the open.)
-int open_listed(Image& im, const DirFd& d, const Item& it, int* fd_out, struct stat* st, int* err) {
+int open_listed_at(FdCount& fds, const DirFd& d, const Item& it, int* fd_out, struct stat* st,
+                   int* err) {
   *fd_out = -1;
   *err = 0;
   if (d.fd < 0) {
     *err = d.err;
     return CIR_CHECK_READ;
   }
-  const int fd = im.fds.took(
+  const int fd = fds.took(
       ::openat(d.fd, it.name.c_str(), O_RDONLY | O_NOFOLLOW | O_CLOEXEC | O_NONBLOCK));
   if (fd < 0) {
     *err = errno;
@@ -187,16 +197,20 @@ int open_listed(Image& im, const DirFd& d, const Item& it, int* fd_out, struct s
   }
   if (::fstat(fd, st) != 0) {
     *err = errno;
-    im.fds.close(fd);
+    fds.close(fd);
     return CIR_CHECK_READ;
   }
   if (!S_ISREG(st->st_mode)) {
     *err = S_ISDIR(st->st_mode) ? EISDIR : EINVAL;
-    im.fds.close(fd);
+    fds.close(fd);
     return CIR_CHECK_READ;
   }
   *fd_out = fd;
   return CIR_CHECK_OK;
+}
+
+int open_listed(Image& im, const DirFd& d, const Item& it, int* fd_out, struct stat* st, int* err) {
+  return open_listed_at(im.fds, d, it, fd_out, st, err);
 }
 
 // A size-0 entry (commit.rs:57-90): absent passes (the caller creates it),
@@ -641,8 +655,489 @@ int check_impl(cir_ctx* ctx, int dirfd, const char* dir, const uint8_t* index, s
   return CIR_OK;
 }
 
+// ---- cir_check_links ------------------------------------------------------
+//
+// try_hardlink (src/daemon/disk/public.rs:308-346) over every candidate of
+// check_and_hardlink (:285-305) in one call.  The pipeline is check_range's
+// without its order and its stop: every candidate is on its own (:303), so a
+// failure is written to the candidate's own verdict and packing goes on.  The
+// candidates are worked through by source root and index order (a packer's
+// and a reader's directory fd serves the neighbours too); their blocks,
+// counted in that order, are what several devices take stripes of.  A batch's
+// segment table (one segment = one candidate's run of blocks in the batch)
+// travels up with the descriptors, k_seg_bad answers per segment, and 16 +
+// nseg bytes come back.
+
+struct Cand {
+  size_t item = 0;         // index into Links::items
+  uint32_t src = 0;        // source root
+  size_t out = 0;          // the caller's candidate number
+  uint64_t first_blk = 0;  // global index of block 0 in the work order
+};
+
+struct Links {
+  const dirsig::Index* idx = nullptr;
+  uint64_t bs = 0;
+  int ht = CIR_HASH_BLAKE2B_256;
+  std::vector<std::vector<std::string>> dirs;
+  std::vector<Item> items;  // every file entry, in index order
+  std::vector<int> root;    // per source: its fd, or -1 with root_err
+  std::vector<int> root_err;
+  std::vector<Cand> cands;  // the non-empty candidates below a root that opened, in work order
+  uint64_t nblk_total = 0;
+  FdCount fds;
+  std::mutex mu;
+  uint8_t* kind = nullptr;  // per candidate of the caller
+  int32_t* err = nullptr;
+  std::atomic<uint64_t> n_blocks{0}, n_bytes{0}, n_batches{0};
+
+  // READ wins over CHECKSUM; the first READ's errno stays
+  void report(size_t out, int k, int e) {
+    std::lock_guard<std::mutex> lk(mu);
+    if (k == CIR_CHECK_READ) {
+      if (kind[out] != CIR_CHECK_READ) {
+        kind[out] = CIR_CHECK_READ;
+        err[out] = e;
+      }
+    } else if (kind[out] == CIR_CHECK_OK) {
+      kind[out] = (uint8_t)k;
+    }
+  }
+  bool exe(const Item& it) const { return idx->entries[it.entry].exe; }
+};
+
+// A directory of one source root, kept while the next candidate needs the same.
+struct LinkDir {
+  DirFd d;
+  uint32_t src = UINT32_MAX;
+  size_t dir = SIZE_MAX;
+  const DirFd& of(Links& L, const Cand& c) {
+    const Item& it = L.items[c.item];
+    if (src != c.src || dir != it.dir) {
+      close_dir_at(L.fds, d);
+      d = open_dir_at(L.fds, L.root[c.src], L.dirs[it.dir]);
+      src = c.src;
+      dir = it.dir;
+    }
+    return d;
+  }
+  void close(Links& L) {
+    close_dir_at(L.fds, d);
+    src = UINT32_MAX;
+    dir = SIZE_MAX;
+  }
+};
+
+// The packer's look at a candidate (try_hardlink without the read): READ,
+// CHECKSUM on a length or mode bits (public.rs:331-338) that are not the
+// entry's, else what identifies the file to the readers.
+int examine_link(Links& L, const DirFd& d, const Item& it, Seen* seen, int* err) {
+  int fd = -1;
+  struct stat st;
+  const int kind = open_listed_at(L.fds, d, it, &fd, &st, err);
+  if (kind) return kind;
+  L.fds.close(fd);
+  if ((uint64_t)st.st_size != it.size) return CIR_CHECK_CHECKSUM;
+  if ((st.st_mode & 0777) != (L.exe(it) ? 0755u : 0644u)) return CIR_CHECK_CHECKSUM;
+  seen->dev = st.st_dev;
+  seen->ino = st.st_ino;
+  return CIR_CHECK_OK;
+}
+
+struct LinkJob {
+  size_t cand;  // index into Links::cands
+  Seen seen;
+  uint64_t file_off, len;
+  uint8_t* dst;
+};
+
+// Read the batch's jobs on `threads` readers.  Every job is tried; a failed
+// one makes READ of its own candidate and of nothing else (its bytes in the
+// slot are then whatever they are: READ wins over what the compare finds).
+void run_link_reads(Links& L, const std::vector<LinkJob>& jobs, unsigned threads) {
+  std::atomic<size_t> next{0};
+  const bool nt = stage_copy_nt();
+  auto worker = [&] {
+    LinkDir dir;
+    for (;;) {
+      const size_t i = next.fetch_add(1);
+      if (i >= jobs.size()) break;
+      const LinkJob& j = jobs[i];
+      const Cand& c = L.cands[j.cand];
+      const Item& it = L.items[c.item];
+      int fd = -1, e = 0;
+      struct stat st;
+      bool ok = open_listed_at(L.fds, dir.of(L, c), it, &fd, &st, &e) == CIR_CHECK_OK;
+      if (ok && (st.st_dev != j.seen.dev || st.st_ino != j.seen.ino ||
+                 (uint64_t)st.st_size != it.size)) {
+        ok = false;  // not the file that was packed
+        e = ESTALE;
+      }
+      uint64_t got = 0;
+      while (ok && got < j.len) {
+        const ssize_t r =
+            pread_staged(fd, j.dst + got, j.len - got, (off_t)(j.file_off + got), nt);
+        if (r < 0 && errno == EINTR) continue;
+        if (r <= 0) {
+          ok = false;
+          e = r == 0 ? ENODATA : errno;  // the file shrank under the read
+          break;
+        }
+        got += (uint64_t)r;
+      }
+      L.fds.close(fd);
+      if (!ok) L.report(c.out, CIR_CHECK_READ, e);
+    }
+    dir.close(L);
+  };
+  parallel_run(std::max(1u, std::min<unsigned>(threads, (unsigned)jobs.size())), worker);
+}
+
+// check_range for the candidates: the block ranges `ranges` (increasing, of
+// the work order's global blocks) on device d.  A candidate is examined by
+// every range that holds some of its blocks; what fails the look is reported
+// and its blocks in the range are passed over.
+int links_range(cir_ctx* ctx, Device& d, Links& L, unsigned threads, const BlockRanges& ranges) {
+  if (ranges.empty()) return CIR_OK;
+  std::lock_guard<std::mutex> lk(d.mu);
+  DeviceGuard guard;
+  CIR_HIP(hipSetDevice(d.id));
+  SlotDrain drain{d};  // an early return leaves no slot busy
+  const std::vector<Cand>& cands = L.cands;
+  const uint64_t bs = L.bs;
+  uint64_t seg = 0;
+  for (const Cand& c : cands) seg = std::max(seg, std::min<uint64_t>(L.items[c.item].size, bs));
+  const uint64_t cap = (std::max<uint64_t>(ctx->staging, seg + 16) + 15) & ~15ull;
+  const uint64_t cap_blk = std::max<uint64_t>(cap / 512, 4096);
+  uint64_t fill = scan_ramp() ? std::max<uint64_t>(seg + 16, cap >> 3) : cap;
+
+  size_t ri = 0;
+  uint64_t b0 = 0, b1 = 0;
+  size_t ci = 0;               // the candidate being packed
+  uint64_t fblk = 0;           // its next block
+  size_t examined = SIZE_MAX;  // the candidate whose look passed (in this range)
+  Seen seen;
+  LinkDir cur;  // the packer's directory
+  struct CloseCur {
+    Links& L;
+    LinkDir& d;
+    ~CloseCur() { d.close(L); }
+  } close_cur{L, cur};
+  constexpr int kS = Device::kSlots;
+  std::vector<size_t> seg_cand[kS];  // per slot in flight: each segment's candidate (Cand::out)
+  auto start_range = [&](size_t r) {
+    ri = r;
+    b0 = ranges[r].first;
+    b1 = ranges[r].second;
+    ci = std::lower_bound(cands.begin(), cands.end(), b0,
+                          [](const Cand& x, uint64_t b) { return x.first_blk < b; }) -
+         cands.begin();
+    fblk = 0;
+    if (ci > 0 && cands[ci - 1].first_blk + L.items[cands[ci - 1].item].nblk > b0) {
+      --ci;
+      fblk = b0 - cands[ci].first_blk;
+    }
+    examined = SIZE_MAX;
+  };
+  auto here = [&] { return ci < cands.size() && cands[ci].first_blk + fblk < b1; };
+  auto more = [&] {
+    while (!here()) {
+      if (ri + 1 >= ranges.size()) return false;
+      start_range(ri + 1);
+    }
+    return true;
+  };
+  auto busy = [&] {
+    for (const Slot& s : d.slot)
+      if (s.busy) return true;
+    return false;
+  };
+  start_range(0);
+  // CIR_TRACE: where this device's host thread spent the call
+  const bool trace = trace_enabled();
+  using Clock = std::chrono::steady_clock;
+  double t_wait = 0, t_pack = 0, t_read = 0, t_submit = 0;
+  uint64_t n_batches = 0;
+  auto lap = [&](Clock::time_point& t0, double& acc) {
+    if (!trace) return;
+    const Clock::time_point t1 = Clock::now();
+    acc += std::chrono::duration<double, std::milli>(t1 - t0).count();
+    t0 = t1;
+  };
+  int k = 0;
+  while (more() || busy()) {
+    Slot& s = d.slot[k];
+    Clock::time_point t0 = trace ? Clock::now() : Clock::time_point();
+    if (s.busy) {
+      int rc = slot_wait(d, s);
+      if (rc) return rc;
+      uint32_t nbad = 0;
+      memcpy(&nbad, s.h_seg_res, 4);
+      if (nbad) {
+        const uint8_t* flags = s.h_seg_res + kSegResHead;
+        for (size_t g = 0; g < seg_cand[k].size(); ++g)
+          if (flags[g]) L.report(seg_cand[k][g], CIR_CHECK_CHECKSUM, 0);
+      }
+    }
+    lap(t0, t_wait);
+    if (more()) {
+      int rc = d.ensure_slot(s, cap, cap_blk);
+      if (rc) return rc;
+      rc = d.ensure_links(s);
+      if (rc) return rc;
+      std::vector<LinkJob> jobs;
+      std::vector<size_t>& segs = seg_cand[k];
+      segs.clear();
+      uint64_t pos = 0, n = 0, used = 0, file_bytes = 0;
+      while (here() && n < cap_blk) {
+        const Cand& c = cands[ci];
+        const Item& it = L.items[c.item];
+        const uint64_t left_blk = std::min<uint64_t>(it.nblk - fblk, b1 - (c.first_blk + fblk));
+        if (examined != ci) {
+          int err = 0;
+          const int kind = examine_link(L, cur.of(L, c), it, &seen, &err);
+          if (kind) {
+            L.report(c.out, kind, err);
+            fblk += left_blk;  // its blocks in this range are passed over
+            if (fblk == it.nblk) {
+              ++ci;
+              fblk = 0;
+            }
+            continue;
+          }
+          examined = ci;
+        }
+        pos = (pos + 15) & ~15ull;
+        if (pos + std::min<uint64_t>(bs, it.size - fblk * bs) > fill) break;
+        uint64_t take = std::min<uint64_t>(left_blk, cap_blk - n);
+        take = std::min<uint64_t>(take, std::max<uint64_t>((fill - pos) / bs, 1));
+        const uint64_t off0 = fblk * bs;
+        const uint64_t bytes = std::min<uint64_t>(take * bs, it.size - off0);
+        if (pos + bytes > fill) break;
+        for (uint64_t j = 0; j < take; ++j) {
+          s.h_off[n + j] = pos + j * bs;
+          s.h_len[n + j] = (uint32_t)std::min<uint64_t>(bs, it.size - off0 - j * bs);
+        }
+        // the entry's digests of these blocks travel up through h_out
+        memcpy(s.h_out + 32 * n, L.idx->entries[it.entry].hashes.data() + 32 * fblk, 32 * take);
+        for (uint64_t piece = 0; piece < bytes; piece += kReadPiece)
+          jobs.push_back({ci, seen, off0 + piece, std::min<uint64_t>(kReadPiece, bytes - piece),
+                          s.h_data + pos + piece});
+        file_bytes += bytes;
+        pos += bytes;
+        used = pos;
+        n += take;
+        fblk += take;
+        s.h_seg_end[segs.size()] = (uint32_t)n;  // (at most one segment per block: <= cap_blk)
+        segs.push_back(c.out);
+        if (fblk == it.nblk) {
+          ++ci;
+          fblk = 0;
+        }
+      }
+      fill = std::min(cap, fill * 2);
+      lap(t0, t_pack);
+      if (n > 0) {
+        run_link_reads(L, jobs, threads);
+        lap(t0, t_read);
+        rc = slot_submit_links(d, s, std::max<uint64_t>(used, 16), n, L.ht, segs.size());
+        if (rc) return rc;
+        lap(t0, t_submit);
+        ++n_batches;
+        L.n_blocks.fetch_add(n);
+        L.n_bytes.fetch_add(file_bytes);
+        L.n_batches.fetch_add(1);
+      }
+    }
+    k = (k + 1) % kS;
+  }
+  if (trace)
+    fprintf(stderr,
+            "cir check_links dev %d: %llu batches; packer's look and segment table %.2f ms, "
+            "reads %.2f ms, submit %.2f ms, waiting for results and flags %.2f ms\n",
+            d.id, (unsigned long long)n_batches, t_pack, t_read, t_submit, t_wait);
+  return CIR_OK;
+}
+
+int links_impl(cir_ctx* ctx, const uint8_t* index, size_t len, const int* src_dirfd,
+               const char* const* src_dir, size_t nsrc, const uint64_t* link_file,
+               const uint32_t* link_src, size_t nlinks, uint32_t threads, uint8_t* kind_out,
+               int32_t* errno_out, uint64_t* stats) {
+  if (!ctx || !index || !stats || (nsrc && (!src_dirfd || !src_dir)) ||
+      (nlinks && (!link_file || !link_src || !kind_out)))
+    return fail(CIR_EINVAL, "null pointer");
+  for (int i = 0; i < CIR_LINKS_STATS_FIELDS; ++i) stats[i] = 0;
+  const auto t_start = std::chrono::steady_clock::now();
+  auto ms_since = [](std::chrono::steady_clock::time_point t) {
+    return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t).count();
+  };
+  for (size_t i = 0; i < nlinks; ++i)
+    if (link_src[i] >= nsrc) return fail(CIR_EINVAL, "link_src names no source root");
+  dirsig::Index idx;
+  std::string perr;
+  if (!dirsig::parse(index, len, &idx, &perr))
+    return idx.bad_hash_size ? fail(CIR_EHASHSIZE, "hash size is unsupported: " + perr)
+                             : fail(CIR_EPARSE, "error parsing index: " + perr);
+  if (dirsig::digest_len(idx.header.hash) != 32)
+    return fail(CIR_EHASHSIZE, "hash size is unsupported");
+  if (idx.header.block_size > 0xffffffffull)
+    return fail(CIR_EINVAL, "block_size must be in 1 .. 2^32-1");
+  Links L;
+  L.idx = &idx;
+  L.bs = idx.header.block_size;
+  L.ht = idx.header.hash == dirsig::HashType::kSha512_256 ? CIR_HASH_SHA512_256
+                                                           : CIR_HASH_BLAKE2B_256;
+  for (size_t e = 0; e < idx.entries.size(); ++e) {
+    const dirsig::Entry& en = idx.entries[e];
+    if (en.kind == dirsig::EntryKind::kDir) {
+      std::vector<std::string> comps;
+      size_t i = 0;
+      while (i < en.path.size()) {
+        size_t j = en.path.find('/', i);
+        if (j == std::string::npos) j = en.path.size();
+        if (j > i) comps.push_back(en.path.substr(i, j - i));
+        i = j + 1;
+      }
+      L.dirs.push_back(std::move(comps));
+    } else if (en.kind == dirsig::EntryKind::kFile) {
+      if (L.dirs.empty()) return fail(CIR_EPARSE, "error parsing index: entry before a directory");
+      Item it;
+      it.entry = e;
+      it.dir = L.dirs.size() - 1;
+      it.name = en.path.substr(en.path.rfind('/') + 1);
+      it.size = en.size;
+      it.nblk = en.hashes.size() / 32;
+      L.items.push_back(std::move(it));
+    }
+  }
+  for (size_t i = 0; i < nlinks; ++i)
+    if (link_file[i] >= L.items.size())
+      return fail(CIR_EINVAL, "link_file is past the last file entry");
+  // ---- nothing above touched a file or a device
+  const double ms_parse = ms_since(t_start);
+  const auto t_roots = std::chrono::steady_clock::now();
+  std::vector<int32_t> errs(nlinks, 0);
+  L.kind = kind_out;
+  L.err = errs.data();
+  for (size_t i = 0; i < nlinks; ++i) kind_out[i] = CIR_CHECK_OK;
+  // the roots some candidate names
+  L.root.assign(nsrc, -1);
+  L.root_err.assign(nsrc, 0);
+  std::vector<char> own(nsrc, 0), used(nsrc, 0);
+  struct CloseRoots {
+    Links& L;
+    std::vector<char>& own;
+    ~CloseRoots() {
+      for (size_t j = 0; j < own.size(); ++j)
+        if (own[j]) L.fds.close(L.root[j]);
+    }
+  } close_roots{L, own};
+  for (size_t i = 0; i < nlinks; ++i) used[link_src[i]] = 1;
+  for (size_t j = 0; j < nsrc; ++j) {
+    if (!used[j]) continue;
+    if (src_dir[j]) {
+      L.root[j] = L.fds.took(::openat(src_dirfd[j], src_dir[j], O_RDONLY | O_DIRECTORY | O_CLOEXEC));
+      if (L.root[j] < 0)
+        L.root_err[j] = errno;
+      else
+        own[j] = 1;
+    } else {
+      struct stat st;
+      if (::fstat(src_dirfd[j], &st) != 0)
+        L.root_err[j] = errno;
+      else if (!S_ISDIR(st.st_mode))
+        L.root_err[j] = ENOTDIR;
+      else
+        L.root[j] = src_dirfd[j];
+    }
+  }
+  // the work order: by root, then by index order
+  std::vector<size_t> order(nlinks);
+  for (size_t i = 0; i < nlinks; ++i) order[i] = i;
+  std::stable_sort(order.begin(), order.end(), [&](size_t a, size_t b) {
+    return link_src[a] != link_src[b] ? link_src[a] < link_src[b] : link_file[a] < link_file[b];
+  });
+  {
+    LinkDir cur;
+    for (size_t i : order) {
+      Cand c;
+      c.item = (size_t)link_file[i];
+      c.src = link_src[i];
+      c.out = i;
+      const Item& it = L.items[c.item];
+      if (L.root[c.src] < 0) {
+        L.report(i, CIR_CHECK_READ, L.root_err[c.src]);
+      } else if (it.nblk == 0) {
+        // a size-0 candidate: an empty regular file of the right mode, seen by the host alone
+        Seen seen;
+        int e = 0;
+        const int kind = examine_link(L, cur.of(L, c), it, &seen, &e);
+        if (kind) L.report(i, kind, e);
+        ++stats[7];
+      } else {
+        c.first_blk = L.nblk_total;
+        L.nblk_total += it.nblk;
+        L.cands.push_back(c);
+      }
+    }
+    cur.close(L);
+  }
+  if (threads == 0) threads = host_copy_threads(ctx->devs.size());
+  const double ms_roots = ms_since(t_roots);
+  const auto t_pipe = std::chrono::steady_clock::now();
+
+  int rc = CIR_OK;
+  const size_t nd = std::min<size_t>(ctx->devs.size(), (size_t)std::max<uint64_t>(L.nblk_total, 1));
+  if (L.nblk_total == 0) {
+    // nothing for a device
+  } else if (nd <= 1) {
+    rc = links_range(ctx, *ctx->devs[0], L, threads, {{0, L.nblk_total}});
+  } else {
+    uint64_t stripe = std::max<uint64_t>(1, ctx->staging / L.bs);
+    if (const char* e = getenv("CIR_DEBUG_STRIPE_BLOCKS"))  // tests: stripes of a few blocks
+      if (atoll(e) > 0) stripe = (uint64_t)atoll(e);
+    const StripePrefix sp(L.nblk_total, stripe);
+    std::vector<BlockRanges> dev_ranges(nd);
+    for (size_t st = 0; st < sp.stripes(); ++st)
+      dev_ranges[st % nd].push_back({st * stripe, st * stripe + sp.stripe_len(st)});
+    const unsigned per = std::max(1u, threads / (unsigned)nd);
+    std::vector<int> rcs(nd, 0);
+    std::vector<std::string> es(nd);
+    fan_out(nd, [&](size_t i) {
+      rcs[i] = links_range(ctx, *ctx->devs[i], L, per, dev_ranges[i]);
+      if (rcs[i]) es[i] = cir_last_error();
+    });
+    for (size_t i = 0; i < nd && !rc; ++i)
+      if (rcs[i]) rc = fail(rcs[i], es[i]);
+  }
+  stats[6] = L.fds.peak.load();
+  if (trace_enabled())
+    fprintf(stderr,
+            "cir check_links: %zu candidates; index parse %.2f ms, roots, work order and size-0 "
+            "candidates %.2f ms, pipeline %.2f ms\n",
+            nlinks, ms_parse, ms_roots, ms_since(t_pipe));
+  if (rc) return rc;
+  for (size_t i = 0; i < nlinks; ++i) {
+    ++stats[kind_out[i] == CIR_CHECK_OK ? 0 : kind_out[i] == CIR_CHECK_CHECKSUM ? 1 : 2];
+    if (errno_out) errno_out[i] = kind_out[i] == CIR_CHECK_READ ? errs[i] : 0;
+  }
+  stats[3] = L.n_blocks.load();
+  stats[4] = L.n_bytes.load();
+  stats[5] = L.n_batches.load();
+  return CIR_OK;
+}
+
 }  // namespace
 }  // namespace cir
+
+extern "C" int cir_check_links(cir_ctx* ctx, const uint8_t* index, size_t len,
+                               const int* src_dirfd, const char* const* src_dir, size_t nsrc,
+                               const uint64_t* link_file, const uint32_t* link_src, size_t nlinks,
+                               uint32_t threads, uint8_t* kind_out, int32_t* errno_out,
+                               uint64_t stats[CIR_LINKS_STATS_FIELDS]) try {
+  return cir::links_impl(ctx, index, len, src_dirfd, src_dir, nsrc, link_file, link_src, nlinks,
+                         threads, kind_out, errno_out, stats);
+} CIR_CATCH_BOUNDARY
 
 extern "C" int cir_check_index(cir_ctx* ctx, int dirfd, const char* dir, const uint8_t* index,
                                size_t len, uint32_t threads, int* kind_out, uint8_t** path_out,

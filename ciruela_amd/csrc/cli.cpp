@@ -19,6 +19,15 @@
 //       commit.rs:51-117) of the image in DIR against INDEX_FILE: silent and
 //       exit 0 when every listed file matches, else exit 1 with one line,
 //       `checksum: <path>` or `read: <path>: <strerror>`
+//   ciruela-index links INDEX SRCDIR=SRCINDEX [SRCDIR=SRCINDEX ...] [--disk-threads N]
+//       the daemon's hardlink step before a download (scan_links, src/daemon/
+//       metadata/hardlink_sources.rs:107-153, then check_and_hardlink, src/
+//       daemon/disk/public.rs:285-346): which files of the new image INDEX
+//       can be linked from the older images -- SRCDIR with its index
+//       SRCINDEX (split at the last `=`), best source first.  Prints
+//       `SRCDIR<TAB>PATH` (the path as the index spells it) for every
+//       candidate that passed the re-hash and the mode test, a summary on
+//       stderr, and exits 0 when the check ran.  Nothing is linked.
 #include <dirent.h>
 #include <errno.h>
 #include <fcntl.h>
@@ -40,7 +49,9 @@ static void usage() {
           "usage: ciruela-index sync [--disk-threads N] [--block-size N] [--index-dir D]\n"
           "                          (--append|--append-weak|--replace) SRC:/DEST ...\n"
           "       ciruela-index hash [--block-size N] FILE...\n"
-          "       ciruela-index check DIR INDEX_FILE [--disk-threads N]\n");
+          "       ciruela-index check DIR INDEX_FILE [--disk-threads N]\n"
+          "       ciruela-index links INDEX SRCDIR=SRCINDEX [SRCDIR=SRCINDEX ...]"
+          " [--disk-threads N]\n");
 }
 
 static std::string hex(const uint8_t* p, size_t n) {
@@ -137,6 +148,51 @@ struct Job {
   std::string kind, src, dest;
 };
 
+static bool read_file(const std::string& path, std::vector<uint8_t>* out) {
+  FILE* f = fopen(path.c_str(), "rb");
+  if (!f) {
+    perror(path.c_str());
+    return false;
+  }
+  uint8_t buf[65536];
+  size_t r;
+  while ((r = fread(buf, 1, sizeof buf, f)) > 0) out->insert(out->end(), buf, buf + r);
+  const bool bad = ferror(f) != 0;
+  fclose(f);
+  if (bad) fprintf(stderr, "%s: read error\n", path.c_str());
+  return !bad;
+}
+
+// The paths of an index's file entries, in index order and as the index
+// spells them (escaped): a directory line starts with '/', an entry line with
+// two spaces, and its second field is f or x for a file.
+static std::vector<std::string> index_file_paths(const std::vector<uint8_t>& index) {
+  std::vector<std::string> out;
+  std::string dir;
+  size_t pos = 0;
+  bool header = true;
+  while (pos < index.size()) {
+    const void* nl = memchr(index.data() + pos, '\n', index.size() - pos);
+    const size_t e = nl ? (size_t)((const uint8_t*)nl - index.data()) : index.size();
+    const std::string line(reinterpret_cast<const char*>(index.data()) + pos, e - pos);
+    pos = e + 1;
+    if (header) {
+      header = false;
+      continue;
+    }
+    if (!line.empty() && line[0] == '/') {
+      dir = line;
+    } else if (line.size() > 2 && line[0] == ' ' && line[1] == ' ') {
+      const size_t sp = line.find(' ', 2);
+      if (sp == std::string::npos || sp + 1 >= line.size()) continue;
+      if ((line[sp + 1] == 'f' || line[sp + 1] == 'x') &&
+          (sp + 2 == line.size() || line[sp + 2] == ' '))
+        out.push_back((dir == "/" ? "" : dir) + "/" + line.substr(2, sp - 2));
+    }
+  }
+  return out;
+}
+
 // split "source:/dir/dest" (src/client/sync/uploads.rs:25-33)
 static bool split(const std::string& cli, std::string* src, std::string* dest) {
   const size_t c = cli.find(':');
@@ -199,7 +255,7 @@ int main(int argc, char** argv) {
         return 2;
       }
       jobs.push_back(j);
-    } else if ((cmd == "hash" || cmd == "check") && a.size() && a[0] != '-') {
+    } else if ((cmd == "hash" || cmd == "check" || cmd == "links") && a.size() && a[0] != '-') {
       files.push_back(a);
     } else {
       usage();
@@ -210,8 +266,27 @@ int main(int argc, char** argv) {
     usage();
     return 2;
   }
-  std::vector<std::string> inputs = files;
+  std::vector<std::string> link_dirs;
+  std::vector<std::vector<uint8_t>> link_indexes;
+  if (cmd == "links") {
+    if (files.size() < 2) {
+      usage();
+      return 2;
+    }
+    for (size_t i = 1; i < files.size(); ++i) {
+      const size_t eq = files[i].rfind('=');
+      if (eq == std::string::npos || eq == 0 || eq + 1 == files[i].size()) {
+        usage();
+        return 2;
+      }
+      link_dirs.push_back(files[i].substr(0, eq));
+      link_indexes.emplace_back();
+      if (!read_file(files[i].substr(eq + 1), &link_indexes.back())) return 2;
+    }
+  }
+  std::vector<std::string> inputs = cmd == "links" ? link_dirs : files;
   std::vector<uint8_t> check_index;
+  if (cmd == "links" && !read_file(files[0], &check_index)) return 2;
   if (cmd == "check") {
     // the index is read (and a missing one reported) before any device is
     // opened; the staging slots are sized from the image alone
@@ -319,6 +394,47 @@ int main(int argc, char** argv) {
       fflush(stdout);
       return 1;
     }
+  } else if (cmd == "links") {
+    static const uint8_t none = 0;
+    const uint8_t* index = check_index.empty() ? &none : check_index.data();
+    std::vector<const uint8_t*> sidx;
+    std::vector<size_t> slen;
+    for (const std::vector<uint8_t>& v : link_indexes) {
+      sidx.push_back(v.empty() ? &none : v.data());
+      slen.push_back(v.size());
+    }
+    uint64_t* lf = nullptr;
+    uint32_t* ls = nullptr;
+    size_t nl = 0, skipped = 0;
+    rc = cir_link_candidates(index, check_index.size(), sidx.data(), slen.data(), sidx.size(), &lf,
+                             &ls, &nl, &skipped);
+    if (rc) {
+      die(rc, files[0].c_str());
+      return 2;
+    }
+    std::vector<int> dirfds(link_dirs.size(), AT_FDCWD);
+    std::vector<const char*> dirs;
+    for (const std::string& d : link_dirs) dirs.push_back(d.c_str());
+    std::vector<uint8_t> kinds(nl);
+    uint64_t st[CIR_LINKS_STATS_FIELDS];
+    rc = cir_check_links(ctx, index, check_index.size(), dirfds.data(), dirs.data(), dirs.size(),
+                         lf, ls, nl, threads, kinds.data(), nullptr, st);
+    if (rc) {
+      die(rc, files[0].c_str());
+      return 2;
+    }
+    const std::vector<std::string> paths = index_file_paths(check_index);
+    for (size_t i = 0; i < nl; ++i)
+      if (kinds[i] == CIR_CHECK_OK && lf[i] < paths.size())
+        printf("%s\t%s\n", link_dirs[ls[i]].c_str(), paths[lf[i]].c_str());
+    fflush(stdout);
+    fprintf(stderr,
+            "links: %zu candidates: %llu ok, %llu checksum, %llu read; %zu source index(es) "
+            "skipped\n",
+            nl, (unsigned long long)st[0], (unsigned long long)st[1], (unsigned long long)st[2],
+            skipped);
+    cir_free(lf);
+    cir_free(ls);
   } else if (cmd == "sync") {
     if (jobs.empty()) {
       usage();

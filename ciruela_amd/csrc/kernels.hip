@@ -23,6 +23,8 @@
 //   k_verify         : digest compare of the daemon-side batch verify.
 //   k_first_bad      : the same compare for the commit-time check of a whole
 //                      image: only the first bad digest's index and a count.
+//   k_seg_bad        : the same compare for the hardlink candidates: one bad
+//                      flag per segment (file) of the batch.
 //   k_compress_only  : register-only compressions (live VALU ceiling).
 //   k_fill_splitmix64: synthetic test data (bench / tests only).
 //
@@ -1126,6 +1128,74 @@ hipError_t launch_first_bad(const uint8_t* got, const uint8_t* want, uint64_t n,
   if (e != hipSuccess || n == 0) return e;
   hipLaunchKernelGGL(k_first_bad, dim3(grid_for(n, kThreads)), dim3(kThreads), 0, s, got, want, n,
                      base, reinterpret_cast<unsigned long long*>(first), nbad, flag);
+  return hipGetLastError();
+}
+
+// Hardlink candidates (try_hardlink, src/daemon/disk/public.rs:285-346: every
+// candidate file is re-hashed on its own and a bad one never affects another):
+// a per-segment verdict out of one batch of digest compares.  Segment s is
+// the blocks [seg_end[s-1], seg_end[s]); the compare is k_first_bad's, and
+// only a mismatching lane looks its segment up (the first s with seg_end[s] >
+// b, by bisection: every read of seg_end stays inside [0, nseg)) and stores a
+// 1 at seg_bad[s], clamped to nseg - 1 so that no table can send the store
+// elsewhere.  A wave without a mismatch issues no store and no atomic.  The
+// flags and the count are zeroed by k_seg_init and the bad segments counted
+// by k_seg_count, on the same stream (launch_seg_bad).
+__global__ void k_seg_init(uint8_t* __restrict__ seg_bad, uint64_t nseg,
+                           uint32_t* __restrict__ nbad_seg) {
+  const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < nseg) seg_bad[i] = 0;
+  if (i == 0 && nbad_seg) *nbad_seg = 0;
+}
+
+__global__ void k_seg_bad(const uint8_t* __restrict__ got, const uint8_t* __restrict__ want,
+                          uint64_t n, const uint32_t* __restrict__ seg_end, uint64_t nseg,
+                          uint8_t* __restrict__ seg_bad, const uint8_t* __restrict__ flag) {
+  const uint64_t b = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  bool bad = false;
+  if (b < n) {
+    const uint4* g = reinterpret_cast<const uint4*>(got + 32 * b);
+    const uint4* w = reinterpret_cast<const uint4*>(want + 32 * b);
+    const uint4 g0 = g[0], g1 = g[1], w0 = w[0], w1 = w[1];
+    const uint32_t diff = (g0.x ^ w0.x) | (g0.y ^ w0.y) | (g0.z ^ w0.z) | (g0.w ^ w0.w) |
+                          (g1.x ^ w1.x) | (g1.y ^ w1.y) | (g1.z ^ w1.z) | (g1.w ^ w1.w);
+    bad = diff != 0 || (flag && flag[b]);
+  }
+  if (__ballot(bad) == 0) return;  // (wave-uniform)
+  if (bad) {
+    uint64_t lo = 0, hi = nseg;  // nseg >= 1 (launch_seg_bad)
+    while (lo < hi) {
+      const uint64_t mid = (lo + hi) >> 1;
+      if ((uint64_t)seg_end[mid] > b)
+        hi = mid;
+      else
+        lo = mid + 1;
+    }
+    seg_bad[lo < nseg ? lo : nseg - 1] = 1;
+  }
+}
+
+__global__ void k_seg_count(const uint8_t* __restrict__ seg_bad, uint64_t nseg,
+                            uint32_t* __restrict__ nbad_seg) {
+  const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const uint64_t mask = __ballot(i < nseg && seg_bad[i] != 0);
+  if (mask && (threadIdx.x & 63) == 0) atomicAdd(nbad_seg, (uint32_t)__popcll(mask));
+}
+
+hipError_t launch_seg_bad(const uint8_t* got, const uint8_t* want, uint64_t n,
+                          const uint32_t* seg_end, uint64_t nseg, uint8_t* seg_bad,
+                          uint32_t* nbad_seg, hipStream_t s, const uint8_t* flag) {
+  static_assert(kThreads % 64 == 0, "whole waves per workgroup");
+  hipLaunchKernelGGL(k_seg_init, dim3(grid_for(nseg ? nseg : 1, kThreads)), dim3(kThreads), 0, s,
+                     seg_bad, nseg, nbad_seg);
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess || n == 0 || nseg == 0) return e;
+  hipLaunchKernelGGL(k_seg_bad, dim3(grid_for(n, kThreads)), dim3(kThreads), 0, s, got, want, n,
+                     seg_end, nseg, seg_bad, flag);
+  e = hipGetLastError();
+  if (e != hipSuccess || !nbad_seg) return e;
+  hipLaunchKernelGGL(k_seg_count, dim3(grid_for(nseg, kThreads)), dim3(kThreads), 0, s, seg_bad,
+                     nseg, nbad_seg);
   return hipGetLastError();
 }
 

@@ -148,6 +148,17 @@ hipError_t launch_first_bad(const uint8_t* got, const uint8_t* want, uint64_t n,
                             uint64_t* first, uint32_t* nbad, hipStream_t s,
                             const uint8_t* flag = nullptr);
 
+// The same compare with a verdict per segment: segment s is the digests
+// [seg_end[s-1], seg_end[s]) (seg_end non-decreasing, seg_end[nseg-1] == n);
+// seg_bad[s] = 1 when any digest of s differs (or its flag is set), else 0;
+// *nbad_seg (device u32, nullable) = how many segments are bad.  All nseg
+// flags and the count are written here, on the same stream (also when n ==
+// 0); a mismatch's segment index is clamped to [0, nseg), so nothing outside
+// seg_bad[0 .. nseg) is written whatever seg_end holds.
+hipError_t launch_seg_bad(const uint8_t* got, const uint8_t* want, uint64_t n,
+                          const uint32_t* seg_end, uint64_t nseg, uint8_t* seg_bad,
+                          uint32_t* nbad_seg, hipStream_t s, const uint8_t* flag = nullptr);
+
 // nlanes x `lines` register-only compressions (diagnostic VALU ceiling).
 hipError_t launch_compress_only(uint64_t nlanes, uint32_t lines, uint8_t* out, hipStream_t s);
 

@@ -80,6 +80,15 @@ struct Slot {
   uint64_t want_blk = 0;
   uint64_t* d_cell = nullptr;
   uint64_t* h_cell = nullptr;
+  // links mode (cir_check_links): the batch's segment table (the end of each
+  // segment, in blocks of the batch) and the result {u32 bad segments, 12 B
+  // of padding, one flag byte per segment} with its pinned host twin; room
+  // for seg_cap segments, allocated on the first links check
+  uint32_t* h_seg_end = nullptr;
+  uint32_t* d_seg_end = nullptr;
+  uint8_t* h_seg_res = nullptr;
+  uint8_t* d_seg_res = nullptr;
+  uint64_t seg_cap = 0;
   hipEvent_t copied = nullptr;  // H2D of this slot finished (copy stream)
   hipEvent_t done = nullptr;    // digests of this slot are back in h_out
   // timing events (created on first use, recorded only while the device's
@@ -206,6 +215,7 @@ struct Device {
   int ensure_slot(Slot& s, uint64_t bytes, uint64_t nblk);
   int ensure_timing(Slot& s);
   int ensure_check(Slot& s);  // the check-mode buffers, sized to s.cap_blk
+  int ensure_links(Slot& s);  // those and the links-mode buffers, sized to s.cap_blk
 };
 
 // Every slot a staged loop submitted is waited for before the loop lets go
@@ -238,6 +248,12 @@ int slot_submit(Device& d, Slot& s, uint64_t bytes, uint64_t nblk, int ht = CIR_
 // after slot_wait, s.h_cell[0] = first bad block or UINT64_MAX, the low 32
 // bits of s.h_cell[1] = the number of bad blocks.
 int slot_submit_check(Device& d, Slot& s, uint64_t bytes, uint64_t nblk, int ht, uint64_t base);
+// Links mode: as check mode, with the batch's segment table in s.h_seg_end
+// (nseg entries, the last one nblk); the compare is launch_seg_bad and only
+// 16 + nseg bytes come back: after slot_wait, the u32 at s.h_seg_res = the
+// number of bad segments and s.h_seg_res[16 + k] = 1 when segment k is bad.
+constexpr uint64_t kSegResHead = 16;
+int slot_submit_links(Device& d, Slot& s, uint64_t bytes, uint64_t nblk, int ht, uint64_t nseg);
 int hash_desc_ordered(Device& d, const uint8_t* arena, const uint64_t* off, const uint32_t* len,
                       uint64_t n, uint8_t* out, hipStream_t s, int ht = CIR_HASH_BLAKE2B_256,
                       bool warm_only = false);

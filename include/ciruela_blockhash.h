@@ -264,6 +264,25 @@ int cir_verify_first_dev(cir_ctx* ctx, int hash_type, const void* d_arena, uint6
                          const uint8_t* d_expected, uint8_t* d_digests,
                          uint64_t* d_first, uint32_t* d_nbad, void* stream);
 
+/* cir_verify_first_dev with one verdict per segment instead of "which block first": the
+ * compare behind cir_check_links (try_hardlink, src/daemon/disk/public.rs:285-346, where a bad
+ * candidate never affects another, :303).  Segment s is the blocks [d_seg_end[s-1],
+ * d_seg_end[s]) with d_seg_end[-1] = 0; d_seg_end (device u32 x nseg) is non-decreasing, empty
+ * segments are allowed and d_seg_end[nseg-1] == nblk.  d_seg_bad[s] (device bytes x nseg) = 1
+ * when any block of s mismatches d_expected or is out of range (arena_bytes = UINT64_MAX:
+ * trusted descriptors), else 0; *d_nbad_seg (device u32, may be NULL) = the number of bad
+ * segments.  Every flag and the count are written on `stream` by the call itself (the caller
+ * initialises nothing; nblk == 0 writes zeros and 0), no digest travels back, a wave without a
+ * mismatch issues no store, and a mismatching block's segment index is clamped to [0, nseg), so
+ * nothing outside d_seg_bad[0 .. nseg) is written whatever d_seg_end holds.  CIR_EINVAL: a
+ * NULL d_seg_end or d_seg_bad, nseg == 0 with nblk > 0, and the alignment and argument cases
+ * of cir_verify_first_dev (d_seg_end and d_nbad_seg 4-byte aligned). */
+int cir_verify_segments_dev(cir_ctx* ctx, int hash_type, const void* d_arena, uint64_t arena_bytes,
+                            const uint64_t* d_off, const uint32_t* d_len, size_t nblk,
+                            const uint8_t* d_expected, uint8_t* d_digests,
+                            const uint32_t* d_seg_end, size_t nseg,
+                            uint8_t* d_seg_bad, uint32_t* d_nbad_seg, void* stream);
+
 /* Host-memory batch of the same check; ok_out (nblk bytes) may be NULL. */
 int cir_verify_blocks(cir_ctx* ctx, int hash_type, const uint8_t* h_arena, const uint64_t* off,
                       const uint32_t* len, size_t nblk, const uint8_t* expected, uint8_t* ok_out,
@@ -361,6 +380,72 @@ enum cir_check_kind { CIR_CHECK_OK = 0, CIR_CHECK_CHECKSUM = 1, CIR_CHECK_READ =
 int cir_check_index(cir_ctx* ctx, int dirfd, const char* dir, const uint8_t* index, size_t len,
                     uint32_t threads, int* kind_out, uint8_t** path_out, size_t* path_len,
                     uint64_t stats[CIR_CHECK_STATS_FIELDS]);
+
+/* scan_links (src/daemon/metadata/hardlink_sources.rs:107-153): which files of a new image
+ * may be hardlinked from older images of the same base directory.  `index` is the new image's
+ * index, src_index[j] / src_len[j] (j < nsrc) the older images' in the order the caller ranks
+ * them (the reference: newest first, :66-72).  Every file entry of `index` is visited in index
+ * order -- file ordinals count the file entries only, from 0 -- and for each the sources in the
+ * order given: a source matches when it lists a file at the same path with equal exe flag, size
+ * and digests (:131-133; a symlink or a directory at that path does not match), and the first
+ * match makes the candidate (file ordinal, source ordinal) and ends the entry's search (the
+ * break at :143).  So there is at most one candidate per file and file_out is strictly
+ * increasing.  *file_out / *src_out hold *n_out values each (malloc'd: cir_free; NULL when
+ * *n_out == 0).  A source that does not parse (the reference skips it with a warning, :95-101)
+ * or whose hash type or block size is not the new index's takes no part and is counted in
+ * *nskipped_out (may be NULL).  CIR_EPARSE / CIR_EHASHSIZE: `index` does not parse;
+ * CIR_EINVAL: null arguments.  Host only.  (The reference walks the sources through the
+ * MergedSignatures iterator of the external dir-signature crate, which is not in its tree:
+ * the matching rule above is what :121-146 show of it.) */
+int cir_link_candidates(const uint8_t* index, size_t len,
+                        const uint8_t* const* src_index, const size_t* src_len, size_t nsrc,
+                        uint64_t** file_out, uint32_t** src_out, size_t* n_out,
+                        size_t* nskipped_out);
+
+/* check_and_hardlink's verify (try_hardlink, src/daemon/disk/public.rs:285-346) over every
+ * candidate in one call: candidate i is file entry link_file[i] of `index` (an ordinal as in
+ * cir_link_candidates; need not be sorted or unique), looked for at the entry's path under
+ * source root link_src[i] -- src_dir[j] opened relative to src_dirfd[j] (AT_FDCWD allowed;
+ * src_dir[j] == NULL: src_dirfd[j] itself).  The candidates go through cir_check_index's
+ * staging pipeline without its stop at the first failure: a batch carries a segment table (one
+ * segment = one candidate's run of blocks in the batch), cir_verify_segments_dev's compare
+ * answers per segment and only one flag byte per segment and a count come back.  Hash type and
+ * block size come from the index header; threads as in cir_scan_v1.
+ *
+ * Each candidate gets its verdict in isolation, in kind_out[i] (a cir_check_kind), with the
+ * errno of a READ in errno_out[i] (may be NULL; else 0):
+ *   CIR_CHECK_READ      the source root or a directory component cannot be opened (:315-319;
+ *                       components one at a time, O_DIRECTORY | O_NOFOLLOW), the file cannot
+ *                       be opened with openat(O_NOFOLLOW) in its directory (:322), is not
+ *                       regular, fails to read (:324), or changes identity (st_dev, st_ino,
+ *                       st_size) between the packer's look and the read.  A root that does not
+ *                       open makes READ of its candidates, not a failed call.
+ *   CIR_CHECK_CHECKSUM  (when not READ) the length is not the index's (the file is not read),
+ *                       a block digest differs (:326), or st_mode & 0777 is not 0755 for an
+ *                       exe entry, 0644 otherwise (:331-338; found by the packer's fstat, and
+ *                       such a file is not read either).
+ *   CIR_CHECK_OK        otherwise.
+ * A size-0 candidate is examined on the host alone: it must exist as an empty regular file of
+ * the right mode (a missing one is READ: there is nothing to link, unlike cir_check_index's
+ * "absent passes").
+ *
+ * Read-only: nothing is linked, created or chmod'ed (link(2) and ensure_path, :340-342, stay
+ * the caller's).  File descriptors held at once: the roots, one directory and one file per
+ * packer and per reader thread.  Several devices take stripes of the candidates' block order;
+ * every candidate is independent, so the verdicts do not depend on timing.
+ *
+ * Returns CIR_OK whenever every candidate got a verdict.  CIR_EINVAL (before any I/O): null
+ * arguments, link_file[i] past the last file entry, link_src[i] >= nsrc; CIR_EPARSE /
+ * CIR_EHASHSIZE as cir_check_index.
+ *
+ * stats: [0] candidates OK, [1] CHECKSUM, [2] READ, [3] blocks hashed, [4] bytes read, [5]
+ * batches, [6] peak of the file descriptors held at once, [7] size-0 candidates examined. */
+#define CIR_LINKS_STATS_FIELDS 8
+int cir_check_links(cir_ctx* ctx, const uint8_t* index, size_t len,
+                    const int* src_dirfd, const char* const* src_dir, size_t nsrc,
+                    const uint64_t* link_file, const uint32_t* link_src, size_t nlinks,
+                    uint32_t threads, uint8_t* kind_out, int32_t* errno_out,
+                    uint64_t stats[CIR_LINKS_STATS_FIELDS]);
 
 /* ---- index (DIRSIGNATURE.v1) ----------------------------------------- */
 
