@@ -34,6 +34,13 @@ Context.check_links,            check_and_hardlink's re-hash and mode test of ev
                                 (src/daemon/disk/public.rs:285-346)
 Context.verify_segments_dev     the same compare on the device, one flag per segment
                                 (src/daemon/disk/public.rs:285-346)
+Context.check_blocks,           what "Resuming download" lacks: which blocks a partial
+  check_blocks                  image already holds, one bit per block, so that
+                                fill_blocks need not queue everything again
+                                (src/daemon/tracking/mod.rs:561-585,
+                                src/daemon/disk/public.rs:91-93,
+                                src/daemon/tracking/progress.rs:129-170)
+Context.verify_bitmap_dev       the same compare on the device, one bit per block
 =============================  ==============================================
 
 All hashing runs on gfx950 through the library; there is no CPU fallback.
@@ -50,6 +57,7 @@ __all__ = [
     "InMemoryIndexes", "ThreadedBlockReader", "BlockHint", "Context", "default_context",
     "IndexError_", "DirError", "ReadError", "CiruelaError", "NoDevice", "sha512_256",
     "check_index", "CheckResult", "link_candidates", "check_links", "LinksResult",
+    "check_blocks", "BlocksResult",
 ]
 
 DEFAULT_BLOCK_SIZE = 32768
@@ -266,6 +274,17 @@ class Context:
                                                 nblk, d_expected, d_digests, d_seg_end, nseg,
                                                 d_seg_bad, d_nbad_seg, stream))
 
+    def verify_bitmap_dev(self, d_arena, arena_bytes, d_off, d_len, nblk, d_expected, d_digests,
+                          d_have, d_nbad=0, stream=0, hash_type=None):
+        """verify_first_dev with one bit per block: bit (b & 63) of
+        d_have[b >> 6] (device u64 x ceil(nblk / 64)) = 1 when block b matches
+        and is in range; the last word's bits past nblk are 0 and nothing past
+        that word is written.  *d_nbad (device u32, optional) = how many bits
+        are 0.  All written by the call."""
+        ht = (hash_type or HashType.blake2b_256()).code
+        _n.check(_n.lib.cir_verify_bitmap_dev(self._h, ht, d_arena, arena_bytes, d_off, d_len,
+                                              nblk, d_expected, d_digests, d_have, d_nbad, stream))
+
     # ---- asynchronous per-block verify (FetchBlock::poll, fetch_blocks.rs:77)
     def verify_submit(self, data, expected, hash_type=None):
         """Queue one block with its expected digest; returns a ticket."""
@@ -386,6 +405,42 @@ class Context:
         del keep
         return LinksResult(index, links, list(kinds)[:n], list(errnos)[:n],
                            dict(zip(self.LINKS_STATS_FIELDS, list(stats))))
+
+    BLOCKS_STATS_FIELDS = ("have", "missing", "complete", "absent", "partial", "blocked", "bytes",
+                           "batches", "peak_fds", "unread_blocks")
+
+    def check_blocks(self, root, index, threads=0, dir_fd=None):
+        """Which blocks of `index` the partial image at `root` (relative to
+        dir_fd when given; root=None: dir_fd itself) already holds: a
+        BlocksResult with one bit per block and one state per file.  What
+        "Resuming download" (src/daemon/tracking/mod.rs:561-585) would need in
+        order not to fetch everything again; nothing is written."""
+        if len(index):
+            ptr, keep = _buf(index)
+        else:  # (an empty index is a parse error, not a null argument)
+            keep = ctypes.create_string_buffer(1)
+            ptr = ctypes.cast(keep, ctypes.c_void_p)
+        if root is None and dir_fd is None:
+            raise ValueError("check_blocks needs a root path or a directory fd")
+        fd = -100 if dir_fd is None else dir_fd  # AT_FDCWD
+        have = ctypes.c_void_p()
+        nblk = ctypes.c_uint64()
+        state = ctypes.c_void_p()
+        errs = ctypes.c_void_p()
+        nfiles = ctypes.c_size_t()
+        stats = (ctypes.c_uint64 * _n.CIR_BLOCKS_STATS_FIELDS)()
+        _n.check(_n.lib.cir_check_blocks(self._h, fd, None if root is None else os.fsencode(root),
+                                         ptr, len(index), threads, ctypes.byref(have),
+                                         ctypes.byref(nblk), ctypes.byref(state),
+                                         ctypes.byref(errs), ctypes.byref(nfiles), stats))
+        del keep
+        nf = nfiles.value
+        bits = _n.take_buffer(have.value, 8 * ((nblk.value + 63) // 64))
+        states = _n.take_buffer(state.value, nf)
+        raw = _n.take_buffer(errs.value, 4 * nf)
+        errnos = list((ctypes.c_int32 * nf).from_buffer_copy(raw)) if nf else []
+        return BlocksResult(index, nblk.value, bits, list(states), errnos,
+                            dict(zip(self.BLOCKS_STATS_FIELDS, list(stats))))
 
     def scan(self, config):
         dirs = [os.fsencode(d) for d, _ in config._dirs]
@@ -548,6 +603,81 @@ class LinksResult:
     def __repr__(self):
         return "LinksResult(%d ok, %d checksum, %d read)" % (
             self.stats["ok"], self.stats["checksum"], self.stats["read"])
+
+
+def _file_blocks(index):
+    """(path as raw bytes, size, block count) of an index's file entries, in
+    index order, and the index's block size."""
+    lines = bytes(index).split(b"\n")
+    bs = 0
+    for tok in lines[0].split(b" "):
+        if tok.startswith(b"block_size="):
+            bs = int(tok[len(b"block_size="):])
+    out = []
+    cur = b"/"
+    for line in lines[1:]:
+        if line.startswith(b"/"):
+            cur = _unescape(line)
+        elif line.startswith(b"  "):
+            tok = line[2:].split(b" ")
+            if len(tok) >= 3 and tok[1] in (b"f", b"x"):
+                size = int(tok[2])
+                out.append(((b"" if cur == b"/" else cur) + b"/" + _unescape(tok[0]), size,
+                            (size + bs - 1) // bs if bs else 0))
+    return out, bs
+
+
+class BlocksResult:
+    """Verdict of check_blocks.  nblk: the index's blocks, numbered in index
+    order over its file entries; have: their bitmap as bytes (bit g & 7 of
+    byte g >> 3), has(g) one bit of it.  Per file entry, in index order:
+    states ("complete", "absent", "partial" or "blocked"), long (the file is
+    longer than its entry and is to be truncated before commit), errnos (of a
+    "blocked", else 0).  complete: every file is complete.  missing(): the
+    (path as raw bytes, byte offset) of every block that is not there, in
+    index order -- what fill_blocks would queue
+    (src/daemon/tracking/progress.rs:136-151)."""
+
+    __slots__ = ("nblk", "have", "states", "long", "errnos", "stats", "_index")
+    STATES = {_n.CIR_FILE_COMPLETE: "complete", _n.CIR_FILE_ABSENT: "absent",
+              _n.CIR_FILE_PARTIAL: "partial", _n.CIR_FILE_BLOCKED: "blocked"}
+
+    def __init__(self, index, nblk, have, states, errnos, stats):
+        self._index = index  # (split into lines only when missing() is asked for)
+        self.nblk = nblk
+        self.have = bytes(have)  # (little-endian u64 words: byte order is bit order)
+        self.states = [self.STATES[s & 3] for s in states]
+        self.long = [bool(s & _n.CIR_FILE_LONG) for s in states]
+        self.errnos = list(errnos)
+        self.stats = stats
+
+    def has(self, g):
+        if not 0 <= g < self.nblk:
+            raise IndexError("block %r of %d" % (g, self.nblk))
+        return bool(self.have[g >> 3] >> (g & 7) & 1)
+
+    @property
+    def complete(self):
+        return all(s == "complete" for s in self.states)
+
+    def __bool__(self):
+        return self.complete
+
+    def missing(self):
+        files, bs = _file_blocks(self._index)
+        out = []
+        g = 0
+        for path, _, n in files:
+            for j in range(n):
+                if not self.has(g + j):
+                    out.append((path, j * bs))
+            g += n
+        return out
+
+    def __repr__(self):
+        return "BlocksResult(%d of %d blocks; %s)" % (
+            self.stats["have"], self.nblk,
+            ", ".join("%d %s" % (self.states.count(s), s) for s in self.STATES.values()))
 
 
 _default = None
@@ -779,6 +909,11 @@ def check_index(root, index, threads=0, dir_fd=None, context=None):
 def check_links(index, roots, links, threads=0, context=None):
     """Context.check_links on the default context."""
     return (context or default_context()).check_links(index, roots, links, threads)
+
+
+def check_blocks(root, index, threads=0, dir_fd=None, context=None):
+    """Context.check_blocks on the default context."""
+    return (context or default_context()).check_blocks(root, index, threads, dir_fd)
 
 
 def link_candidates(index, sources):

@@ -51,6 +51,12 @@ CIR_CHECK_CHECKSUM = 1
 CIR_CHECK_READ = 2
 CIR_CHECK_STATS_FIELDS = 8
 CIR_LINKS_STATS_FIELDS = 8
+CIR_BLOCKS_STATS_FIELDS = 10
+CIR_FILE_COMPLETE = 0
+CIR_FILE_ABSENT = 1
+CIR_FILE_PARTIAL = 2
+CIR_FILE_BLOCKED = 3
+CIR_FILE_LONG = 0x80  # or'ed into a file's state: longer on disk than its entry
 CIR_INIT_ONE_SHOT = 1  # cir_init_n: one stream and one staging slot per device
 CIR_STAGING_LAZY = (1 << 64) - 1  # cir_init: no staging slots until a host path needs them
 
@@ -146,6 +152,12 @@ _SIGS = {
                                        ctypes.POINTER(ctypes.c_char_p), ctypes.c_size_t, c_u64p,
                                        c_u32p, ctypes.c_size_t, ctypes.c_uint32, c_u8p,
                                        ctypes.POINTER(ctypes.c_int32), c_u64p]),
+    "cir_verify_bitmap_dev": (ctypes.c_int, [c_vp, ctypes.c_int, c_vp, ctypes.c_uint64, c_vp, c_vp,
+                                             ctypes.c_size_t, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    "cir_check_blocks": (ctypes.c_int, [c_vp, ctypes.c_int, ctypes.c_char_p, c_vp, ctypes.c_size_t,
+                                        ctypes.c_uint32, ctypes.POINTER(c_vp), c_u64p,
+                                        ctypes.POINTER(c_vp), ctypes.POINTER(c_vp), c_sizep,
+                                        c_u64p]),
     "cir_debug_compress_only_dev": (ctypes.c_int, [ctypes.c_uint64, ctypes.c_uint32, c_vp, c_vp]),
     "cir_debug_relay_blocks": (ctypes.c_uint64, [ctypes.c_uint64, ctypes.c_uint64]),
     "cir_debug_device_identity": (ctypes.c_int, [ctypes.c_int, ctypes.c_char_p, ctypes.c_size_t,

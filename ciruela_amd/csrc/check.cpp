@@ -1,6 +1,7 @@
 // cir_check_index: the re-hash loop of commit_image over a whole image
 // (and, below it, cir_check_links: the same pipeline with a verdict per file
-// for the hardlink candidates of check_and_hardlink).
+// for the hardlink candidates of check_and_hardlink, and cir_check_blocks: the
+// same pipeline with a verdict per block, for the resume of a partial image).
 //
 // Reference: commit_image (src/daemon/disk/commit.rs:51-117) walks the
 // index's entries in order, re-hashes every non-empty file
@@ -50,6 +51,7 @@
 #include <string>
 #include <vector>
 
+#include "bits.hpp"
 #include "dirsig.hpp"
 #include "runtime.hpp"
 #include "stripes.hpp"
@@ -1127,8 +1129,539 @@ int links_impl(cir_ctx* ctx, const uint8_t* index, size_t len, const int* src_di
   return CIR_OK;
 }
 
+// ---- cir_check_blocks -----------------------------------------------------
+//
+// The resume the reference does not have: after a restart it finds the image
+// unfinished ("Resuming download", src/daemon/tracking/mod.rs:561-585), removes
+// the partial .tmp directory (start_image, src/daemon/disk/public.rs:91-93) and
+// queues every block again (fill_blocks, src/daemon/tracking/progress.rs:
+// 129-170).  Here the directory is kept and every block of the index gets one
+// bit: present and correct, or not.  The pipeline is links_range's -- no stop,
+// every file on its own -- over one root in index order; a file may be short
+// (only the blocks wholly inside the length the packer saw are packed), long
+// (its blocks up to the entry's size are judged) or missing.  A slot keeps a
+// host-side run table in place of a segment table: each run of packed blocks
+// with its place in the batch and in the global block order; launch_block_bits
+// answers with one bit per block of the batch and slot_wait's side copies each
+// run's bits into the device's bitmap (bits.hpp).  Several devices take
+// stripes of the global block order, each into a bitmap of its own; every
+// block has one owner, so the merge is an OR and does not depend on timing.
+
+// What the looks and the reads found of a file.
+constexpr uint8_t kLookAbsent = 1, kLookBlocked = 2, kLookShort = 4, kLookLong = 8;
+
+struct Blocks {
+  const dirsig::Index* idx = nullptr;
+  uint64_t bs = 0;
+  int ht = CIR_HASH_BLAKE2B_256;
+  int root = -1;
+  std::vector<std::vector<std::string>> dirs;
+  std::vector<Item> items;   // every file entry, in index order
+  std::vector<size_t> work;  // the non-empty ones (indices into items), in index order
+  uint64_t nblk_total = 0;
+  FdCount fds;
+  std::mutex mu;
+  // what the looks and the reads found of each file (kLook* bits), and the
+  // errno of the first thing that blocked it
+  std::vector<uint8_t> look;
+  std::vector<int32_t> err;
+  std::atomic<uint64_t> n_bytes{0}, n_batches{0}, n_unread{0};
+
+  void report(size_t item, uint8_t bits, int e = 0) {
+    std::lock_guard<std::mutex> lk(mu);
+    if ((bits & kLookBlocked) && !(look[item] & kLookBlocked)) err[item] = e;
+    look[item] |= bits;
+  }
+};
+
+// What keeps a file from being judged: ENOENT (on it or on a directory
+// component) is ABSENT, everything else BLOCKED.
+uint8_t look_of_errno(int e) { return e == ENOENT ? kLookAbsent : kLookBlocked; }
+
+// The packer's look at a non-empty entry: false with the file's state
+// reported, else what identifies the file to the readers and its length.
+bool examine_block_file(Blocks& B, const DirFd& d, size_t item, Seen* seen, uint64_t* cur_len) {
+  const Item& it = B.items[item];
+  int fd = -1, e = 0;
+  struct stat st;
+  if (open_listed_at(B.fds, d, it, &fd, &st, &e) != CIR_CHECK_OK) {
+    B.report(item, look_of_errno(e), e);
+    return false;
+  }
+  B.fds.close(fd);
+  seen->dev = st.st_dev;
+  seen->ino = st.st_ino;
+  *cur_len = (uint64_t)st.st_size;
+  if (*cur_len < it.size) B.report(item, kLookShort);
+  if (*cur_len > it.size) B.report(item, kLookLong);
+  return true;
+}
+
+// A size-0 entry, judged by the host alone.
+void examine_block_empty(Blocks& B, const DirFd& d, size_t item) {
+  const Item& it = B.items[item];
+  if (d.fd < 0) {
+    B.report(item, look_of_errno(d.err), d.err);
+    return;
+  }
+  struct stat st;
+  if (::fstatat(d.fd, it.name.c_str(), &st, AT_SYMLINK_NOFOLLOW) != 0) {
+    B.report(item, look_of_errno(errno), errno);
+    return;
+  }
+  if (!S_ISREG(st.st_mode))  // (the errno an openat(O_NOFOLLOW) and the fstat test would give)
+    B.report(item, kLookBlocked,
+             S_ISDIR(st.st_mode) ? EISDIR : S_ISLNK(st.st_mode) ? ELOOP : EINVAL);
+  else if (st.st_size != 0)
+    B.report(item, kLookLong);
+}
+
+struct BlockJob {
+  size_t item;
+  Seen seen;
+  uint64_t seen_len;  // the file's length at the packer's look
+  uint64_t file_off, len;
+  uint8_t* dst;
+};
+
+// Read the batch's jobs on `threads` readers.  Every job is tried; a failed
+// one blocks its own file and nothing else.
+void run_block_reads(Blocks& B, const std::vector<BlockJob>& jobs, unsigned threads) {
+  std::atomic<size_t> next{0};
+  const bool nt = stage_copy_nt();
+  auto worker = [&] {
+    DirFd d;  // this reader's directory, kept across the jobs that share it
+    size_t d_dir = SIZE_MAX;
+    for (;;) {
+      const size_t i = next.fetch_add(1);
+      if (i >= jobs.size()) break;
+      const BlockJob& j = jobs[i];
+      const Item& it = B.items[j.item];
+      if (d_dir != it.dir) {
+        close_dir_at(B.fds, d);
+        d = open_dir_at(B.fds, B.root, B.dirs[it.dir]);
+        d_dir = it.dir;
+      }
+      int fd = -1, e = 0;
+      struct stat st;
+      bool ok = open_listed_at(B.fds, d, it, &fd, &st, &e) == CIR_CHECK_OK;
+      if (ok && (st.st_dev != j.seen.dev || st.st_ino != j.seen.ino ||
+                 (uint64_t)st.st_size < j.seen_len)) {
+        ok = false;  // not the file that was packed, or it shrank
+        e = ESTALE;
+      }
+      uint64_t got = 0;
+      while (ok && got < j.len) {
+        const ssize_t r =
+            pread_staged(fd, j.dst + got, j.len - got, (off_t)(j.file_off + got), nt);
+        if (r < 0 && errno == EINTR) continue;
+        if (r <= 0) {
+          ok = false;
+          e = r == 0 ? ENODATA : errno;  // the file shrank under the read
+          break;
+        }
+        got += (uint64_t)r;
+      }
+      B.fds.close(fd);
+      if (!ok) B.report(j.item, kLookBlocked, e);
+    }
+    close_dir_at(B.fds, d);
+  };
+  parallel_run(std::max(1u, std::min<unsigned>(threads, (unsigned)jobs.size())), worker);
+}
+
+// One run of packed blocks: `count` blocks from block `at` of the batch are
+// the global blocks from `global` on.
+struct BitRun {
+  uint64_t at, global, count;
+};
+
+// links_range for the blocks of one image: the block ranges `ranges`
+// (increasing, of the global block order) on device d, their verdicts into
+// `have` (this device's bitmap of the whole image, zeroed by the caller).  A
+// file is looked at by every range that holds some of its blocks.
+int blocks_range(cir_ctx* ctx, Device& d, Blocks& B, unsigned threads, const BlockRanges& ranges,
+                 uint64_t* have) {
+  if (ranges.empty()) return CIR_OK;
+  std::lock_guard<std::mutex> lk(d.mu);
+  DeviceGuard guard;
+  CIR_HIP(hipSetDevice(d.id));
+  SlotDrain drain{d};  // an early return leaves no slot busy
+  const std::vector<size_t>& work = B.work;
+  const uint64_t bs = B.bs;
+  uint64_t seg = 0;
+  for (size_t w : work) seg = std::max(seg, std::min<uint64_t>(B.items[w].size, bs));
+  const uint64_t cap = (std::max<uint64_t>(ctx->staging, seg + 16) + 15) & ~15ull;
+  const uint64_t cap_blk = std::max<uint64_t>(cap / 512, 4096);
+  uint64_t fill = scan_ramp() ? std::max<uint64_t>(seg + 16, cap >> 3) : cap;
+
+  size_t ri = 0;
+  uint64_t b0 = 0, b1 = 0;
+  size_t wi = 0;               // the file being packed (index into work)
+  uint64_t fblk = 0;           // its next block
+  size_t examined = SIZE_MAX;  // the file whose look passed (in this range)
+  Seen seen;
+  uint64_t cur_len = 0;        // its length at that look
+  DirFd cur;                   // the packer's directory
+  size_t cur_dir = SIZE_MAX;
+  struct CloseCur {
+    Blocks& B;
+    DirFd& d;
+    ~CloseCur() { close_dir_at(B.fds, d); }
+  } close_cur{B, cur};
+  auto dir_of = [&](const Item& it) -> const DirFd& {
+    if (cur_dir != it.dir) {
+      close_dir_at(B.fds, cur);
+      cur = open_dir_at(B.fds, B.root, B.dirs[it.dir]);
+      cur_dir = it.dir;
+    }
+    return cur;
+  };
+  constexpr int kS = Device::kSlots;
+  std::vector<BitRun> runs[kS];  // per slot in flight
+  auto start_range = [&](size_t r) {
+    ri = r;
+    b0 = ranges[r].first;
+    b1 = ranges[r].second;
+    wi = std::lower_bound(work.begin(), work.end(), b0,
+                          [&](size_t x, uint64_t b) { return B.items[x].first_blk < b; }) -
+         work.begin();
+    fblk = 0;
+    if (wi > 0 && B.items[work[wi - 1]].first_blk + B.items[work[wi - 1]].nblk > b0) {
+      --wi;
+      fblk = b0 - B.items[work[wi]].first_blk;
+    }
+    examined = SIZE_MAX;
+  };
+  auto here = [&] { return wi < work.size() && B.items[work[wi]].first_blk + fblk < b1; };
+  auto more = [&] {
+    while (!here()) {
+      if (ri + 1 >= ranges.size()) return false;
+      start_range(ri + 1);
+    }
+    return true;
+  };
+  auto busy = [&] {
+    for (const Slot& s : d.slot)
+      if (s.busy) return true;
+    return false;
+  };
+  start_range(0);
+  // CIR_TRACE: where this device's host thread spent the call
+  const bool trace = trace_enabled();
+  using Clock = std::chrono::steady_clock;
+  double t_wait = 0, t_pack = 0, t_read = 0, t_submit = 0;
+  uint64_t n_batches = 0;
+  auto lap = [&](Clock::time_point& t0, double& acc) {
+    if (!trace) return;
+    const Clock::time_point t1 = Clock::now();
+    acc += std::chrono::duration<double, std::milli>(t1 - t0).count();
+    t0 = t1;
+  };
+  int k = 0;
+  while (more() || busy()) {
+    Slot& s = d.slot[k];
+    Clock::time_point t0 = trace ? Clock::now() : Clock::time_point();
+    if (s.busy) {
+      int rc = slot_wait(d, s);
+      if (rc) return rc;
+      const uint64_t* bits = reinterpret_cast<const uint64_t*>(s.h_bits + kBitsResHead);
+      for (const BitRun& r : runs[k]) copy_bits(have, r.global, bits, r.at, r.count);
+    }
+    lap(t0, t_wait);
+    if (more()) {
+      int rc = d.ensure_slot(s, cap, cap_blk);
+      if (rc) return rc;
+      rc = d.ensure_blocks(s);
+      if (rc) return rc;
+      std::vector<BlockJob> jobs;
+      std::vector<BitRun>& rs = runs[k];
+      rs.clear();
+      uint64_t pos = 0, n = 0, used = 0, file_bytes = 0;
+      while (here() && n < cap_blk) {
+        const size_t item = work[wi];
+        const Item& it = B.items[item];
+        const uint64_t in_range = std::min<uint64_t>(it.nblk - fblk, b1 - (it.first_blk + fblk));
+        // its blocks in this range are passed over (their bits stay 0)
+        auto pass_over = [&] {
+          B.n_unread.fetch_add(in_range);
+          fblk += in_range;
+          if (fblk == it.nblk) {
+            ++wi;
+            fblk = 0;
+          }
+        };
+        if (examined != wi) {
+          if (!examine_block_file(B, dir_of(it), item, &seen, &cur_len)) {
+            pass_over();
+            continue;
+          }
+          examined = wi;
+        }
+        // the blocks that lie wholly inside the length the packer saw
+        const uint64_t avail = cur_len >= it.size ? it.nblk : cur_len / bs;
+        if (fblk >= avail) {
+          pass_over();
+          continue;
+        }
+        const uint64_t left_blk = std::min<uint64_t>(avail - fblk, in_range);
+        pos = (pos + 15) & ~15ull;
+        if (pos + std::min<uint64_t>(bs, it.size - fblk * bs) > fill) break;
+        uint64_t take = std::min<uint64_t>(left_blk, cap_blk - n);
+        take = std::min<uint64_t>(take, std::max<uint64_t>((fill - pos) / bs, 1));
+        const uint64_t off0 = fblk * bs;
+        const uint64_t bytes = std::min<uint64_t>(take * bs, it.size - off0);
+        if (pos + bytes > fill) break;
+        for (uint64_t j = 0; j < take; ++j) {
+          s.h_off[n + j] = pos + j * bs;
+          s.h_len[n + j] = (uint32_t)std::min<uint64_t>(bs, it.size - off0 - j * bs);
+        }
+        // the entry's digests of these blocks travel up through h_out
+        memcpy(s.h_out + 32 * n, B.idx->entries[it.entry].hashes.data() + 32 * fblk, 32 * take);
+        for (uint64_t piece = 0; piece < bytes; piece += kReadPiece)
+          jobs.push_back({item, seen, cur_len, off0 + piece,
+                          std::min<uint64_t>(kReadPiece, bytes - piece), s.h_data + pos + piece});
+        if (!rs.empty() && rs.back().at + rs.back().count == n &&
+            rs.back().global + rs.back().count == it.first_blk + fblk)
+          rs.back().count += take;  // (neighbouring files, both complete: one run)
+        else
+          rs.push_back({n, it.first_blk + fblk, take});
+        file_bytes += bytes;
+        pos += bytes;
+        used = pos;
+        n += take;
+        fblk += take;
+        if (fblk == it.nblk) {
+          ++wi;
+          fblk = 0;
+        }
+      }
+      fill = std::min(cap, fill * 2);
+      lap(t0, t_pack);
+      if (n > 0) {
+        run_block_reads(B, jobs, threads);
+        lap(t0, t_read);
+        rc = slot_submit_blocks(d, s, std::max<uint64_t>(used, 16), n, B.ht);
+        if (rc) return rc;
+        lap(t0, t_submit);
+        ++n_batches;
+        B.n_bytes.fetch_add(file_bytes);
+        B.n_batches.fetch_add(1);
+      }
+    }
+    k = (k + 1) % kS;
+  }
+  if (trace)
+    fprintf(stderr,
+            "cir check_blocks dev %d: %llu batches; packer's look and run table %.2f ms, "
+            "reads %.2f ms, submit %.2f ms, waiting for results and bit runs %.2f ms\n",
+            d.id, (unsigned long long)n_batches, t_pack, t_read, t_submit, t_wait);
+  return CIR_OK;
+}
+
+int blocks_impl(cir_ctx* ctx, int dirfd, const char* dir, const uint8_t* index, size_t len,
+                uint32_t threads, uint64_t** have_out, uint64_t* nblk_out, uint8_t** state_out,
+                int32_t** errno_out, size_t* nfiles_out, uint64_t* stats) {
+  if (!ctx || !index || !have_out || !nblk_out || !state_out || !nfiles_out || !stats)
+    return fail(CIR_EINVAL, "null pointer");
+  *have_out = nullptr;
+  *nblk_out = 0;
+  *state_out = nullptr;
+  if (errno_out) *errno_out = nullptr;
+  *nfiles_out = 0;
+  for (int i = 0; i < CIR_BLOCKS_STATS_FIELDS; ++i) stats[i] = 0;
+  const auto t_start = std::chrono::steady_clock::now();
+  auto ms_since = [](std::chrono::steady_clock::time_point t) {
+    return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t).count();
+  };
+  dirsig::Index idx;
+  std::string perr;
+  if (!dirsig::parse(index, len, &idx, &perr))
+    return idx.bad_hash_size ? fail(CIR_EHASHSIZE, "hash size is unsupported: " + perr)
+                             : fail(CIR_EPARSE, "error parsing index: " + perr);
+  if (dirsig::digest_len(idx.header.hash) != 32)
+    return fail(CIR_EHASHSIZE, "hash size is unsupported");
+  if (idx.header.block_size > 0xffffffffull)
+    return fail(CIR_EINVAL, "block_size must be in 1 .. 2^32-1");
+  Blocks B;
+  B.idx = &idx;
+  B.bs = idx.header.block_size;
+  B.ht = idx.header.hash == dirsig::HashType::kSha512_256 ? CIR_HASH_SHA512_256
+                                                           : CIR_HASH_BLAKE2B_256;
+  for (size_t e = 0; e < idx.entries.size(); ++e) {
+    const dirsig::Entry& en = idx.entries[e];
+    if (en.kind == dirsig::EntryKind::kDir) {
+      std::vector<std::string> comps;
+      size_t i = 0;
+      while (i < en.path.size()) {
+        size_t j = en.path.find('/', i);
+        if (j == std::string::npos) j = en.path.size();
+        if (j > i) comps.push_back(en.path.substr(i, j - i));
+        i = j + 1;
+      }
+      B.dirs.push_back(std::move(comps));
+    } else if (en.kind == dirsig::EntryKind::kFile) {
+      if (B.dirs.empty()) return fail(CIR_EPARSE, "error parsing index: entry before a directory");
+      Item it;
+      it.entry = e;
+      it.dir = B.dirs.size() - 1;
+      it.name = en.path.substr(en.path.rfind('/') + 1);
+      it.size = en.size;
+      it.nblk = en.hashes.size() / 32;
+      it.first_blk = B.nblk_total;
+      B.nblk_total += it.nblk;
+      if (it.nblk) B.work.push_back(B.items.size());
+      B.items.push_back(std::move(it));
+    }
+  }
+  // ---- nothing above touched a file or a device
+  const double ms_parse = ms_since(t_start);
+  const auto t_empty = std::chrono::steady_clock::now();
+  struct CloseRoot {
+    Blocks& B;
+    bool own = false;
+    ~CloseRoot() {
+      if (own) B.fds.close(B.root);
+    }
+  } close_root{B};
+  if (dir) {
+    B.root = B.fds.took(::openat(dirfd, dir, O_RDONLY | O_DIRECTORY | O_CLOEXEC));
+    if (B.root < 0)
+      return fail(CIR_EIO, std::string("error opening image ") + dir + ": " + strerror(errno));
+    close_root.own = true;
+  } else {
+    struct stat st;
+    if (::fstat(dirfd, &st) != 0 || !S_ISDIR(st.st_mode))
+      return fail(CIR_EIO, "image root fd is not a directory");
+    B.root = dirfd;
+  }
+  const size_t nfiles = B.items.size();
+  const size_t nwords = (size_t)((B.nblk_total + 63) / 64);
+  B.look.assign(nfiles, 0);
+  B.err.assign(nfiles, 0);
+  // the outputs (calloc: every bit starts as "not have")
+  struct Outs {
+    uint64_t* have = nullptr;
+    uint8_t* state = nullptr;
+    int32_t* err = nullptr;
+    ~Outs() {
+      free(have);
+      free(state);
+      free(err);
+    }
+  } outs;
+  if (nwords && !(outs.have = (uint64_t*)calloc(nwords, 8))) return fail(CIR_ENOMEM, "malloc");
+  if (nfiles && !(outs.state = (uint8_t*)calloc(nfiles, 1))) return fail(CIR_ENOMEM, "malloc");
+  if (nfiles && errno_out && !(outs.err = (int32_t*)calloc(nfiles, 4)))
+    return fail(CIR_ENOMEM, "malloc");
+  // the size-0 entries, by the host alone
+  {
+    DirFd cur;
+    size_t cur_dir = SIZE_MAX;
+    for (size_t i = 0; i < nfiles; ++i) {
+      const Item& it = B.items[i];
+      if (it.nblk) continue;
+      if (cur_dir != it.dir) {
+        close_dir_at(B.fds, cur);
+        cur = open_dir_at(B.fds, B.root, B.dirs[it.dir]);
+        cur_dir = it.dir;
+      }
+      examine_block_empty(B, cur, i);
+    }
+    close_dir_at(B.fds, cur);
+  }
+  if (threads == 0) threads = host_copy_threads(ctx->devs.size());
+  const double ms_empty = ms_since(t_empty);
+  const auto t_pipe = std::chrono::steady_clock::now();
+
+  int rc = CIR_OK;
+  const size_t nd = std::min<size_t>(ctx->devs.size(), (size_t)std::max<uint64_t>(B.nblk_total, 1));
+  if (B.nblk_total == 0) {
+    // nothing for a device
+  } else if (nd <= 1) {
+    rc = blocks_range(ctx, *ctx->devs[0], B, threads, {{0, B.nblk_total}}, outs.have);
+  } else {
+    uint64_t stripe = std::max<uint64_t>(1, ctx->staging / B.bs);
+    if (const char* e = getenv("CIR_DEBUG_STRIPE_BLOCKS"))  // tests: stripes of a few blocks
+      if (atoll(e) > 0) stripe = (uint64_t)atoll(e);
+    const StripePrefix sp(B.nblk_total, stripe);
+    std::vector<BlockRanges> dev_ranges(nd);
+    for (size_t st = 0; st < sp.stripes(); ++st)
+      dev_ranges[st % nd].push_back({st * stripe, st * stripe + sp.stripe_len(st)});
+    const unsigned per = std::max(1u, threads / (unsigned)nd);
+    std::vector<int> rcs(nd, 0);
+    std::vector<std::string> es(nd);
+    // a bitmap per device (stripes do not end on word boundaries); device 0
+    // writes into the result itself
+    std::vector<std::vector<uint64_t>> part(nd);
+    for (size_t i = 1; i < nd; ++i) part[i].assign(nwords, 0);
+    fan_out(nd, [&](size_t i) {
+      rcs[i] = blocks_range(ctx, *ctx->devs[i], B, per, dev_ranges[i],
+                            i ? part[i].data() : outs.have);
+      if (rcs[i]) es[i] = cir_last_error();
+    });
+    for (size_t i = 0; i < nd && !rc; ++i)
+      if (rcs[i]) rc = fail(rcs[i], es[i]);
+    for (size_t i = 1; i < nd; ++i)
+      for (size_t w = 0; w < nwords; ++w) outs.have[w] |= part[i][w];
+  }
+  stats[8] = B.fds.peak.load();
+  if (trace_enabled())
+    fprintf(stderr,
+            "cir check_blocks: %zu files, %llu blocks; index parse %.2f ms, root and size-0 "
+            "entries %.2f ms, pipeline %.2f ms\n",
+            nfiles, (unsigned long long)B.nblk_total, ms_parse, ms_empty, ms_since(t_pipe));
+  if (rc) return rc;
+  // the files' states.  A file that is absent or blocked has none of its
+  // blocks: whatever a range packed of it before it went is cleared.
+  for (size_t i = 0; i < nfiles; ++i) {
+    const Item& it = B.items[i];
+    const uint8_t lk = B.look[i];
+    uint8_t st;
+    if (lk & kLookBlocked)
+      st = CIR_FILE_BLOCKED;
+    else if (lk & kLookAbsent)
+      st = CIR_FILE_ABSENT;
+    else if (!(lk & (kLookShort | kLookLong)) &&
+             count_bits(outs.have, it.first_blk, it.nblk) == it.nblk)
+      st = CIR_FILE_COMPLETE;
+    else
+      st = CIR_FILE_PARTIAL;
+    if (st == CIR_FILE_BLOCKED || st == CIR_FILE_ABSENT) {
+      clear_bits(outs.have, it.first_blk, it.nblk);
+    } else if (lk & kLookLong) {
+      st |= CIR_FILE_LONG;
+    }
+    outs.state[i] = st;
+    if (outs.err) outs.err[i] = st == CIR_FILE_BLOCKED ? B.err[i] : 0;
+    ++stats[2 + (st & 3)];
+  }
+  stats[0] = nwords ? count_bits(outs.have, 0, B.nblk_total) : 0;
+  stats[1] = B.nblk_total - stats[0];
+  stats[6] = B.n_bytes.load();
+  stats[7] = B.n_batches.load();
+  stats[9] = B.n_unread.load();
+  *have_out = outs.have;
+  *nblk_out = B.nblk_total;
+  *state_out = outs.state;
+  if (errno_out) *errno_out = outs.err;
+  *nfiles_out = nfiles;
+  outs.have = nullptr;
+  outs.state = nullptr;
+  outs.err = nullptr;
+  return CIR_OK;
+}
+
 }  // namespace
 }  // namespace cir
+
+extern "C" int cir_check_blocks(cir_ctx* ctx, int dirfd, const char* dir, const uint8_t* index,
+                                size_t len, uint32_t threads, uint64_t** have_out,
+                                uint64_t* nblk_out, uint8_t** state_out, int32_t** errno_out,
+                                size_t* nfiles_out, uint64_t stats[CIR_BLOCKS_STATS_FIELDS]) try {
+  return cir::blocks_impl(ctx, dirfd, dir, index, len, threads, have_out, nblk_out, state_out,
+                          errno_out, nfiles_out, stats);
+} CIR_CATCH_BOUNDARY
 
 extern "C" int cir_check_links(cir_ctx* ctx, const uint8_t* index, size_t len,
                                const int* src_dirfd, const char* const* src_dir, size_t nsrc,

@@ -51,7 +51,8 @@ static void usage() {
           "       ciruela-index hash [--block-size N] FILE...\n"
           "       ciruela-index check DIR INDEX_FILE [--disk-threads N]\n"
           "       ciruela-index links INDEX SRCDIR=SRCINDEX [SRCDIR=SRCINDEX ...]"
-          " [--disk-threads N]\n");
+          " [--disk-threads N]\n"
+          "       ciruela-index blocks DIR INDEX_FILE [--list] [--disk-threads N]\n");
 }
 
 static std::string hex(const uint8_t* p, size_t n) {
@@ -166,7 +167,9 @@ static bool read_file(const std::string& path, std::vector<uint8_t>* out) {
 // The paths of an index's file entries, in index order and as the index
 // spells them (escaped): a directory line starts with '/', an entry line with
 // two spaces, and its second field is f or x for a file.
-static std::vector<std::string> index_file_paths(const std::vector<uint8_t>& index) {
+static std::vector<std::string> index_file_paths(const std::vector<uint8_t>& index,
+                                                 std::vector<uint64_t>* sizes = nullptr,
+                                                 uint64_t* block_size = nullptr) {
   std::vector<std::string> out;
   std::string dir;
   size_t pos = 0;
@@ -178,6 +181,9 @@ static std::vector<std::string> index_file_paths(const std::vector<uint8_t>& ind
     pos = e + 1;
     if (header) {
       header = false;
+      const size_t b = line.find(" block_size=");
+      if (block_size && b != std::string::npos)
+        *block_size = strtoull(line.c_str() + b + 12, nullptr, 10);
       continue;
     }
     if (!line.empty() && line[0] == '/') {
@@ -186,8 +192,11 @@ static std::vector<std::string> index_file_paths(const std::vector<uint8_t>& ind
       const size_t sp = line.find(' ', 2);
       if (sp == std::string::npos || sp + 1 >= line.size()) continue;
       if ((line[sp + 1] == 'f' || line[sp + 1] == 'x') &&
-          (sp + 2 == line.size() || line[sp + 2] == ' '))
+          (sp + 2 == line.size() || line[sp + 2] == ' ')) {
         out.push_back((dir == "/" ? "" : dir) + "/" + line.substr(2, sp - 2));
+        if (sizes)
+          sizes->push_back(sp + 3 < line.size() ? strtoull(line.c_str() + sp + 3, nullptr, 10) : 0);
+      }
     }
   }
   return out;
@@ -218,6 +227,7 @@ int main(int argc, char** argv) {
   uint32_t threads = 0;
   uint64_t bs = CIR_DEFAULT_BLOCK_SIZE;
   std::string index_dir;
+  bool list_blocks = false;
   std::vector<Job> jobs;
   std::vector<std::string> files;
   for (int i = 2; i < argc; ++i) {
@@ -247,6 +257,7 @@ int main(int argc, char** argv) {
         bs = n;
     }
     else if (a == "--index-dir") index_dir = val();
+    else if (a == "--list" && cmd == "blocks") list_blocks = true;
     else if (a == "--append" || a == "--append-weak" || a == "--replace") {
       Job j;
       j.kind = a.substr(2);
@@ -255,14 +266,15 @@ int main(int argc, char** argv) {
         return 2;
       }
       jobs.push_back(j);
-    } else if ((cmd == "hash" || cmd == "check" || cmd == "links") && a.size() && a[0] != '-') {
+    } else if ((cmd == "hash" || cmd == "check" || cmd == "links" || cmd == "blocks") && a.size() &&
+               a[0] != '-') {
       files.push_back(a);
     } else {
       usage();
       return 2;
     }
   }
-  if (cmd == "check" && files.size() != 2) {
+  if ((cmd == "check" || cmd == "blocks") && files.size() != 2) {
     usage();
     return 2;
   }
@@ -287,7 +299,7 @@ int main(int argc, char** argv) {
   std::vector<std::string> inputs = cmd == "links" ? link_dirs : files;
   std::vector<uint8_t> check_index;
   if (cmd == "links" && !read_file(files[0], &check_index)) return 2;
-  if (cmd == "check") {
+  if (cmd == "check" || cmd == "blocks") {
     // the index is read (and a missing one reported) before any device is
     // opened; the staging slots are sized from the image alone
     inputs.pop_back();
@@ -394,6 +406,42 @@ int main(int argc, char** argv) {
       fflush(stdout);
       return 1;
     }
+  } else if (cmd == "blocks") {
+    // exit statuses as `check`: 0 when every file is complete, 1 otherwise
+    uint64_t* have = nullptr;
+    uint64_t nblk = 0;
+    uint8_t* state = nullptr;
+    size_t nfiles = 0;
+    uint64_t st[CIR_BLOCKS_STATS_FIELDS];
+    static const uint8_t none = 0;
+    rc = cir_check_blocks(ctx, AT_FDCWD, files[0].c_str(),
+                          check_index.empty() ? &none : check_index.data(), check_index.size(),
+                          threads, &have, &nblk, &state, nullptr, &nfiles, st);
+    if (rc) {
+      die(rc, files[0].c_str());
+      return 2;
+    }
+    printf("blocks: %llu of %llu; files: %llu complete, %llu absent, %llu partial, %llu blocked\n",
+           (unsigned long long)st[0], (unsigned long long)nblk, (unsigned long long)st[2],
+           (unsigned long long)st[3], (unsigned long long)st[4], (unsigned long long)st[5]);
+    if (list_blocks) {
+      std::vector<uint64_t> sizes;
+      uint64_t ibs = 0;
+      const std::vector<std::string> paths = index_file_paths(check_index, &sizes, &ibs);
+      uint64_t g = 0;
+      for (size_t i = 0; i < paths.size() && ibs; ++i) {
+        const uint64_t n = (sizes[i] + ibs - 1) / ibs;
+        for (uint64_t j = 0; j < n && g + j < nblk; ++j)
+          if (!(have[(g + j) >> 6] >> ((g + j) & 63) & 1))
+            printf("%s %llu\n", paths[i].c_str(), (unsigned long long)(j * ibs));
+        g += n;
+      }
+    }
+    fflush(stdout);
+    const bool complete = st[2] == nfiles;
+    cir_free(have);
+    cir_free(state);
+    if (!complete) return 1;
   } else if (cmd == "links") {
     static const uint8_t none = 0;
     const uint8_t* index = check_index.empty() ? &none : check_index.data();

@@ -25,6 +25,8 @@
 //                      image: only the first bad digest's index and a count.
 //   k_seg_bad        : the same compare for the hardlink candidates: one bad
 //                      flag per segment (file) of the batch.
+//   k_block_bits     : the same compare for the resume of a partial image:
+//                      one bit per digest, one 64-bit word per wave.
 //   k_compress_only  : register-only compressions (live VALU ceiling).
 //   k_fill_splitmix64: synthetic test data (bench / tests only).
 //
@@ -1196,6 +1198,58 @@ hipError_t launch_seg_bad(const uint8_t* got, const uint8_t* want, uint64_t n,
   if (e != hipSuccess || !nbad_seg) return e;
   hipLaunchKernelGGL(k_seg_count, dim3(grid_for(nseg, kThreads)), dim3(kThreads), 0, s, seg_bad,
                      nseg, nbad_seg);
+  return hipGetLastError();
+}
+
+// Resume of a partial image (the daemon's "Resuming download",
+// src/daemon/tracking/mod.rs:561-585, which today fetches every block again):
+// which digests match, as one bit per digest.  The compare is k_first_bad's;
+// a wave's 64 verdicts are one ballot, and lane 0 stores it to have[b >> 6] --
+// kThreads is a multiple of the wave size, so a wave's first index is a
+// multiple of 64 and every wave owns exactly one aligned word.  A wave whose
+// first index is >= n stores nothing, so nothing past word ceil(n/64) - 1 is
+// written; lanes at or past n vote 0, so the last word's tail bits are 0; and
+// every word of [0, ceil(n/64)) is stored by its wave, so nothing needs
+// initialising and no atomic touches the bitmap.  *nbad (nullable, zeroed by
+// k_count_init on the same stream) receives one atomicAdd per wave that has a
+// valid lane that is not ok.
+__global__ void k_count_init(uint32_t* __restrict__ nbad) {
+  if (threadIdx.x == 0) *nbad = 0;
+}
+
+__global__ void k_block_bits(const uint8_t* __restrict__ got, const uint8_t* __restrict__ want,
+                             uint64_t n, unsigned long long* __restrict__ have,
+                             uint32_t* __restrict__ nbad, const uint8_t* __restrict__ flag) {
+  const uint64_t b = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  bool ok = false;
+  if (b < n) {
+    const uint4* g = reinterpret_cast<const uint4*>(got + 32 * b);
+    const uint4* w = reinterpret_cast<const uint4*>(want + 32 * b);
+    const uint4 g0 = g[0], g1 = g[1], w0 = w[0], w1 = w[1];
+    const uint32_t diff = (g0.x ^ w0.x) | (g0.y ^ w0.y) | (g0.z ^ w0.z) | (g0.w ^ w0.w) |
+                          (g1.x ^ w1.x) | (g1.y ^ w1.y) | (g1.z ^ w1.z) | (g1.w ^ w1.w);
+    ok = diff == 0 && !(flag && flag[b]);
+  }
+  const uint64_t mask = __ballot(ok);
+  const uint64_t miss = __ballot(b < n && !ok);
+  // (lane 0's b is the wave's first index, a multiple of 64)
+  if ((threadIdx.x & 63) == 0 && b < n) {
+    have[b >> 6] = mask;
+    if (nbad && miss) atomicAdd(nbad, (uint32_t)__popcll(miss));
+  }
+}
+
+hipError_t launch_block_bits(const uint8_t* got, const uint8_t* want, uint64_t n, uint64_t* have,
+                             uint32_t* nbad, hipStream_t s, const uint8_t* flag) {
+  static_assert(kThreads % 64 == 0, "whole waves per workgroup: a wave owns one aligned word");
+  hipError_t e = hipSuccess;
+  if (nbad) {
+    hipLaunchKernelGGL(k_count_init, dim3(1), dim3(64), 0, s, nbad);
+    e = hipGetLastError();
+  }
+  if (e != hipSuccess || n == 0) return e;
+  hipLaunchKernelGGL(k_block_bits, dim3(grid_for(n, kThreads)), dim3(kThreads), 0, s, got, want, n,
+                     reinterpret_cast<unsigned long long*>(have), nbad, flag);
   return hipGetLastError();
 }
 

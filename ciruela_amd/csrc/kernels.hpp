@@ -159,6 +159,15 @@ hipError_t launch_seg_bad(const uint8_t* got, const uint8_t* want, uint64_t n,
                           const uint32_t* seg_end, uint64_t nseg, uint8_t* seg_bad,
                           uint32_t* nbad_seg, hipStream_t s, const uint8_t* flag = nullptr);
 
+// The same compare as a bitmap: bit (b & 63) of have[b >> 6] (device u64s,
+// 8-B aligned) = 1 when digest b equals the expected one and its flag is not
+// set.  Every word of [0, ceil(n/64)) is stored here (the last word's bits at
+// positions >= n as 0) and nothing past them; n == 0 stores no word.  *nbad
+// (device u32, nullable) = how many of the n are not ok, initialised here on
+// the same stream (also when n == 0).
+hipError_t launch_block_bits(const uint8_t* got, const uint8_t* want, uint64_t n, uint64_t* have,
+                             uint32_t* nbad, hipStream_t s, const uint8_t* flag = nullptr);
+
 // nlanes x `lines` register-only compressions (diagnostic VALU ceiling).
 hipError_t launch_compress_only(uint64_t nlanes, uint32_t lines, uint8_t* out, hipStream_t s);
 

@@ -82,6 +82,8 @@ Device::~Device() {
     (void)hipFree(s.d_seg_end);
     (void)hipHostFree(s.h_seg_res);
     (void)hipFree(s.d_seg_res);
+    (void)hipHostFree(s.h_bits);
+    (void)hipFree(s.d_bits);
     if (s.copied) (void)hipEventDestroy(s.copied);
     if (s.done) (void)hipEventDestroy(s.done);
     for (hipEvent_t e : {s.t_copy0, s.t_copy1, s.t_hash0, s.t_done})
@@ -357,6 +359,22 @@ int Device::ensure_links(Slot& s) {
   return CIR_OK;
 }
 
+int Device::ensure_blocks(Slot& s) {
+  int rc = ensure_check(s);
+  if (rc) return rc;
+  if (s.bits_cap < s.cap_blk) {
+    (void)hipHostFree(s.h_bits);
+    (void)hipFree(s.d_bits);
+    s.h_bits = s.d_bits = nullptr;
+    s.bits_cap = 0;
+    const size_t bytes = kBitsResHead + 8 * ((s.cap_blk + 63) / 64);
+    CIR_HIP(hipHostMalloc((void**)&s.h_bits, bytes, hipHostMallocDefault));
+    CIR_HIP(hipMalloc((void**)&s.d_bits, bytes));
+    s.bits_cap = s.cap_blk;
+  }
+  return CIR_OK;
+}
+
 int Device::ensure_timing(Slot& s) {
   for (hipEvent_t* e : {&s.t_copy0, &s.t_copy1, &s.t_hash0, &s.t_done})
     if (!*e) CIR_HIP(hipEventCreate(e));
@@ -486,7 +504,7 @@ int hash_desc_ordered(Device& d, const uint8_t* arena, const uint64_t* off, cons
 // bytes of one file split into chunk_bs blocks (nblk = ceil(bytes / bs)).
 static int slot_submit_impl(Device& d, Slot& s, uint64_t bytes, uint64_t nblk,
                             uint64_t chunk_bs, int ht, const uint64_t* check_base = nullptr,
-                            uint64_t nseg = 0) {
+                            uint64_t nseg = 0, bool bits = false) {
   s.timed = d.record_times || trace_enabled();
   if (s.timed) {
     int rc = d.ensure_timing(s);
@@ -499,7 +517,7 @@ static int slot_submit_impl(Device& d, Slot& s, uint64_t bytes, uint64_t nblk,
     CIR_HIP(hipMemcpyAsync(s.d_off, s.h_off, nblk * 8, hipMemcpyHostToDevice, d.copy));
     CIR_HIP(hipMemcpyAsync(s.d_len, s.h_len, nblk * 4, hipMemcpyHostToDevice, d.copy));
   }
-  if (check_base || nseg)
+  if (check_base || nseg || bits)
     CIR_HIP(hipMemcpyAsync(s.d_want, s.h_out, nblk * 32, hipMemcpyHostToDevice, d.copy));
   if (nseg)
     CIR_HIP(hipMemcpyAsync(s.d_seg_end, s.h_seg_end, nseg * 4, hipMemcpyHostToDevice, d.copy));
@@ -522,6 +540,12 @@ static int slot_submit_impl(Device& d, Slot& s, uint64_t bytes, uint64_t nblk,
                                 reinterpret_cast<uint32_t*>(s.d_seg_res), d.compute));
     CIR_HIP(hipMemcpyAsync(s.h_seg_res, s.d_seg_res, kSegResHead + nseg, hipMemcpyDeviceToHost,
                            d.compute));
+  } else if (bits) {
+    CIR_HIP(dev::launch_block_bits(s.d_out, s.d_want, nblk,
+                                   reinterpret_cast<uint64_t*>(s.d_bits + kBitsResHead),
+                                   reinterpret_cast<uint32_t*>(s.d_bits), d.compute));
+    CIR_HIP(hipMemcpyAsync(s.h_bits, s.d_bits, kBitsResHead + 8 * ((nblk + 63) / 64),
+                           hipMemcpyDeviceToHost, d.compute));
   } else {
     CIR_HIP(hipMemcpyAsync(s.h_out, s.d_out, nblk * 32, hipMemcpyDeviceToHost, d.compute));
   }
@@ -546,6 +570,12 @@ int slot_submit_links(Device& d, Slot& s, uint64_t bytes, uint64_t nblk, int ht,
   if (!s.d_seg_res || !s.h_seg_res || s.want_blk < nblk || s.seg_cap < nseg || nseg == 0)
     return fail(CIR_EINVAL, "links-mode submit without ensure_links");
   return slot_submit_impl(d, s, bytes, nblk, 0, ht, nullptr, nseg);
+}
+
+int slot_submit_blocks(Device& d, Slot& s, uint64_t bytes, uint64_t nblk, int ht) {
+  if (!s.d_bits || !s.h_bits || s.want_blk < nblk || s.bits_cap < nblk || nblk == 0)
+    return fail(CIR_EINVAL, "blocks-mode submit without ensure_blocks");
+  return slot_submit_impl(d, s, bytes, nblk, 0, ht, nullptr, 0, true);
 }
 
 int slot_wait(Device& d, Slot& s) {
@@ -1177,7 +1207,7 @@ static int bounded_run(cir_ctx* ctx, Device* d, int ht, const uint8_t* arena,
                        uint64_t arena_bytes, const uint64_t* off, const uint32_t* len, size_t n,
                        uint8_t* out, uint32_t* nrange, const uint8_t* expected, uint8_t* ok,
                        uint32_t* nbad, void* scratch, hipStream_t s, uint64_t* first = nullptr,
-                       const SegTable* seg = nullptr) {
+                       const SegTable* seg = nullptr, uint64_t* have = nullptr) {
   uint32_t* slen = nullptr;
   uint8_t* flag = nullptr;
   CIR_HIP(dev::launch_desc_bound(off, len, n, arena_bytes, scratch, nrange, &slen, &flag, s));
@@ -1190,7 +1220,9 @@ static int bounded_run(cir_ctx* ctx, Device* d, int ht, const uint8_t* arena,
     CIR_HIP(dev::launch_general_desc(arena, off, slen, nullptr, n, out, s));
   }
   CIR_HIP(dev::launch_desc_zero(flag, n, out, s));
-  if (expected && seg)
+  if (expected && have)
+    CIR_HIP(dev::launch_block_bits(out, expected, n, have, nbad, s, flag));
+  else if (expected && seg)
     CIR_HIP(dev::launch_seg_bad(out, expected, n, seg->end, seg->nseg, seg->bad, nbad, s, flag));
   else if (expected && first)
     CIR_HIP(dev::launch_first_bad(out, expected, n, 0, first, nbad, s, flag));
@@ -1203,7 +1235,8 @@ static int hash_desc_bounded(cir_ctx* ctx, int ht, const void* d_arena, uint64_t
                              const uint64_t* d_off, const uint32_t* d_len, size_t n,
                              uint8_t* d_out, uint32_t* d_nrange, const uint8_t* d_expected,
                              uint8_t* d_ok, uint32_t* d_nbad, hipStream_t s,
-                             uint64_t* d_first = nullptr, const SegTable* seg = nullptr) {
+                             uint64_t* d_first = nullptr, const SegTable* seg = nullptr,
+                             uint64_t* d_have = nullptr) {
   if (!valid_hash_type(ht)) return fail(CIR_EINVAL, "unknown hash type");
   if (n && (!d_off || !d_len || !d_out)) return fail(CIR_EINVAL, "null device pointer");
   // (d_arena may be NULL with arena_bytes == 0: every non-empty block is then
@@ -1218,12 +1251,13 @@ static int hash_desc_bounded(cir_ctx* ctx, int ht, const void* d_arena, uint64_t
     if (!d) return fail(CIR_EINVAL, "stream device is not part of the context");
   }
   // (with d_first the compare's launcher initialises both result cells)
-  if (d_nbad && !d_first && !seg) CIR_HIP(hipMemsetAsync(d_nbad, 0, 4, s));
+  if (d_nbad && !d_first && !seg && !d_have) CIR_HIP(hipMemsetAsync(d_nbad, 0, 4, s));
   if (n == 0) {
     if (d_nrange) CIR_HIP(hipMemsetAsync(d_nrange, 0, 4, s));
     if (d_first) CIR_HIP(dev::launch_first_bad(nullptr, nullptr, 0, 0, d_first, d_nbad, s));
     if (seg)
       CIR_HIP(dev::launch_seg_bad(nullptr, nullptr, 0, seg->end, seg->nseg, seg->bad, d_nbad, s));
+    if (d_have) CIR_HIP(dev::launch_block_bits(nullptr, nullptr, 0, d_have, d_nbad, s));
     return CIR_OK;
   }
   const uint8_t* arena = static_cast<const uint8_t*>(d_arena);
@@ -1232,7 +1266,7 @@ static int hash_desc_bounded(cir_ctx* ctx, int ht, const void* d_arena, uint64_t
     void* scratch = nullptr;
     CIR_HIP(hipMallocAsync(&scratch, need, s));
     const int rc = bounded_run(ctx, d, ht, arena, arena_bytes, d_off, d_len, n, d_out, d_nrange,
-                               d_expected, d_ok, d_nbad, scratch, s, d_first, seg);
+                               d_expected, d_ok, d_nbad, scratch, s, d_first, seg, d_have);
     const hipError_t e = hipFreeAsync(scratch, s);
     if (rc) return rc;
     CIR_HIP(e);
@@ -1254,7 +1288,8 @@ static int hash_desc_bounded(cir_ctx* ctx, int ht, const void* d_arena, uint64_t
   }
   CIR_HIP(hipStreamWaitEvent(s, d->bound_free, 0));
   const int rc = bounded_run(ctx, d, ht, arena, arena_bytes, d_off, d_len, n, d_out, d_nrange,
-                             d_expected, d_ok, d_nbad, d->bound_scratch, s, d_first, seg);
+                             d_expected, d_ok, d_nbad, d->bound_scratch, s, d_first, seg,
+                             d_have);
   // recorded on every path: whatever of the batch was queued is ordered
   // before the scratch's next user
   const hipError_t e = hipEventRecord(d->bound_free, s);
@@ -1328,6 +1363,27 @@ int cir_verify_segments_dev(cir_ctx* ctx, int hash_type, const void* d_arena, ui
   if (rc) return rc;
   CIR_HIP(dev::launch_seg_bad(d_digests, d_expected, nblk, d_seg_end, nseg, d_seg_bad, d_nbad_seg,
                               s));
+  return CIR_OK;
+} CIR_CATCH_BOUNDARY
+
+int cir_verify_bitmap_dev(cir_ctx* ctx, int hash_type, const void* d_arena, uint64_t arena_bytes,
+                          const uint64_t* d_off, const uint32_t* d_len, size_t nblk,
+                          const uint8_t* d_expected, uint8_t* d_digests, uint64_t* d_have,
+                          uint32_t* d_nbad, void* stream) try {
+  if (!d_have || (nblk && (!d_expected || !d_digests)))
+    return fail(CIR_EINVAL, "null device pointer");
+  if ((reinterpret_cast<uintptr_t>(d_expected) | reinterpret_cast<uintptr_t>(d_digests)) & 15u)
+    return fail(CIR_EINVAL, "digest arrays must be 16-byte aligned");
+  if ((reinterpret_cast<uintptr_t>(d_have) & 7u) || (reinterpret_cast<uintptr_t>(d_nbad) & 3u))
+    return fail(CIR_EINVAL, "bitmap and count must be naturally aligned");
+  hipStream_t s = (hipStream_t)stream;
+  if (arena_bytes != UINT64_MAX || nblk == 0)
+    return hash_desc_bounded(ctx, hash_type, d_arena, arena_bytes, d_off, d_len, nblk, d_digests,
+                             nullptr, d_expected, nullptr, d_nbad, s, nullptr, nullptr, d_have);
+  // trusted descriptors: no bounds pass, cir_verify_blocks_dev's batch
+  int rc = cir_hash_blocks_dev_ht(ctx, hash_type, d_arena, d_off, d_len, nblk, d_digests, stream);
+  if (rc) return rc;
+  CIR_HIP(dev::launch_block_bits(d_digests, d_expected, nblk, d_have, d_nbad, s));
   return CIR_OK;
 } CIR_CATCH_BOUNDARY
 

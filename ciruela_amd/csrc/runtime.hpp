@@ -89,6 +89,12 @@ struct Slot {
   uint8_t* h_seg_res = nullptr;
   uint8_t* d_seg_res = nullptr;
   uint64_t seg_cap = 0;
+  // blocks mode (cir_check_blocks): the result {u32 blocks not ok, 12 B of
+  // padding, one bit per block of the batch in u64 words} with its pinned
+  // host twin; room for bits_cap blocks, allocated on the first blocks check
+  uint8_t* h_bits = nullptr;
+  uint8_t* d_bits = nullptr;
+  uint64_t bits_cap = 0;
   hipEvent_t copied = nullptr;  // H2D of this slot finished (copy stream)
   hipEvent_t done = nullptr;    // digests of this slot are back in h_out
   // timing events (created on first use, recorded only while the device's
@@ -216,6 +222,7 @@ struct Device {
   int ensure_timing(Slot& s);
   int ensure_check(Slot& s);  // the check-mode buffers, sized to s.cap_blk
   int ensure_links(Slot& s);  // those and the links-mode buffers, sized to s.cap_blk
+  int ensure_blocks(Slot& s);  // the check-mode and the blocks-mode buffers, sized to s.cap_blk
 };
 
 // Every slot a staged loop submitted is waited for before the loop lets go
@@ -254,6 +261,13 @@ int slot_submit_check(Device& d, Slot& s, uint64_t bytes, uint64_t nblk, int ht,
 // number of bad segments and s.h_seg_res[16 + k] = 1 when segment k is bad.
 constexpr uint64_t kSegResHead = 16;
 int slot_submit_links(Device& d, Slot& s, uint64_t bytes, uint64_t nblk, int ht, uint64_t nseg);
+// Blocks mode: as check mode, but every block gets a verdict: the compare is
+// launch_block_bits and 16 + 8 * ceil(nblk / 64) bytes come back: after
+// slot_wait, the u32 at s.h_bits = the number of blocks that are not ok and
+// bit (b & 63) of the u64 at s.h_bits + 16 + 8 * (b >> 6) = 1 when block b of
+// the batch matches (the last word's bits at and past nblk are 0).
+constexpr uint64_t kBitsResHead = 16;
+int slot_submit_blocks(Device& d, Slot& s, uint64_t bytes, uint64_t nblk, int ht);
 int hash_desc_ordered(Device& d, const uint8_t* arena, const uint64_t* off, const uint32_t* len,
                       uint64_t n, uint8_t* out, hipStream_t s, int ht = CIR_HASH_BLAKE2B_256,
                       bool warm_only = false);

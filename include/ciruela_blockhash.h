@@ -283,6 +283,21 @@ int cir_verify_segments_dev(cir_ctx* ctx, int hash_type, const void* d_arena, ui
                             const uint32_t* d_seg_end, size_t nseg,
                             uint8_t* d_seg_bad, uint32_t* d_nbad_seg, void* stream);
 
+/* cir_verify_first_dev with one bit per block instead of "which block first": the compare
+ * behind cir_check_blocks.  Bit (b & 63) of d_have[b >> 6] (device u64 x ceil(nblk / 64),
+ * 8-byte aligned, never NULL) = 1 when block b hashes to d_expected[32 b ..) and is in range
+ * (arena_bytes = UINT64_MAX: trusted descriptors); an out-of-range block is never read and its
+ * bit is 0.  Every word of [0, ceil(nblk / 64)) is written on `stream` by the call itself, the
+ * bits of the last word at positions >= nblk as 0, and nothing past that word is written; the
+ * caller initialises nothing and no atomic touches the bitmap.  *d_nbad (device u32, may be
+ * NULL) = the number of blocks whose bit is 0, written by the call (nblk == 0 writes only
+ * *d_nbad = 0).  CIR_EINVAL: a NULL or misaligned d_have and the alignment and argument cases
+ * of cir_verify_first_dev. */
+int cir_verify_bitmap_dev(cir_ctx* ctx, int hash_type, const void* d_arena, uint64_t arena_bytes,
+                          const uint64_t* d_off, const uint32_t* d_len, size_t nblk,
+                          const uint8_t* d_expected, uint8_t* d_digests, uint64_t* d_have,
+                          uint32_t* d_nbad, void* stream);
+
 /* Host-memory batch of the same check; ok_out (nblk bytes) may be NULL. */
 int cir_verify_blocks(cir_ctx* ctx, int hash_type, const uint8_t* h_arena, const uint64_t* off,
                       const uint32_t* len, size_t nblk, const uint8_t* expected, uint8_t* ok_out,
@@ -446,6 +461,71 @@ int cir_check_links(cir_ctx* ctx, const uint8_t* index, size_t len,
                     const uint64_t* link_file, const uint32_t* link_src, size_t nlinks,
                     uint32_t threads, uint8_t* kind_out, int32_t* errno_out,
                     uint64_t stats[CIR_LINKS_STATS_FIELDS]);
+
+/* Which blocks of an index a partial image directory already holds, for resume and repair.
+ * The reference resumes by starting over: "Resuming download" (src/daemon/tracking/mod.rs:
+ * 561-585) goes through start_image, which removes the partial .tmp directory
+ * (src/daemon/disk/public.rs:91-93), and fill_blocks queues every block of every file again
+ * (src/daemon/tracking/progress.rs:129-170).  Here the directory stays and the caller queues
+ * only the blocks whose bit is 0.
+ *
+ * Root, hash type, block size and threads as in cir_check_index.  Blocks are numbered globally
+ * in index order over the file entries (the numbering of cir_check_index's stats[7]), files by
+ * file ordinal as in cir_link_candidates.  *have_out: one bit per block (bit (g & 63) of word
+ * g >> 6; ceil(*nblk_out / 64) words); *state_out: one cir_file_state per file entry
+ * (*nfiles_out of them), with CIR_FILE_LONG or'ed in; *errno_out (errno_out may be NULL): the
+ * errno of a BLOCKED file, else 0.  All malloc'd (cir_free), NULL when their count is 0.
+ *
+ * Bit g is 1 exactly when the entry's path -- every directory component opened with
+ * openat(O_DIRECTORY | O_NOFOLLOW) below the root, the file with openat(O_NOFOLLOW) -- is a
+ * regular file, block j's bytes [j bs, min((j + 1) bs, size)) lie wholly inside the file's
+ * current length, and their digest is the index's.  A block that reaches past EOF is not read;
+ * a hole reads as zeros and is judged like any other bytes.
+ *
+ *   CIR_FILE_ABSENT    ENOENT on the file or on a directory component.
+ *   CIR_FILE_BLOCKED   anything else keeps the file from being opened, something that is not a
+ *                      regular file is in its place, a read fails, or the file changes
+ *                      identity (st_dev, st_ino) or shrinks (ESTALE / ENODATA) between the
+ *                      packer's look and the read.  None of the file's bits is set (the caller
+ *                      removes the object and fetches the whole file); other files are
+ *                      unaffected.
+ *   CIR_FILE_COMPLETE  every block has its bit and the length is the entry's.
+ *   CIR_FILE_PARTIAL   otherwise.
+ *   CIR_FILE_LONG      or'ed into PARTIAL when the file is longer than the entry: the caller
+ *                      truncates it before commit; its blocks up to the entry's size are
+ *                      judged all the same (all of them may have their bits).
+ * A size-0 entry is judged by the host alone: COMPLETE when an empty regular file is there,
+ * ABSENT when nothing is, PARTIAL | LONG when it is regular and not empty, else BLOCKED.  Mode
+ * bits are not examined (commit sets them).  cir_check_index gives CIR_CHECK_OK on the same
+ * directory exactly when every non-empty file is COMPLETE and every size-0 file COMPLETE or
+ * ABSENT.
+ *
+ * The pipeline is cir_check_links': the blocks inside each file's length are packed into the
+ * staging slots, hashed, compared by cir_verify_bitmap_dev's kernel, and 16 + 8 ceil(n / 64)
+ * bytes come back per batch of n blocks.  Read-only: nothing is created, truncated or
+ * chmod'ed.  File descriptors held at once: the root, one directory and one file per packer
+ * and per reader thread.  Several devices take stripes of the global block order; every block
+ * has one owner, so the result does not depend on timing.
+ *
+ * Returns CIR_OK whenever every block and file got a verdict.  CIR_EINVAL / CIR_EPARSE /
+ * CIR_EHASHSIZE (before any I/O) as cir_check_index; CIR_EIO only when the root cannot be
+ * opened.
+ *
+ * stats: [0] blocks have, [1] blocks not have, [2] files COMPLETE, [3] ABSENT, [4] PARTIAL,
+ * [5] BLOCKED, [6] bytes read, [7] batches, [8] peak of the file descriptors held at once,
+ * [9] blocks not read because the file is absent or blocked or the block lies past EOF. */
+enum cir_file_state {
+  CIR_FILE_COMPLETE = 0,
+  CIR_FILE_ABSENT = 1,
+  CIR_FILE_PARTIAL = 2,
+  CIR_FILE_BLOCKED = 3
+};
+#define CIR_FILE_LONG 0x80 /* or'ed in: on-disk length exceeds the entry's */
+#define CIR_BLOCKS_STATS_FIELDS 10
+int cir_check_blocks(cir_ctx* ctx, int dirfd, const char* dir, const uint8_t* index, size_t len,
+                     uint32_t threads, uint64_t** have_out, uint64_t* nblk_out,
+                     uint8_t** state_out, int32_t** errno_out, size_t* nfiles_out,
+                     uint64_t stats[CIR_BLOCKS_STATS_FIELDS]);
 
 /* ---- index (DIRSIGNATURE.v1) ----------------------------------------- */
 

@@ -11,7 +11,8 @@
 // sizes up to 2^32-1 (a file that grows, CIR_DEBUG_GROW), the asynchronous
 // verify with forgets, the device-resident entry points on a stream of the
 // caller's, scans returned whole and written out as they go,
-// the rewrite, and the registries; every fifth round four more threads call
+// the rewrite, the registries, and cir_check_blocks over the scanned tree
+// (complete, then with one file a byte short and one gone); every fifth round four more threads call
 // into the same context at once.  Any memory error or undefined behaviour
 // ends the run with the sanitizer's report.  The same source builds under
 // ThreadSanitizer (make build/host_tsan_driver; tools/tsan_hip.supp drops
@@ -290,6 +291,7 @@ static void scan(cir_ctx* ctx, int ht, const std::string& dir, int round) {
   const std::string root = dir + "/tree" + std::to_string(round);
   const uint64_t bs = pick({128, 4096, 32768, 65539, (1 << 20) + 5});
   std::vector<std::string> files;
+  std::vector<size_t> sizes;
   bool empty_dir = false;
   mkdir(root.c_str(), 0755);
   for (int d = 0; d < 4; ++d) {
@@ -305,6 +307,7 @@ static void scan(cir_ctx* ctx, int ht, const std::string& dir, int round) {
       CHECK(f && fwrite(b.data(), 1, b.size(), f) == b.size());
       fclose(f);
       files.push_back(p);
+      sizes.push_back(b.size());
     }
   }
   const char* dirs[1] = {root.c_str()};
@@ -373,6 +376,51 @@ static void scan(cir_ctx* ctx, int ht, const std::string& dir, int round) {
   CHECK(cir_blocks_register_memory_ht(ctx, mb, ht, mem.data(), mem.size(), bs) == 0);
   CHECK(cir_blocks_len(mb) <= (mem.size() + bs - 1) / bs);
   cir_blocks_free(mb);
+  // which blocks the tree holds (cir_check_blocks): all of them; then, with
+  // one file a byte short and one gone, all but those files' (last: it
+  // changes the tree)
+  uint64_t nblk = 0;
+  for (size_t n : sizes) nblk += (n + bs - 1) / bs;
+  size_t cut = files.size(), gone = files.size();
+  for (size_t i = 0; i < files.size(); ++i) {
+    if (sizes[i] > 0 && cut == files.size())
+      cut = i;
+    else if (sizes[i] > 0 && gone == files.size())
+      gone = i;
+  }
+  for (int pass = 0; pass < 2; ++pass) {
+    uint64_t lost = 0;
+    if (pass == 1) {
+      if (cut < files.size()) {
+        CHECK(truncate(files[cut].c_str(), (off_t)sizes[cut] - 1) == 0);
+        lost += 1;
+      }
+      if (gone < files.size()) {
+        CHECK(unlink(files[gone].c_str()) == 0);
+        lost += (sizes[gone] + bs - 1) / bs;
+      }
+    }
+    uint64_t* have = nullptr;
+    uint64_t got_blk = 0;
+    uint8_t* state = nullptr;
+    int32_t* errs = nullptr;
+    size_t nfiles = 0;
+    uint64_t st[CIR_BLOCKS_STATS_FIELDS];
+    CHECK(cir_check_blocks(ctx, AT_FDCWD, root.c_str(), index, len, threads, &have, &got_blk,
+                           &state, pass ? &errs : nullptr, &nfiles, st) == 0);
+    CHECK(got_blk == nblk && nfiles == files.size());
+    CHECK(st[0] == nblk - lost && st[1] == lost && st[5] == 0);
+    CHECK(st[3] == (pass && gone < files.size() ? 1u : 0u));
+    CHECK(st[4] == (pass && cut < files.size() ? 1u : 0u));
+    uint64_t ones = 0;
+    for (uint64_t g = 0; g < got_blk; ++g) ones += have[g >> 6] >> (g & 63) & 1;
+    CHECK(ones == st[0]);
+    if (got_blk % 64) CHECK(have[got_blk >> 6] >> (got_blk % 64) == 0);  // the tail bits
+    for (size_t i = 0; i < nfiles; ++i) CHECK(!errs || errs[i] == 0);
+    cir_free(have);
+    cir_free(state);
+    cir_free(errs);
+  }
   cir_free(index);
 }
 
