@@ -18,9 +18,9 @@ OBJDIR := build/obj
 LIB := ciruela_amd/libciruela_amd.so
 CLI := bin/ciruela-index
 
-SRCS_HIP := $(CSRC)/kernels.hip $(CSRC)/order.hip
+SRCS_HIP := $(CSRC)/kernels.hip $(CSRC)/order.hip $(CSRC)/join.hip
 SRCS_CPP := $(CSRC)/runtime.cpp $(CSRC)/dirsig.cpp $(CSRC)/scan.cpp $(CSRC)/check.cpp \
-            $(CSRC)/links.cpp $(CSRC)/registry.cpp \
+            $(CSRC)/links.cpp $(CSRC)/sources.cpp $(CSRC)/registry.cpp \
             $(CSRC)/blake2b_host.cpp $(CSRC)/sha512_host.cpp
 OBJS := $(patsubst $(CSRC)/%.hip,$(OBJDIR)/%.o,$(SRCS_HIP)) \
         $(patsubst $(CSRC)/%.cpp,$(OBJDIR)/%.o,$(SRCS_CPP))

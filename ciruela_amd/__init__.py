@@ -41,6 +41,13 @@ Context.check_blocks,           what "Resuming download" lacks: which blocks a p
                                 src/daemon/disk/public.rs:91-93,
                                 src/daemon/tracking/progress.rs:129-170)
 Context.verify_bitmap_dev       the same compare on the device, one bit per block
+block_sources                   what fill_blocks lacks: which of the blocks it queues an
+                                older local image already holds, and where
+                                (src/daemon/tracking/progress.rs:129-170; scan_links
+                                matches whole files only, src/daemon/metadata/
+                                hardlink_sources.rs:131-133)
+Context.match_digests_dev       the join behind it on the device: per needed digest the
+                                smallest ordinal of an equal digest in a pool
 =============================  ==============================================
 
 All hashing runs on gfx950 through the library; there is no CPU fallback.
@@ -57,7 +64,7 @@ __all__ = [
     "InMemoryIndexes", "ThreadedBlockReader", "BlockHint", "Context", "default_context",
     "IndexError_", "DirError", "ReadError", "CiruelaError", "NoDevice", "sha512_256",
     "check_index", "CheckResult", "link_candidates", "check_links", "LinksResult",
-    "check_blocks", "BlocksResult",
+    "check_blocks", "BlocksResult", "block_sources", "SourcesResult",
 ]
 
 DEFAULT_BLOCK_SIZE = 32768
@@ -284,6 +291,23 @@ class Context:
         ht = (hash_type or HashType.blake2b_256()).code
         _n.check(_n.lib.cir_verify_bitmap_dev(self._h, ht, d_arena, arena_bytes, d_off, d_len,
                                               nblk, d_expected, d_digests, d_have, d_nbad, stream))
+
+    @staticmethod
+    def match_table_slots(n_pool):
+        """cir_match_table_slots: the u32 slots match_digests_dev's table needs."""
+        return _n.lib.cir_match_table_slots(n_pool)
+
+    def match_digests_dev(self, d_need, n_need, d_pool, n_pool, d_table, table_slots, seed,
+                          d_match, d_nmatch=0, stream=0):
+        """The join behind block_sources on device-resident digests:
+        d_match[i] (device u32) = the smallest j < n_pool with pool[j] ==
+        need[i] over all 32 bytes, or 2^32-1; *d_nmatch (device u32, optional)
+        = how many matched.  d_table: table_slots u32 of scratch (a power of
+        two >= match_table_slots(n_pool)) that the call initialises; a caller
+        that joins untrusted digests passes an unpredictable seed.  All
+        written by the call, on `stream` alone."""
+        _n.check(_n.lib.cir_match_digests_dev(self._h, d_need, n_need, d_pool, n_pool, d_table,
+                                              table_slots, seed, d_match, d_nmatch, stream))
 
     # ---- asynchronous per-block verify (FetchBlock::poll, fetch_blocks.rs:77)
     def verify_submit(self, data, expected, hash_type=None):
@@ -678,6 +702,140 @@ class BlocksResult:
         return "BlocksResult(%d of %d blocks; %s)" % (
             self.stats["have"], self.nblk,
             ", ".join("%d %s" % (self.states.count(s), s) for s in self.STATES.values()))
+
+
+class SourcesResult:
+    """Answer of block_sources.  nblk: the index's blocks, numbered in index
+    order over its file entries; per block g: src[g] the source ordinal (None
+    when no local copy is known or the block was not wanted), file[g] the file
+    ordinal inside that source's index, block[g] the block number inside that
+    file.  found: how many blocks have a source; bytes_local: their bytes.
+    copies(): (dst_path, dst_offset, length, src, src_path, src_offset) per
+    found block in index order, paths as raw bytes -- what a caller copies
+    instead of what fill_blocks would queue (src/daemon/tracking/progress.rs:
+    136-151).  want_after(): the bitmap (as BlocksResult.have is laid out) of
+    the wanted blocks that were not found."""
+
+    __slots__ = ("nblk", "src", "file", "block", "stats", "skipped", "_index", "_sources", "_want")
+    STATS_FIELDS = ("wanted", "found", "bytes_local", "pool_blocks", "sources_used",
+                    "dropped_length", "table_slots", "on_device")
+
+    def __init__(self, index, sources, nblk, src, file, block, stats, skipped=0, want=None):
+        self._index = index      # (split into lines only when copies() is asked for)
+        self._sources = sources
+        self._want = want        # bytes of the want bitmap, or None = every block
+        self.nblk = nblk
+        self.src = [None if s == 0xFFFFFFFF else s for s in src]
+        self.file = [f if s is not None else None for f, s in zip(file, self.src)]
+        self.block = [b if s is not None else None for b, s in zip(block, self.src)]
+        self.stats = stats
+        self.skipped = skipped
+
+    @property
+    def found(self):
+        return self.stats["found"]
+
+    @property
+    def bytes_local(self):
+        return self.stats["bytes_local"]
+
+    def copies(self):
+        files, bs = _file_blocks(self._index)
+        paths = {}
+        g = 0
+        for path, size, n in files:
+            for j in range(n):
+                s = self.src[g + j]
+                if s is not None:
+                    if s not in paths:
+                        paths[s] = [p for p, _, _ in _file_blocks(self._sources[s])[0]]
+                    yield (path, j * bs, min(bs, size - j * bs), s, paths[s][self.file[g + j]],
+                           self.block[g + j] * bs)
+            g += n
+
+    def want_after(self):
+        out = bytearray(8 * ((self.nblk + 63) // 64))
+        for g in range(self.nblk):
+            wanted = self._want is None or self._want[g >> 3] >> (g & 7) & 1
+            if wanted and self.src[g] is None:
+                out[g >> 3] |= 1 << (g & 7)
+        return bytes(out)
+
+    def __repr__(self):
+        return "SourcesResult(%d of %d wanted blocks found, %d bytes)" % (
+            self.stats["found"], self.stats["wanted"], self.stats["bytes_local"])
+
+
+def _want_bitmap(index, want, skip_files, have):
+    """The want bitmap of block_sources as bytes (whole u64 words), or None
+    for "every block": `want` (bytes, bit g & 7 of byte g >> 3) minus the
+    blocks of the files in skip_files minus the 1-bits of `have`."""
+    if want is None and not skip_files and have is None:
+        return None
+    files, _ = _file_blocks(index)
+    nblk = sum(n for _, _, n in files)
+    nbytes = 8 * ((nblk + 63) // 64)
+    if want is None:
+        bits = bytearray(b"\xff" * nbytes)
+    else:
+        bits = bytearray(bytes(want)[:nbytes].ljust(nbytes, b"\0"))
+    if skip_files:
+        g = 0
+        for f, (_, _, n) in enumerate(files):
+            if f in skip_files:
+                for k in range(g, g + n):
+                    bits[k >> 3] &= ~(1 << (k & 7)) & 0xFF
+            g += n
+    if have is not None:
+        hv = bytes(have.have if isinstance(have, BlocksResult) else have)
+        for i, b in enumerate(hv[:nbytes]):
+            bits[i] &= ~b & 0xFF
+    return bytes(bits)
+
+
+def block_sources(index, sources, want=None, skip_files=None, have=None, context=None):
+    """Which blocks of `index` the older images whose indexes are `sources`
+    (best first) already hold, and where: what fill_blocks
+    (src/daemon/tracking/progress.rs:129-170) need not queue.  want: a bitmap
+    over the index's blocks (bytes, bit g & 7 of byte g >> 3; None = all);
+    skip_files: file ordinals whose blocks are not wanted (the hardlinked
+    files); have: a BlocksResult or bitmap whose 1-bits are not wanted.  With
+    a context the join runs on its first GPU; without one the same rule runs
+    on the host (no default context is opened).  Returns a SourcesResult; no
+    file is read and nothing is copied."""
+    if len(index):
+        ptr, keep = _buf(index)
+    else:  # (an empty index is a parse error, not a null argument)
+        keep = ctypes.create_string_buffer(1)
+        ptr = ctypes.cast(keep, ctypes.c_void_p)
+    sources = [bytes(s) for s in sources]
+    nsrc = len(sources)
+    bufs = [ctypes.create_string_buffer(s, max(len(s), 1)) for s in sources]
+    sp = (ctypes.c_void_p * max(nsrc, 1))(*[ctypes.cast(b, ctypes.c_void_p) for b in bufs])
+    sl = (ctypes.c_size_t * max(nsrc, 1))(*[len(s) for s in sources])
+    wbits = _want_bitmap(index, want, skip_files, have)
+    wbuf = None
+    if wbits is not None:
+        wbuf = (ctypes.c_uint64 * max(len(wbits) // 8, 1)).from_buffer_copy(
+            wbits.ljust(8, b"\0"))
+    so, fo, bo = ctypes.c_void_p(), ctypes.c_void_p(), ctypes.c_void_p()
+    nblk = ctypes.c_uint64()
+    skipped = ctypes.c_size_t()
+    stats = (ctypes.c_uint64 * _n.CIR_SOURCES_STATS_FIELDS)()
+    _n.check(_n.lib.cir_block_sources(context.handle if context is not None else None, ptr,
+                                      len(index), sp, sl, nsrc, wbuf, ctypes.byref(so),
+                                      ctypes.byref(fo), ctypes.byref(bo), ctypes.byref(nblk),
+                                      ctypes.byref(skipped), stats))
+    del keep
+    n = nblk.value
+    raw_s = _n.take_buffer(so.value, 4 * n)
+    raw_f = _n.take_buffer(fo.value, 8 * n)
+    raw_b = _n.take_buffer(bo.value, 8 * n)
+    src = list((ctypes.c_uint32 * n).from_buffer_copy(raw_s)) if n else []
+    file = list((ctypes.c_uint64 * n).from_buffer_copy(raw_f)) if n else []
+    block = list((ctypes.c_uint64 * n).from_buffer_copy(raw_b)) if n else []
+    return SourcesResult(index, sources, n, src, file, block,
+                         dict(zip(SourcesResult.STATS_FIELDS, list(stats))), skipped.value, wbits)
 
 
 _default = None

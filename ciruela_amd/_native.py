@@ -52,6 +52,7 @@ CIR_CHECK_READ = 2
 CIR_CHECK_STATS_FIELDS = 8
 CIR_LINKS_STATS_FIELDS = 8
 CIR_BLOCKS_STATS_FIELDS = 10
+CIR_SOURCES_STATS_FIELDS = 8
 CIR_FILE_COMPLETE = 0
 CIR_FILE_ABSENT = 1
 CIR_FILE_PARTIAL = 2
@@ -158,6 +159,14 @@ _SIGS = {
                                         ctypes.c_uint32, ctypes.POINTER(c_vp), c_u64p,
                                         ctypes.POINTER(c_vp), ctypes.POINTER(c_vp), c_sizep,
                                         c_u64p]),
+    "cir_match_table_slots": (ctypes.c_uint64, [ctypes.c_uint64]),
+    "cir_match_digests_dev": (ctypes.c_int, [c_vp, c_vp, ctypes.c_size_t, c_vp, ctypes.c_size_t,
+                                             c_vp, ctypes.c_uint64, ctypes.c_uint64, c_vp, c_vp,
+                                             c_vp]),
+    "cir_block_sources": (ctypes.c_int, [c_vp, c_vp, ctypes.c_size_t, ctypes.POINTER(c_vp),
+                                         c_sizep, ctypes.c_size_t, c_u64p, ctypes.POINTER(c_vp),
+                                         ctypes.POINTER(c_vp), ctypes.POINTER(c_vp), c_u64p,
+                                         c_sizep, c_u64p]),
     "cir_debug_compress_only_dev": (ctypes.c_int, [ctypes.c_uint64, ctypes.c_uint32, c_vp, c_vp]),
     "cir_debug_relay_blocks": (ctypes.c_uint64, [ctypes.c_uint64, ctypes.c_uint64]),
     "cir_debug_device_identity": (ctypes.c_int, [ctypes.c_int, ctypes.c_char_p, ctypes.c_size_t,

@@ -28,6 +28,18 @@
 //       `SRCDIR<TAB>PATH` (the path as the index spells it) for every
 //       candidate that passed the re-hash and the mode test, a summary on
 //       stderr, and exits 0 when the check ran.  Nothing is linked.
+//   ciruela-index blocks DIR INDEX_FILE [--list] [--disk-threads N]
+//       which blocks of INDEX_FILE the partial image in DIR already holds
+//       (cir_check_blocks); --list prints `PATH OFFSET` per missing block
+//   ciruela-index sources INDEX SRCINDEX [SRCINDEX ...] [--list] [--host]
+//       what fill_blocks (src/daemon/tracking/progress.rs:129-170) need not
+//       fetch: which blocks of the new image INDEX the older images'
+//       indexes SRCINDEX (best first) list, by digest, and where
+//       (cir_block_sources; no file is read).  Prints one summary line --
+//       blocks, found, bytes found, sources used and skipped -- and with
+//       --list one line per found block, `PATH OFFSET LENGTH SRC# SRCPATH
+//       SRCOFFSET` (paths escaped as in the index).  --host passes no
+//       context: the join runs on the host and no device is opened.
 #include <dirent.h>
 #include <errno.h>
 #include <fcntl.h>
@@ -52,7 +64,8 @@ static void usage() {
           "       ciruela-index check DIR INDEX_FILE [--disk-threads N]\n"
           "       ciruela-index links INDEX SRCDIR=SRCINDEX [SRCDIR=SRCINDEX ...]"
           " [--disk-threads N]\n"
-          "       ciruela-index blocks DIR INDEX_FILE [--list] [--disk-threads N]\n");
+          "       ciruela-index blocks DIR INDEX_FILE [--list] [--disk-threads N]\n"
+          "       ciruela-index sources INDEX SRCINDEX [SRCINDEX ...] [--list] [--host]\n");
 }
 
 static std::string hex(const uint8_t* p, size_t n) {
@@ -227,7 +240,7 @@ int main(int argc, char** argv) {
   uint32_t threads = 0;
   uint64_t bs = CIR_DEFAULT_BLOCK_SIZE;
   std::string index_dir;
-  bool list_blocks = false;
+  bool list_blocks = false, host_only = false;
   std::vector<Job> jobs;
   std::vector<std::string> files;
   for (int i = 2; i < argc; ++i) {
@@ -257,7 +270,8 @@ int main(int argc, char** argv) {
         bs = n;
     }
     else if (a == "--index-dir") index_dir = val();
-    else if (a == "--list" && cmd == "blocks") list_blocks = true;
+    else if (a == "--list" && (cmd == "blocks" || cmd == "sources")) list_blocks = true;
+    else if (a == "--host" && cmd == "sources") host_only = true;
     else if (a == "--append" || a == "--append-weak" || a == "--replace") {
       Job j;
       j.kind = a.substr(2);
@@ -266,7 +280,9 @@ int main(int argc, char** argv) {
         return 2;
       }
       jobs.push_back(j);
-    } else if ((cmd == "hash" || cmd == "check" || cmd == "links" || cmd == "blocks") && a.size() &&
+    } else if ((cmd == "hash" || cmd == "check" || cmd == "links" || cmd == "blocks" ||
+                cmd == "sources") &&
+               a.size() &&
                a[0] != '-') {
       files.push_back(a);
     } else {
@@ -296,8 +312,21 @@ int main(int argc, char** argv) {
       if (!read_file(files[i].substr(eq + 1), &link_indexes.back())) return 2;
     }
   }
+  if (cmd == "sources") {
+    // the indexes are read (and a missing one reported) before any device is opened
+    if (files.size() < 2) {
+      usage();
+      return 2;
+    }
+    for (size_t i = 1; i < files.size(); ++i) {
+      link_indexes.emplace_back();
+      if (!read_file(files[i], &link_indexes.back())) return 2;
+    }
+  }
   std::vector<std::string> inputs = cmd == "links" ? link_dirs : files;
+  if (cmd == "sources") inputs.clear();  // (indexes only: nothing is staged)
   std::vector<uint8_t> check_index;
+  if (cmd == "sources" && !read_file(files[0], &check_index)) return 2;
   if (cmd == "links" && !read_file(files[0], &check_index)) return 2;
   if (cmd == "check" || cmd == "blocks") {
     // the index is read (and a missing one reported) before any device is
@@ -336,7 +365,7 @@ int main(int argc, char** argv) {
   auto ms_since = [](std::chrono::steady_clock::time_point t) {
     return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t).count();
   };
-  if (trace) {
+  if (trace && !host_only) {
     fprintf(stderr, "ciruela-index: staging %llu bytes per slot (0 = library default), %s copies\n",
             (unsigned long long)staging,
             strcmp(getenv("HSA_ENABLE_SDMA") ? getenv("HSA_ENABLE_SDMA") : "1", "0") == 0
@@ -358,9 +387,9 @@ int main(int argc, char** argv) {
   // and a small input is one short job: one stream and one slot per device
   // (CIR_INIT_ONE_SHOT; the other streams' hardware queues were ~25 ms of
   // cir_init, profiles/r05/start_env.log)
-  int rc = cir_init_n(&ctx, 0, staging, ndev, small ? CIR_INIT_ONE_SHOT : 0u);
+  int rc = host_only ? CIR_OK : cir_init_n(&ctx, 0, staging, ndev, small ? CIR_INIT_ONE_SHOT : 0u);
   if (rc) return die(rc, "cir_init");
-  if (trace) {
+  if (trace && !host_only) {
     int ids[64];
     const int opened = cir_ctx_devices(ctx, ids, 64);
     fprintf(stderr, "ciruela-index: cir_init %.1f ms, %d device(s) for %llu input bytes\n",
@@ -483,6 +512,59 @@ int main(int argc, char** argv) {
             skipped);
     cir_free(lf);
     cir_free(ls);
+  } else if (cmd == "sources") {
+    static const uint8_t none = 0;
+    std::vector<const uint8_t*> sidx;
+    std::vector<size_t> slen;
+    for (const std::vector<uint8_t>& v : link_indexes) {
+      sidx.push_back(v.empty() ? &none : v.data());
+      slen.push_back(v.size());
+    }
+    uint32_t* bsrc = nullptr;
+    uint64_t* bfile = nullptr;
+    uint64_t* bblock = nullptr;
+    uint64_t nblk = 0;
+    size_t skipped = 0;
+    uint64_t st[CIR_SOURCES_STATS_FIELDS];
+    rc = cir_block_sources(ctx, check_index.empty() ? &none : check_index.data(),
+                           check_index.size(), sidx.data(), slen.data(), sidx.size(), nullptr,
+                           &bsrc, &bfile, &bblock, &nblk, &skipped, st);
+    if (rc) {
+      die(rc, files[0].c_str());
+      return 2;
+    }
+    printf("sources: %llu blocks, %llu found, %llu bytes found; %llu source index(es) used, %zu "
+           "skipped\n",
+           (unsigned long long)nblk, (unsigned long long)st[1], (unsigned long long)st[2],
+           (unsigned long long)st[4], skipped);
+    if (list_blocks) {
+      std::vector<uint64_t> sizes;
+      uint64_t ibs = 0;
+      const std::vector<std::string> paths = index_file_paths(check_index, &sizes, &ibs);
+      std::vector<std::vector<std::string>> spaths(link_indexes.size());
+      std::vector<bool> loaded(link_indexes.size(), false);
+      uint64_t g = 0;
+      for (size_t i = 0; i < paths.size() && ibs; ++i) {
+        const uint64_t n = (sizes[i] + ibs - 1) / ibs;
+        for (uint64_t j = 0; j < n && g + j < nblk; ++j) {
+          const uint32_t s = bsrc[g + j];
+          if (s == UINT32_MAX || s >= link_indexes.size()) continue;
+          if (!loaded[s]) {
+            spaths[s] = index_file_paths(link_indexes[s]);
+            loaded[s] = true;
+          }
+          if (bfile[g + j] >= spaths[s].size()) continue;
+          printf("%s %llu %llu %u %s %llu\n", paths[i].c_str(), (unsigned long long)(j * ibs),
+                 (unsigned long long)std::min<uint64_t>(ibs, sizes[i] - j * ibs), s,
+                 spaths[s][bfile[g + j]].c_str(), (unsigned long long)(bblock[g + j] * ibs));
+        }
+        g += n;
+      }
+    }
+    fflush(stdout);
+    cir_free(bsrc);
+    cir_free(bfile);
+    cir_free(bblock);
   } else if (cmd == "sync") {
     if (jobs.empty()) {
       usage();
@@ -553,7 +635,7 @@ int main(int argc, char** argv) {
     _exit(0);
   }
   const auto t_destroy = std::chrono::steady_clock::now();
-  cir_destroy(ctx);
+  if (ctx) cir_destroy(ctx);
   if (trace) fprintf(stderr, "ciruela-index: cir_destroy %.1f ms\n", ms_since(t_destroy));
   return 0;
 }

@@ -168,6 +168,26 @@ hipError_t launch_seg_bad(const uint8_t* got, const uint8_t* want, uint64_t n,
 hipError_t launch_block_bits(const uint8_t* got, const uint8_t* want, uint64_t n, uint64_t* have,
                              uint32_t* nbad, hipStream_t s, const uint8_t* flag = nullptr);
 
+// Join of two digest lists (join.hip; cir_match_digests_dev): match[i] = the
+// smallest j < n_pool with pool[j] == need[i] over all 32 bytes, or
+// UINT32_MAX; *nmatch (device u32, nullable) = how many matched.  `table` is
+// table_slots u32 of scratch (a power of two >= join_table_slots(n_pool)),
+// initialised here; every match[0 .. n_need) and the count are written here,
+// all on `s`.  n_pool <= kJoinMaxPool, n_need < 2^32; both lists 16-B aligned.
+// tev (nullable, a traced cir_block_sources): 3 events recorded before the
+// build kernel, between the two kernels and after the probe kernel.
+constexpr uint32_t kJoinEmpty = 0xFFFFFFFFu;
+constexpr uint64_t kJoinMaxPool = 0x7FFFFFFFull;
+inline uint64_t join_table_slots(uint64_t n_pool) {
+  if (n_pool > (1ull << 62)) return 0;  // no u64 holds it (callers cap n_pool far below)
+  uint64_t s = 64;
+  while (s < 2 * n_pool) s <<= 1;
+  return s;
+}
+hipError_t launch_join(const uint8_t* need, uint64_t n_need, const uint8_t* pool, uint64_t n_pool,
+                       uint32_t* table, uint64_t table_slots, uint64_t seed, uint32_t* match,
+                       uint32_t* nmatch, hipStream_t s, const hipEvent_t* tev = nullptr);
+
 // nlanes x `lines` register-only compressions (diagnostic VALU ceiling).
 hipError_t launch_compress_only(uint64_t nlanes, uint32_t lines, uint8_t* out, hipStream_t s);
 

@@ -527,6 +527,97 @@ int cir_check_blocks(cir_ctx* ctx, int dirfd, const char* dir, const uint8_t* in
                      uint8_t** state_out, int32_t** errno_out, size_t* nfiles_out,
                      uint64_t stats[CIR_BLOCKS_STATS_FIELDS]);
 
+/* Slots the table of cir_match_digests_dev needs for n_pool digests: the smallest power of two
+ * >= max(64, 2 * n_pool), so the table is never more than half full (0 when no u64 holds it:
+ * n_pool > 2^62).  Pure: no HIP call. */
+uint64_t cir_match_table_slots(uint64_t n_pool);
+
+/* The join behind cir_block_sources, device-resident: which of n_need digests (d_need, 32 bytes
+ * each) occur among n_pool digests (d_pool), and where first.  The reference has no counterpart:
+ * fill_blocks queues every block of every file that was not hardlinked whole (src/daemon/
+ * tracking/progress.rs:129-170), and scan_links matches whole files only (src/daemon/metadata/
+ * hardlink_sources.rs:131-133, the break at :143).
+ *
+ * d_match[i] (device u32 x n_need) = the smallest j < n_pool with pool[j] == need[i] over all 32
+ * bytes, or UINT32_MAX; *d_nmatch (device u32, may be NULL) = the number of entries that
+ * matched.  d_table is table_slots u32 of device scratch that the call initialises itself
+ * (table_slots a power of two >= cir_match_table_slots(n_pool)).  Like every *_dev call it
+ * allocates nothing, synchronises nothing and runs on `stream` alone; there are no side
+ * streams, so ctx may be NULL and is not used for scratch.  Every d_match[0 .. n_need) and the
+ * count are written by the call, nothing past them and nothing past d_table[table_slots);
+ * n_pool == 0 writes all UINT32_MAX and 0, n_need == 0 writes only the count.
+ *
+ * The table is open addressing with linear probing (wrapping) over pool ordinals, and the home
+ * slot is part of the contract: x = seed; for the digest's four little-endian u64 words w in
+ * order, x = (x ^ w) * 0x9E3779B97F4A7C15, x ^= x >> 32; home = x & (table_slots - 1).  It
+ * folds all 32 bytes under the caller's seed because pool digests come from other parties'
+ * indexes: digests crafted to share a prefix do not share a home slot, and a caller that joins
+ * untrusted digests passes an unpredictable seed (cir_block_sources draws one per call), so
+ * nobody can craft a pool that chains through one run of slots.  The result does not depend
+ * on the seed.
+ *
+ * CIR_EINVAL: a NULL or non-16-byte-aligned d_need or d_pool when its count is not 0; a NULL
+ * d_match with n_need > 0; a NULL d_table; table_slots not a power of two or below
+ * cir_match_table_slots(n_pool); n_pool > 2^31 - 1; n_need > 2^32 - 1 (the count is a u32);
+ * d_match, d_table or d_nmatch not 4-byte aligned. */
+int cir_match_digests_dev(cir_ctx* ctx, const uint8_t* d_need, size_t n_need,
+                          const uint8_t* d_pool, size_t n_pool,
+                          uint32_t* d_table, uint64_t table_slots, uint64_t seed,
+                          uint32_t* d_match, uint32_t* d_nmatch, void* stream);
+
+/* Which blocks of a new image older local images already hold, and where: what fill_blocks
+ * (src/daemon/tracking/progress.rs:129-170) would need in order not to put every block of a
+ * changed, appended-to or moved file on the wire.  scan_links matches whole files only -- same
+ * path, same size, all digests equal (src/daemon/metadata/hardlink_sources.rs:131-133) -- so
+ * one changed block sends its whole file, although the other blocks sit in an older image of
+ * the same base directory.  The indexes say where; no file is read, and nothing is copied (the
+ * copy stays the caller's, and cir_check_blocks afterwards re-hashes what was copied).
+ *
+ * The rule.  Need list: the file entries of `index` in index order, blocks ascending -- the
+ * global block numbering of cir_check_index's stats[7] and of cir_check_blocks.  Pool: the
+ * sources src_index[s] / src_len[s] (s < nsrc) in the order given (the reference ranks newest
+ * first, hardlink_sources.rs:66-72), within a source the file entries in index order, blocks
+ * ascending; pool ordinal j counts across all sources.  A source that does not parse, or whose
+ * hash type or block size is not the new index's, takes no part and is counted in
+ * *nskipped_out (may be NULL), as in cir_link_candidates; source ordinals in the result still
+ * refer to the order given.  Block g matches the smallest pool ordinal j whose 32-byte digest
+ * equals its own: the first source in the caller's ranking, then the first place in index
+ * order (the flavour of scan_links' break at :143).  Then the two blocks' lengths, min(bs,
+ * size - block * bs) on either side, are compared: if they differ the source index lies or a
+ * digest collided, the block is reported as not found and counted in stats[5], and no second
+ * candidate is looked for.  Matches inside `index` itself are not looked for.
+ *
+ * want (may be NULL = every block): a bitmap over the global blocks, bit (g & 63) of word
+ * g >> 6, ceil(nblk / 64) words; bits at and past nblk are ignored.  The caller clears the
+ * blocks of hardlinked files and the 1-bits of a cir_check_blocks bitmap.
+ *
+ * For every global block g: src_out[g] = the source ordinal, or UINT32_MAX for "not found" and
+ * for "not wanted"; src_file_out[g] = the file ordinal inside that source's index, counting
+ * file entries only as in cir_link_candidates; src_block_out[g] = the block number inside that
+ * file (byte offset block x block_size; the length is the new block's own).  Unmatched entries
+ * of the last two are UINT64_MAX.  The arrays are malloc'd (cir_free), *nblk_out long, and
+ * NULL when *nblk_out == 0.
+ *
+ * With a context the join runs on the context's first device (cir_match_digests_dev's kernels;
+ * device buffers are allocated for the call and freed after it, the seed is drawn per call, the
+ * current device is restored); with ctx == NULL the same rule is applied on the host with a
+ * hash map in which the first entry wins, and no GPU is needed.  Both give identical arrays.
+ *
+ * CIR_EINVAL: null arguments, or more than 2^31 - 1 pool blocks in total (pass fewer sources);
+ * CIR_EPARSE / CIR_EHASHSIZE: `index` does not parse; CIR_ENOMEM.  All are decided before any
+ * device work.
+ *
+ * stats: [0] blocks wanted, [1] blocks found, [2] bytes found locally, [3] pool blocks, [4]
+ * sources used, [5] matches dropped because the lengths differ, [6] table slots (0 on the
+ * host), [7] 1 if joined on the device (a context was given), 0 if on the host. */
+#define CIR_SOURCES_STATS_FIELDS 8
+int cir_block_sources(cir_ctx* ctx, const uint8_t* index, size_t len,
+                      const uint8_t* const* src_index, const size_t* src_len, size_t nsrc,
+                      const uint64_t* want,
+                      uint32_t** src_out, uint64_t** src_file_out, uint64_t** src_block_out,
+                      uint64_t* nblk_out, size_t* nskipped_out,
+                      uint64_t stats[CIR_SOURCES_STATS_FIELDS]);
+
 /* ---- index (DIRSIGNATURE.v1) ----------------------------------------- */
 
 /* dir_signature::v1::scan(&ScannerConfig, &mut Vec<u8>)
