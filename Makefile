@@ -18,17 +18,19 @@ OBJDIR := build/obj
 LIB := ciruela_amd/libciruela_amd.so
 CLI := bin/ciruela-index
 
-SRCS_HIP := $(CSRC)/kernels.hip $(CSRC)/order.hip $(CSRC)/join.hip
+SRCS_HIP := $(CSRC)/kernels.hip $(CSRC)/order.hip $(CSRC)/join.hip \
+            $(CSRC)/idxscan.hip
 SRCS_CPP := $(CSRC)/runtime.cpp $(CSRC)/dirsig.cpp $(CSRC)/scan.cpp $(CSRC)/check.cpp \
-            $(CSRC)/links.cpp $(CSRC)/sources.cpp $(CSRC)/registry.cpp \
+            $(CSRC)/links.cpp $(CSRC)/sources.cpp $(CSRC)/idxscan.cpp $(CSRC)/registry.cpp \
             $(CSRC)/blake2b_host.cpp $(CSRC)/sha512_host.cpp
-OBJS := $(patsubst $(CSRC)/%.hip,$(OBJDIR)/%.o,$(SRCS_HIP)) \
+OBJS := $(patsubst $(CSRC)/%.hip,$(OBJDIR)/%.hip.o,$(SRCS_HIP)) \
         $(patsubst $(CSRC)/%.cpp,$(OBJDIR)/%.o,$(SRCS_CPP))
 HDRS := $(wildcard $(CSRC)/*.hpp) include/ciruela_blockhash.h
 
 all: $(LIB) $(CLI) build/hash_bytes_conc build/verify_daemon_sim oracle
 
-$(OBJDIR)/%.o: $(CSRC)/%.hip $(HDRS)
+# (x.hip -> x.hip.o: idxscan.hip and idxscan.cpp share a stem)
+$(OBJDIR)/%.hip.o: $(CSRC)/%.hip $(HDRS)
 	@mkdir -p $(OBJDIR)
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
 
@@ -61,7 +63,7 @@ build/verify_daemon_sim: tools/verify_daemon_sim.cpp $(LIB) include/ciruela_bloc
 # code (tools/host_asan_driver.cpp; sanitizers on the host side only)
 ASAN_HOST := -O1 -g -Xarch_host -fsanitize=address -Xarch_host -fsanitize=undefined \
              -Xarch_host -fno-sanitize-recover=all -Xarch_host -fno-omit-frame-pointer
-ASAN_OBJS := $(patsubst $(CSRC)/%.hip,$(OBJDIR)/%.o,$(SRCS_HIP)) \
+ASAN_OBJS := $(patsubst $(CSRC)/%.hip,$(OBJDIR)/%.hip.o,$(SRCS_HIP)) \
              $(patsubst $(CSRC)/%.cpp,build/asan/%.o,$(SRCS_CPP)) build/asan/host_asan_driver.o
 build/asan/%.o: $(CSRC)/%.cpp $(HDRS)
 	@mkdir -p build/asan
@@ -76,7 +78,7 @@ asan: build/host_asan_driver
 # the same driver with the host code under ThreadSanitizer
 # (TSAN_OPTIONS=suppressions=tools/tsan_hip.supp)
 TSAN_HOST := -O1 -g -Xarch_host -fsanitize=thread
-TSAN_OBJS := $(patsubst $(CSRC)/%.hip,$(OBJDIR)/%.o,$(SRCS_HIP)) \
+TSAN_OBJS := $(patsubst $(CSRC)/%.hip,$(OBJDIR)/%.hip.o,$(SRCS_HIP)) \
              $(patsubst $(CSRC)/%.cpp,build/tsan/%.o,$(SRCS_CPP)) build/tsan/host_asan_driver.o
 build/tsan/%.o: $(CSRC)/%.cpp $(HDRS)
 	@mkdir -p build/tsan

@@ -48,6 +48,10 @@ block_sources                   what fill_blocks lacks: which of the blocks it q
                                 hardlink_sources.rs:131-133)
 Context.match_digests_dev       the join behind it on the device: per needed digest the
                                 smallest ordinal of an equal digest in a pool
+index_digests,                  what every consumer of an index starts with: its block
+  Context.index_digests_dev     digests as one array and a run record per non-empty
+                                file, parsed on the device (the reference parses the
+                                text on a host thread: src/blocks.rs:150-183)
 =============================  ==============================================
 
 All hashing runs on gfx950 through the library; there is no CPU fallback.
@@ -65,6 +69,7 @@ __all__ = [
     "IndexError_", "DirError", "ReadError", "CiruelaError", "NoDevice", "sha512_256",
     "check_index", "CheckResult", "link_candidates", "check_links", "LinksResult",
     "check_blocks", "BlocksResult", "block_sources", "SourcesResult",
+    "index_digests", "IndexDigests",
 ]
 
 DEFAULT_BLOCK_SIZE = 32768
@@ -308,6 +313,18 @@ class Context:
         written by the call, on `stream` alone."""
         _n.check(_n.lib.cir_match_digests_dev(self._h, d_need, n_need, d_pool, n_pool, d_table,
                                               table_slots, seed, d_match, d_nmatch, stream))
+
+    def index_digests_dev(self, d_text, length, body_off, body_end, block_size, d_digests,
+                          cap_blocks, d_runs, cap_runs, d_work, work_bytes, d_res, stream=0):
+        """A device-resident index text to device-resident digests and run
+        records (cir_index_digests_dev): the body [body_off, body_end) as
+        index_frame gives it; d_res: 5 u64 {status, file entries, runs,
+        blocks, first declined line}; d_work: index_work_bytes(length) bytes.
+        cap_blocks = length // 65 and cap_runs = length // 73 always suffice.
+        All written by the call, on `stream` alone."""
+        _n.check(_n.lib.cir_index_digests_dev(self._h, d_text, length, body_off, body_end,
+                                              block_size, d_digests, cap_blocks, d_runs,
+                                              cap_runs, d_work, work_bytes, d_res, stream))
 
     # ---- asynchronous per-block verify (FetchBlock::poll, fetch_blocks.rs:77)
     def verify_submit(self, data, expected, hash_type=None):
@@ -836,6 +853,67 @@ def block_sources(index, sources, want=None, skip_files=None, have=None, context
     block = list((ctypes.c_uint64 * n).from_buffer_copy(raw_b)) if n else []
     return SourcesResult(index, sources, n, src, file, block,
                          dict(zip(SourcesResult.STATS_FIELDS, list(stats))), skipped.value, wbits)
+
+
+class IndexDigests:
+    """Answer of index_digests.  hash_type: a CIR_HASH_* code; block_size;
+    digests: numpy u8 (nblk, 32), the file entries' block digests in index
+    order (the global block numbering of check_blocks); runs: numpy u64
+    (nruns, 4), per non-empty file {first block, size, file ordinal, offset of
+    the first hash token's leading space in the text}; nfiles: the file
+    entries; stats: on_device, fell_back, declined_at (None when no line was
+    reported), uploaded_bytes."""
+
+    STATS_FIELDS = ("on_device", "fell_back", "declined_at", "uploaded_bytes")
+
+    def __init__(self, hash_type, block_size, digests, runs, nfiles, stats):
+        self.hash_type = hash_type
+        self.block_size = block_size
+        self.digests = digests
+        self.runs = runs
+        self.nfiles = nfiles
+        self.stats = stats
+
+    @property
+    def nblk(self):
+        return len(self.digests)
+
+    def __repr__(self):
+        return "IndexDigests(%d blocks of %d files, block_size %d)" % (
+            self.nblk, self.nfiles, self.block_size)
+
+
+def index_digests(index, ctx=None):
+    """An index's block digests as an array: the text parsed into a flat
+    digest list and a run record per non-empty file.  With a context the text
+    is uploaded and parsed by the gfx950 kernels on its first GPU
+    (cir_index_digests_dev; a text outside the canonical form the device
+    takes goes through the host parser instead); without one the host parser
+    alone runs and no GPU is needed.  Both give identical arrays and raise the
+    same errors.  Returns an IndexDigests."""
+    import numpy as np
+    if len(index):
+        ptr, keep = _buf(index)
+    else:  # (an empty index is a parse error, not a null argument)
+        keep = ctypes.create_string_buffer(1)
+        ptr = ctypes.cast(keep, ctypes.c_void_p)
+    ht = ctypes.c_int()
+    bs, nblk = ctypes.c_uint64(), ctypes.c_uint64()
+    dg, rn = ctypes.c_void_p(), ctypes.c_void_p()
+    nruns, nfiles = ctypes.c_size_t(), ctypes.c_size_t()
+    stats = (ctypes.c_uint64 * _n.CIR_INDEX_STATS_FIELDS)()
+    _n.check(_n.lib.cir_index_digests(ctx.handle if ctx is not None else None, ptr, len(index),
+                                      ctypes.byref(ht), ctypes.byref(bs), ctypes.byref(dg),
+                                      ctypes.byref(nblk), ctypes.byref(rn), ctypes.byref(nruns),
+                                      ctypes.byref(nfiles), stats))
+    del keep
+    digests = np.frombuffer(_n.take_buffer(dg.value, 32 * nblk.value), dtype=np.uint8)
+    runs = np.frombuffer(_n.take_buffer(rn.value, 32 * nruns.value), dtype=np.uint64)
+    st = dict(zip(IndexDigests.STATS_FIELDS, list(stats)))
+    if st["declined_at"] == (1 << 64) - 1:
+        st["declined_at"] = None
+    return IndexDigests(ht.value, bs.value, digests.reshape(-1, 32), runs.reshape(-1, 4),
+                        nfiles.value, st)
 
 
 _default = None

@@ -53,6 +53,11 @@ CIR_CHECK_STATS_FIELDS = 8
 CIR_LINKS_STATS_FIELDS = 8
 CIR_BLOCKS_STATS_FIELDS = 10
 CIR_SOURCES_STATS_FIELDS = 8
+CIR_INDEX_RES_FIELDS = 5
+CIR_INDEX_STATS_FIELDS = 4
+CIR_INDEX_OK = 0
+CIR_INDEX_CAPACITY = 1
+CIR_INDEX_DECLINED = 2
 CIR_FILE_COMPLETE = 0
 CIR_FILE_ABSENT = 1
 CIR_FILE_PARTIAL = 2
@@ -167,6 +172,18 @@ _SIGS = {
                                          c_sizep, ctypes.c_size_t, c_u64p, ctypes.POINTER(c_vp),
                                          ctypes.POINTER(c_vp), ctypes.POINTER(c_vp), c_u64p,
                                          c_sizep, c_u64p]),
+    "cir_index_frame": (ctypes.c_int, [c_vp, ctypes.c_size_t, ctypes.POINTER(ctypes.c_int), c_u64p,
+                                       c_u64p, c_u64p]),
+    "cir_index_work_bytes": (ctypes.c_uint64, [ctypes.c_uint64]),
+    "cir_debug_index_tile_bytes": (ctypes.c_uint64, []),
+    "cir_index_digests_dev": (ctypes.c_int, [c_vp, c_vp, ctypes.c_uint64, ctypes.c_uint64,
+                                             ctypes.c_uint64, ctypes.c_uint64, c_vp,
+                                             ctypes.c_uint64, c_vp, ctypes.c_uint64, c_vp,
+                                             ctypes.c_uint64, c_vp, c_vp]),
+    "cir_index_digests": (ctypes.c_int, [c_vp, c_vp, ctypes.c_size_t,
+                                         ctypes.POINTER(ctypes.c_int), c_u64p,
+                                         ctypes.POINTER(c_vp), c_u64p, ctypes.POINTER(c_vp),
+                                         c_sizep, c_sizep, c_u64p]),
     "cir_debug_compress_only_dev": (ctypes.c_int, [ctypes.c_uint64, ctypes.c_uint32, c_vp, c_vp]),
     "cir_debug_relay_blocks": (ctypes.c_uint64, [ctypes.c_uint64, ctypes.c_uint64]),
     "cir_debug_device_identity": (ctypes.c_int, [ctypes.c_int, ctypes.c_char_p, ctypes.c_size_t,

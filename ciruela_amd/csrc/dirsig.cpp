@@ -236,6 +236,56 @@ static bool valid_dir_path(const std::string& p) {
   return true;
 }
 
+// The header line's rules, shared by parse() and frame().
+static bool parse_header_line(const std::string& line, Header* h, std::string* err) {
+  std::vector<std::string> tok;
+  split_ws(line, &tok);
+  if (tok.size() < 2 || tok[0] != "DIRSIGNATURE.v1") {
+    *err = "bad header signature";
+    return false;
+  }
+  if (!parse_hash_type(tok[1], &h->hash)) {
+    *err = "unknown hash type " + tok[1];
+    return false;
+  }
+  h->block_size = 32768;
+  for (size_t i = 2; i < tok.size(); ++i) {
+    if (tok[i].compare(0, 11, "block_size=") == 0) {
+      if (!parse_u64(tok[i].substr(11), &h->block_size) || h->block_size == 0) {
+        *err = "bad block_size";
+        return false;
+      }
+    }
+  }
+  return true;
+}
+
+bool frame(const uint8_t* data, size_t len, Header* h, size_t* body_off, size_t* body_end,
+           std::string* err) {
+  if (len && data[len - 1] != '\n') {
+    *err = "index does not end with a newline";
+    return false;
+  }
+  const uint8_t* nl = len ? (const uint8_t*)memchr(data, '\n', len) : nullptr;
+  if (!nl || (size_t)(nl - data) == len - 1) {  // fewer than two lines
+    *err = "index too short";
+    return false;
+  }
+  const size_t first = nl - data;
+  size_t last = len - 1;  // start of the last line: behind the '\n' before the final one
+  while (data[last - 1] != '\n') --last;
+  if (!parse_header_line(std::string((const char*)data, first), h, err)) return false;
+  std::vector<uint8_t> footer;
+  if (!from_hex(std::string((const char*)data + last, len - 1 - last), &footer) ||
+      footer.empty()) {
+    *err = "bad footer line";
+    return false;
+  }
+  *body_off = first + 1;
+  *body_end = last;
+  return true;
+}
+
 bool parse(const uint8_t* data, size_t len, Index* out, std::string* err) {
   out->entries.clear();
   std::vector<std::string> lines;
@@ -254,25 +304,8 @@ bool parse(const uint8_t* data, size_t len, Index* out, std::string* err) {
     *err = "index too short";
     return false;
   }
+  if (!parse_header_line(lines[0], &out->header, err)) return false;
   std::vector<std::string> tok;
-  split_ws(lines[0], &tok);
-  if (tok.size() < 2 || tok[0] != "DIRSIGNATURE.v1") {
-    *err = "bad header signature";
-    return false;
-  }
-  if (!parse_hash_type(tok[1], &out->header.hash)) {
-    *err = "unknown hash type " + tok[1];
-    return false;
-  }
-  out->header.block_size = 32768;
-  for (size_t i = 2; i < tok.size(); ++i) {
-    if (tok[i].compare(0, 11, "block_size=") == 0) {
-      if (!parse_u64(tok[i].substr(11), &out->header.block_size) || out->header.block_size == 0) {
-        *err = "bad block_size";
-        return false;
-      }
-    }
-  }
   const size_t dl = digest_len(out->header.hash);
   std::string cur_dir;
   bool have_dir = false;

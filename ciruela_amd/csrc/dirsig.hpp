@@ -117,6 +117,13 @@ struct Index {
 // (the reference's v1::ParseError).
 bool parse(const uint8_t* data, size_t len, Index* out, std::string* err);
 
+// The frame of an index without its body: parse()'s rules for the line
+// structure, the header line and the footer line, with parse()'s error texts.
+// The body is the bytes [*body_off, *body_end): behind the header line, before
+// the footer line; empty or ending in '\n'.
+bool frame(const uint8_t* data, size_t len, Header* h, size_t* body_off, size_t* body_end,
+           std::string* err);
+
 // dir_signature::get_hash: decode the hex on the last line.
 bool get_hash(const uint8_t* data, size_t len, std::vector<uint8_t>* id, std::string* err);
 

@@ -188,6 +188,40 @@ hipError_t launch_join(const uint8_t* need, uint64_t n_need, const uint8_t* pool
                        uint32_t* table, uint64_t table_slots, uint64_t seed, uint32_t* match,
                        uint32_t* nmatch, hipStream_t s, const hipEvent_t* tev = nullptr);
 
+// An index's block digests parsed on the device (idxscan.hip;
+// cir_index_digests_dev): the body text[body_off, body_end) of a
+// DIRSIGNATURE.v1 index of `len` bytes (text 8-B aligned) to digests (32 B
+// per block, 16-B aligned, at most cap_blocks) and runs (4 u64 per non-empty
+// file {first, size, file, hash_off}, at most cap_runs), all on `s`.  work:
+// idx_work_bytes(len) bytes of scratch; res: kIdxResFields u64 {status, file
+// entries, runs, blocks, start of the first declined line or UINT64_MAX}, all
+// initialised here.  Unchecked: body_off <= body_end <= len <= kIdxMaxLen, bs
+// != 0, cap_blocks < 2^32.
+constexpr uint32_t kIdxTile = 4096;  // bytes of text per workgroup of the count and emit passes
+// Longest text: below it no sum of per-line block counts can pass 2^64 even
+// over lines that overlap (at most len / 8 lines of at most len / 65 blocks).
+constexpr uint64_t kIdxMaxLen = 1ull << 36;
+constexpr int kIdxResFields = 5;
+constexpr uint64_t kIdxOk = 0, kIdxCapacity = 1, kIdxDeclined = 2;
+inline uint64_t idx_work_bytes(uint64_t len) { return 24 * (len / kIdxTile + 2); }
+hipError_t launch_index_digests(const uint8_t* text, uint64_t len, uint64_t body_off,
+                                uint64_t body_end, uint64_t bs, uint8_t* digests,
+                                uint64_t cap_blocks, uint64_t* runs, uint64_t cap_runs,
+                                uint64_t* work, uint64_t* res, hipStream_t s);
+// Its two halves, for a caller that learns the counts in between (a
+// synchronise of its own) in order to place the digests: launch_index_count =
+// the count and scan passes (res is complete but for a bad token's verdict);
+// launch_index_emit = the emit and decode passes into digests / runs, gated on
+// the scan's status in `work`; max_blocks = an upper bound of res[3] (the
+// decode's grid), at most the digests' capacity.
+hipError_t launch_index_count(const uint8_t* text, uint64_t len, uint64_t body_off,
+                              uint64_t body_end, uint64_t bs, uint64_t cap_blocks,
+                              uint64_t cap_runs, uint64_t* work, uint64_t* res, hipStream_t s);
+hipError_t launch_index_emit(const uint8_t* text, uint64_t len, uint64_t body_off,
+                             uint64_t body_end, uint64_t bs, uint8_t* digests, uint64_t max_blocks,
+                             uint64_t* runs, uint64_t cap_runs, uint64_t* work, uint64_t* res,
+                             hipStream_t s);
+
 // nlanes x `lines` register-only compressions (diagnostic VALU ceiling).
 hipError_t launch_compress_only(uint64_t nlanes, uint32_t lines, uint8_t* out, hipStream_t s);
 

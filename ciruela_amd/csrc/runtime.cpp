@@ -35,6 +35,11 @@ int fail(int code, const std::string& msg) {
   return code;
 }
 
+int parse_fail(bool bad_hash_size, const std::string& err) {
+  return bad_hash_size ? fail(CIR_EHASHSIZE, "hash size is unsupported: " + err)
+                       : fail(CIR_EPARSE, "error parsing index: " + err);
+}
+
 int boundary_error() noexcept {
   int code = CIR_EIO;
   const char* what = "unknown exception";

@@ -21,6 +21,9 @@ namespace cir {
 
 int fail(int code, const std::string& msg);
 int hip_fail(hipError_t e, const char* what);
+// An index that dirsig::parse rejected with `err`: CIR_EHASHSIZE when a block
+// hash had another size (Index::bad_hash_size), else CIR_EPARSE.
+int parse_fail(bool bad_hash_size, const std::string& err);
 
 // No C++ exception crosses the C ABI (a Rust caller unwinding through it is
 // undefined behaviour; a C caller would be terminated): every int-returning

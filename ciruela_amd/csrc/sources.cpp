@@ -11,7 +11,10 @@
 // of two digest lists; no file is read here, and the copy stays the caller's.
 //
 // The rule, the pool builder, the host join and the mapping are sources.hpp
-// (no HIP); the device join is join.hip.
+// (no HIP); the device join is join.hip.  With a context the indexes' text is
+// parsed on the device as well (idxscan.hip, the rule idxscan.hpp): the need
+// list and the pool are decoded straight into the join's buffers and only the
+// run tables come back.
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -23,6 +26,7 @@
 #include <vector>
 
 #include "dirsig.hpp"
+#include "idxscan.hpp"
 #include "runtime.hpp"
 #include "sources.hpp"
 
@@ -128,6 +132,386 @@ int device_join(cir_ctx* ctx, const std::vector<uint8_t>& need, uint64_t n_need,
   return CIR_OK;
 }
 
+// CIR_SOURCES_PARSE=host: with a context, parse every text on the host as
+// before the device parse existed (A/B measurement).
+bool parse_on_host() {
+  const char* v = getenv("CIR_SOURCES_PARSE");
+  return v && strcmp(v, "host") == 0;
+}
+
+// One index text of a call with the device parse.
+struct Text {
+  const uint8_t* p = nullptr;
+  size_t len = 0;
+  dirsig::Header h;
+  size_t body_off = 0, body_end = 0;
+  bool framed = false;     // dirsig::frame took it
+  bool candidate = false;  // takes part unless its body does not parse
+  bool dev = false;        // its body is parsed on the device in this attempt
+  bool usable = false;
+  uint64_t nblk = 0;
+  uint64_t text_off = 0, work_off = 0, runs_off = 0;  // bytes / bytes / records in the buffers
+  uint64_t res[CIR_INDEX_RES_FIELDS] = {0, 0, 0, 0, 0};
+  dirsig::Index parsed;  // on the host path
+  std::string err;
+  bool host_done = false, host_ok = false;  // dirsig::parse ran / took it
+  std::vector<uint8_t> digests;       // host path: its digests, until they are uploaded
+  std::vector<idxscan::Run> runs;     // device path: its run table
+};
+
+struct DevSet {
+  std::vector<void*> p;
+  hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
+  ~DevSet() {
+    for (void* q : p)
+      if (q) (void)hipFree(q);
+    for (hipEvent_t e : ev)
+      if (e) (void)hipEventDestroy(e);
+  }
+  int alloc(void** out, size_t bytes) {
+    void* q = nullptr;
+    if (hipMalloc(&q, bytes ? bytes : 16) != hipSuccess) {
+      (void)hipGetLastError();
+      return fail(CIR_ENOMEM, "hipMalloc of the call's buffers");
+    }
+    p.push_back(q);
+    *out = q;
+    return CIR_OK;
+  }
+};
+
+// What an attempt returns besides a CIR_* code (none of those is positive).
+constexpr int kRetry = 1;     // again, with more texts on the host
+constexpr int kHostFlow = 2;  // the host flow decides this call
+
+// Waits for the stream on scope exit: declared behind the host buffers that
+// asynchronous copies write, so none is destroyed with a copy in flight on an
+// error return.
+struct StreamDrain {
+  hipStream_t s;
+  ~StreamDrain() { (void)hipStreamSynchronize(s); }
+};
+
+struct DevLaps {
+  double frame = 0, text_upload = 0, count = 0, host_parse = 0, decode = 0, runs_download = 0;
+  double upload = 0, build = 0, probe = 0, download = 0, map = 0;
+};
+
+// One attempt of cir_block_sources with the texts parsed on the device.
+// force_host[k]: text k (nsrc = the new index) goes through the host parser.
+// Returns kRetry, with more force_host flags set, when a token turned out bad
+// in the decode pass: by then the pool's layout rested on that text's counts.
+// The counts of the count pass are provisional until the decode pass has given
+// its verdicts, so nothing is reported from them alone: a call they would end
+// without a decode pass -- a new index without blocks, a pool or a need list
+// past its limit -- returns kHostFlow and is decided by the host parser.
+// No text is kept from the device for being small: one source of n blocks
+// against n, whole call, device parse against CIR_SOURCES_PARSE=host
+// (profiles/index_digests/bench.json, size_sweep): n = 500 (33 KB per text)
+// 0.22-0.25 ms against 0.18-0.33 ms, a tie; 2,000 0.25-0.29 against 0.64-0.75;
+// 512,000 6.8-6.9 against 132-138.  No size was found at which the host wins.
+int sources_dev_attempt(cir_ctx* ctx, std::vector<Text>& tx, size_t nsrc,
+                        std::vector<uint8_t>& force_host, const uint64_t* want,
+                        uint32_t** src_out, uint64_t** src_file_out, uint64_t** src_block_out,
+                        uint64_t* nblk_out, size_t* nskipped_out, uint64_t* stats, bool trace,
+                        DevLaps* laps) {
+  Text& nw = tx[nsrc];
+  const auto t0 = Clock::now();
+  auto host_parse = [&](Text& t) {  // (once per text: a second attempt keeps the first's)
+    if (t.host_done) return;
+    t.host_ok = t.p && dirsig::parse(t.p, t.len, &t.parsed, &t.err);
+    t.host_done = true;
+  };
+  auto want_dev = [&](size_t k) {
+    const Text& t = tx[k];
+    return t.framed && !force_host[k] && t.len <= dev::kIdxMaxLen &&
+           t.len / idxscan::kTokenBytes <= 0xFFFFFFFFull;
+  };
+  // the new index first: its header decides which sources take part
+  nw.dev = want_dev(nsrc);
+  if (!nw.dev) {
+    host_parse(nw);
+    if (!nw.host_ok) return parse_fail(nw.parsed.bad_hash_size, nw.err);
+    nw.h = nw.parsed.header;
+  }
+  std::vector<size_t> on_host, on_dev;
+  if (nw.dev) on_dev.push_back(nsrc);
+  for (size_t j = 0; j < nsrc; ++j) {
+    Text& t = tx[j];
+    t.candidate = t.framed && t.h.hash == nw.h.hash && t.h.block_size == nw.h.block_size;
+    t.dev = t.candidate && want_dev(j);
+    t.usable = false;
+    if (t.dev)
+      on_dev.push_back(j);
+    else if (t.candidate)
+      on_host.push_back(j);
+  }
+  if (nsrc > 0xFFFFFFFEull) return fail(CIR_EINVAL, "too many sources");
+  const uint64_t bs = nw.h.block_size;
+  // the host's share first: the device's lock is not held across a host parse
+  const auto th0 = Clock::now();
+  fan_out(on_host.size(), [&](size_t i) { host_parse(tx[on_host[i]]); });
+  const double host_first_ms = ms_between(th0, Clock::now());
+
+  Device& d = *ctx->devs[0];
+  std::unique_lock<std::mutex> lk(d.mu);
+  DeviceGuard guard;
+  CIR_HIP(hipSetDevice(d.id));
+  hipStream_t s = d.compute;
+  DevSet b;
+  // the texts, their scratch, result words and run tables
+  uint64_t text_bytes = 0, work_bytes = 0, run_recs = 0;
+  for (size_t k : on_dev) {
+    Text& t = tx[k];
+    t.text_off = text_bytes;
+    t.work_off = work_bytes;
+    t.runs_off = run_recs;
+    text_bytes += (t.len + 15) & ~(uint64_t)15;
+    work_bytes += dev::idx_work_bytes(t.len);
+    run_recs += t.len / idxscan::kMinRunLine;
+  }
+  uint8_t* d_text = nullptr;
+  uint8_t* d_work = nullptr;
+  uint64_t* d_res = nullptr;
+  uint64_t* d_runs = nullptr;
+  std::vector<uint64_t> h_res(CIR_INDEX_RES_FIELDS * on_dev.size() + 1);
+  StreamDrain drain{s};
+  if (!on_dev.empty()) {
+    int rc;
+    if ((rc = b.alloc((void**)&d_text, text_bytes)) || (rc = b.alloc((void**)&d_work, work_bytes)) ||
+        (rc = b.alloc((void**)&d_res, sizeof(uint64_t) * CIR_INDEX_RES_FIELDS * on_dev.size())) ||
+        (rc = b.alloc((void**)&d_runs, 32 * run_recs)))
+      return rc;
+  }
+  const auto t1 = Clock::now();
+  for (size_t k : on_dev)
+    CIR_HIP(hipMemcpyAsync(d_text + tx[k].text_off, tx[k].p, tx[k].len, hipMemcpyHostToDevice, s));
+  if (trace) CIR_HIP(hipStreamSynchronize(s));
+  const auto t2 = Clock::now();
+  for (size_t i = 0; i < on_dev.size(); ++i) {
+    const Text& t = tx[on_dev[i]];
+    CIR_HIP(dev::launch_index_count(d_text + t.text_off, t.len, t.body_off, t.body_end, bs,
+                                    t.len / idxscan::kTokenBytes, t.len / idxscan::kMinRunLine,
+                                    (uint64_t*)(d_work + t.work_off),
+                                    d_res + CIR_INDEX_RES_FIELDS * i, s));
+  }
+  if (!on_dev.empty())
+    CIR_HIP(hipMemcpyAsync(h_res.data(), d_res,
+                           sizeof(uint64_t) * CIR_INDEX_RES_FIELDS * on_dev.size(),
+                           hipMemcpyDeviceToHost, s));
+  CIR_HIP(hipStreamSynchronize(s));
+  const auto t5 = Clock::now();
+  // what the count pass declined takes the host parser, that text alone
+  std::vector<size_t> declined;
+  for (size_t i = 0; i < on_dev.size(); ++i) {
+    Text& t = tx[on_dev[i]];
+    memcpy(t.res, h_res.data() + CIR_INDEX_RES_FIELDS * i, sizeof t.res);
+    if (t.res[0] != CIR_INDEX_OK) {
+      t.dev = false;
+      force_host[on_dev[i]] = 1;
+      declined.push_back(on_dev[i]);
+    } else {
+      t.usable = true;
+      t.nblk = t.res[3];
+    }
+  }
+  if (!declined.empty()) {  // (the stream is idle and the buffers are this call's own)
+    lk.unlock();
+    fan_out(declined.size(), [&](size_t i) { host_parse(tx[declined[i]]); });
+    lk.lock();
+  }
+  if (!nw.dev) {
+    if (!nw.host_ok) return parse_fail(nw.parsed.bad_hash_size, nw.err);
+    nw.usable = true;  // (its header is the frame's: both read it by the same rules)
+    nw.nblk = sources::count_blocks(nw.parsed);
+  }
+  for (size_t j = 0; j < nsrc; ++j) {
+    Text& t = tx[j];
+    if (t.dev || !t.candidate) continue;
+    t.usable = t.host_ok && t.parsed.header.hash == nw.h.hash &&
+               t.parsed.header.block_size == nw.h.block_size;
+    t.nblk = t.usable ? sources::count_blocks(t.parsed) : 0;
+  }
+  const auto t6 = Clock::now();
+  size_t used = 0;
+  uint64_t n_pool = 0;
+  for (size_t j = 0; j < nsrc; ++j)
+    if (tx[j].usable) {
+      ++used;
+      n_pool += tx[j].nblk;
+    }
+  const uint64_t n_need = nw.nblk;
+  // (a source's count may still fall to a bad token: the host parser decides
+  // what ends here, before any join, exactly as without the device parse)
+  if (n_need == 0 || n_need > 0xFFFFFFFFull || !sources::pool_count_ok(n_pool)) return kHostFlow;
+  // the join's buffers; the digests are decoded, or uploaded, straight into them
+  const uint64_t slots = dev::join_table_slots(n_pool);
+  uint8_t* d_need = nullptr;
+  uint8_t* d_pool = nullptr;
+  uint32_t* d_table = nullptr;
+  uint32_t* d_match = nullptr;
+  {
+    int rc;
+    if ((rc = b.alloc((void**)&d_need, 32 * n_need)) || (rc = b.alloc((void**)&d_pool, 32 * n_pool)) ||
+        (rc = b.alloc((void**)&d_table, slots * sizeof(uint32_t))) ||
+        (rc = b.alloc((void**)&d_match, (n_need + 4) * sizeof(uint32_t))))
+      return rc;
+  }
+  if (trace)
+    for (hipEvent_t& e : b.ev) CIR_HIP(hipEventCreate(&e));
+  uint64_t at = 0;  // pool ordinal of the next source's block 0
+  double upload_ms = 0;
+  for (size_t k = 0; k <= nsrc; ++k) {
+    const size_t j = k == 0 ? nsrc : k - 1;  // the new index, then the sources in order
+    Text& t = tx[j];
+    if (!t.usable) continue;
+    uint8_t* dst = j == nsrc ? d_need : d_pool + 32 * at;
+    if (t.dev) {
+      const size_t i = std::find(on_dev.begin(), on_dev.end(), j) - on_dev.begin();
+      CIR_HIP(dev::launch_index_emit(d_text + t.text_off, t.len, t.body_off, t.body_end, bs, dst,
+                                     t.nblk, d_runs + 4 * t.runs_off,
+                                     t.len / idxscan::kMinRunLine,
+                                     (uint64_t*)(d_work + t.work_off),
+                                     d_res + CIR_INDEX_RES_FIELDS * i, s));
+    } else if (t.nblk) {
+      const auto u0 = Clock::now();
+      t.digests.resize(32 * t.nblk);
+      sources::copy_digests(t.parsed, t.digests.data());
+      CIR_HIP(hipMemcpyAsync(dst, t.digests.data(), 32 * t.nblk, hipMemcpyHostToDevice, s));
+      upload_ms += ms_between(u0, Clock::now());
+    }
+    if (j != nsrc) at += t.nblk;
+  }
+  if (trace) CIR_HIP(hipStreamSynchronize(s));
+  const auto t7 = Clock::now();
+  // the verdicts again (a bad token shows only now) and the run tables
+  if (!on_dev.empty())
+    CIR_HIP(hipMemcpyAsync(h_res.data(), d_res,
+                           sizeof(uint64_t) * CIR_INDEX_RES_FIELDS * on_dev.size(),
+                           hipMemcpyDeviceToHost, s));
+  for (size_t k : on_dev) {
+    Text& t = tx[k];
+    if (!t.dev) continue;
+    t.runs.resize(t.res[2]);
+    if (t.res[2])
+      CIR_HIP(hipMemcpyAsync(t.runs.data(), d_runs + 4 * t.runs_off, 32 * t.res[2],
+                             hipMemcpyDeviceToHost, s));
+  }
+  CIR_HIP(hipStreamSynchronize(s));
+  const auto t8 = Clock::now();
+  bool again = false;
+  for (size_t i = 0; i < on_dev.size(); ++i)
+    if (tx[on_dev[i]].dev && h_res[CIR_INDEX_RES_FIELDS * i] != CIR_INDEX_OK) {
+      force_host[on_dev[i]] = 1;
+      again = true;
+    }
+  if (again) return kRetry;
+  // every verdict is in: the counts are the host parser's
+  if (nskipped_out) *nskipped_out = nsrc - used;
+  stats[3] = n_pool;
+  stats[4] = used;
+  stats[7] = 1;
+  // the block lists, from the run tables
+  sources::BlockList need, pool;
+  for (size_t k = 0; k <= nsrc; ++k) {
+    const size_t j = k == 0 ? nsrc : k - 1;
+    Text& t = tx[j];
+    if (!t.usable) continue;
+    sources::BlockList* list = j == nsrc ? &need : &pool;
+    const uint32_t src = j == nsrc ? 0 : (uint32_t)j;
+    if (t.dev) {
+      for (const idxscan::Run& r : t.runs)
+        list->runs.push_back(sources::FileRun{list->n + r.first, r.size, r.file, src});
+      list->n += t.nblk;
+    } else {
+      sources::append_runs(t.parsed, src, list);
+      t.parsed = dirsig::Index();
+      t.digests = std::vector<uint8_t>();
+    }
+  }
+  std::vector<uint32_t> match(n_need);
+  uint32_t* so = (uint32_t*)malloc(n_need * sizeof(uint32_t));
+  uint64_t* fo = (uint64_t*)malloc(n_need * sizeof(uint64_t));
+  uint64_t* bo = (uint64_t*)malloc(n_need * sizeof(uint64_t));
+  auto drop = [&](int rc) {
+    free(so);
+    free(fo);
+    free(bo);
+    return rc;
+  };
+  if (!so || !fo || !bo) return drop(fail(CIR_ENOMEM, "malloc"));
+  hipError_t e = dev::launch_join(d_need, n_need, d_pool, n_pool, d_table, slots, draw_seed(),
+                                  d_match, d_match + n_need, s, trace ? b.ev : nullptr);
+  if (e != hipSuccess) return drop(hip_fail(e, "launch_join"));
+  if (trace && (e = hipStreamSynchronize(s)) != hipSuccess) return drop(hip_fail(e, "join"));
+  const auto t9 = Clock::now();
+  if ((e = hipMemcpyAsync(match.data(), d_match, n_need * sizeof(uint32_t), hipMemcpyDeviceToHost,
+                          s)) != hipSuccess ||
+      (e = hipStreamSynchronize(s)) != hipSuccess)
+    return drop(hip_fail(e, "download of the matches"));
+  const auto t10 = Clock::now();
+  stats[6] = slots;
+  const sources::MapStats ms =
+      sources::map_matches(need, pool, bs, want, match.data(), so, fo, bo);
+  stats[0] = ms.wanted;
+  stats[1] = ms.found;
+  stats[2] = ms.bytes;
+  stats[5] = ms.dropped;
+  *src_out = so;
+  *src_file_out = fo;
+  *src_block_out = bo;
+  *nblk_out = n_need;
+  if (trace) {
+    float f = 0;
+    if (hipEventElapsedTime(&f, b.ev[0], b.ev[1]) == hipSuccess) laps->build = f;
+    if (hipEventElapsedTime(&f, b.ev[1], b.ev[2]) == hipSuccess) laps->probe = f;
+    laps->frame += ms_between(t0, t1);  // (with the host's share and the buffers' hipMalloc)
+    laps->text_upload += ms_between(t1, t2);
+    laps->count += ms_between(t2, t5);
+    laps->host_parse += host_first_ms + ms_between(t5, t6);
+    laps->decode += ms_between(t6, t7) - upload_ms;
+    laps->upload += upload_ms;
+    laps->runs_download += ms_between(t7, t8);
+    laps->download = ms_between(t9, t10);
+    laps->map = ms_between(t10, Clock::now());
+    fprintf(stderr,
+            "cir block_sources: %llu blocks against %llu pool blocks of %zu source(s), device; "
+            "parse %.2f ms, pool %.2f ms, upload %.2f ms, build kernel %.3f ms, probe kernel "
+            "%.3f ms, download %.2f ms, map %.2f ms; device parse of %zu text(s): frame %.2f ms, "
+            "text upload %.2f ms, count kernels %.2f ms, host parse %.2f ms, decode kernels "
+            "%.2f ms, runs download %.2f ms\n",
+            (unsigned long long)n_need, (unsigned long long)n_pool, used, ms_between(t0, t8), 0.0,
+            laps->upload, laps->build, laps->probe, laps->download, laps->map, on_dev.size(),
+            laps->frame, laps->text_upload, laps->count, laps->host_parse, laps->decode,
+            laps->runs_download);
+  }
+  return CIR_OK;
+}
+
+// cir_block_sources with a context: the texts are framed on the host and
+// their bodies parsed on the device, straight into the join's buffers.
+int block_sources_dev(cir_ctx* ctx, const uint8_t* index, size_t len,
+                      const uint8_t* const* src_index, const size_t* src_len, size_t nsrc,
+                      const uint64_t* want, uint32_t** src_out, uint64_t** src_file_out,
+                      uint64_t** src_block_out, uint64_t* nblk_out, size_t* nskipped_out,
+                      uint64_t* stats, bool trace) {
+  std::vector<Text> tx(nsrc + 1);
+  for (size_t k = 0; k <= nsrc; ++k) {
+    Text& t = tx[k];
+    t.p = k == nsrc ? index : src_index[k];
+    t.len = k == nsrc ? len : src_len[k];
+    std::string err;
+    t.framed = t.p && dirsig::frame(t.p, t.len, &t.h, &t.body_off, &t.body_end, &err);
+  }
+  std::vector<uint8_t> force_host(nsrc + 1, 0);
+  DevLaps laps;
+  for (;;) {  // (again only after a bad token: at most once per text)
+    const int rc = sources_dev_attempt(ctx, tx, nsrc, force_host, want, src_out, src_file_out,
+                                       src_block_out, nblk_out, nskipped_out, stats, trace, &laps);
+    if (rc != kRetry) return rc;
+  }
+}
+
 int block_sources_impl(cir_ctx* ctx, const uint8_t* index, size_t len,
                        const uint8_t* const* src_index, const size_t* src_len, size_t nsrc,
                        const uint64_t* want, uint32_t** src_out, uint64_t** src_file_out,
@@ -143,6 +527,12 @@ int block_sources_impl(cir_ctx* ctx, const uint8_t* index, size_t len,
   if (nskipped_out) *nskipped_out = 0;
   for (int i = 0; i < CIR_SOURCES_STATS_FIELDS; ++i) stats[i] = 0;
   const bool trace = trace_enabled();
+  if (ctx && !parse_on_host()) {
+    const int rc = block_sources_dev(ctx, index, len, src_index, src_len, nsrc, want, src_out,
+                                     src_file_out, src_block_out, nblk_out, nskipped_out, stats,
+                                     trace);
+    if (rc != kHostFlow) return rc;  // (nothing was reported yet)
+  }
   const auto t0 = Clock::now();
   // the new index and the sources, parsed in parallel; a source that does
   // not parse or has another hash type or block size takes no part
@@ -159,9 +549,7 @@ int block_sources_impl(cir_ctx* ctx, const uint8_t* index, size_t len,
     std::string serr;
     usable[k] = src_index[k] && dirsig::parse(src_index[k], src_len[k], &parsed[k], &serr);
   });
-  if (!index_ok)
-    return idx.bad_hash_size ? fail(CIR_EHASHSIZE, "hash size is unsupported: " + err)
-                             : fail(CIR_EPARSE, "error parsing index: " + err);
+  if (!index_ok) return parse_fail(idx.bad_hash_size, err);
   for (size_t j = 0; j < nsrc; ++j)
     usable[j] = usable[j] && parsed[j].header.hash == idx.header.hash &&
                 parsed[j].header.block_size == idx.header.block_size;

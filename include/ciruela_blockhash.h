@@ -41,6 +41,9 @@
  *                              sooner);
  *       CIR_FOOTER=gpu         cir_init's contexts start with CIR_FOOTER_GPU;
  *       CIR_TRACE=1            per-batch timings on stderr;
+ *       CIR_SOURCES_PARSE=host cir_block_sources with a context parses the index
+ *                              texts on the host, as before the device parse
+ *                              (cir_index_digests_dev) existed (A/B measurement);
  *       CIR_DEBUG_SPLIT=k      (tests) every opened GPU appears k times.
  *       CIR_DEBUG_STRIPE_BLOCKS=n  (tests) a scan over several devices deals
  *                              stripes of n blocks (default: one staging
@@ -598,14 +601,26 @@ int cir_match_digests_dev(cir_ctx* ctx, const uint8_t* d_need, size_t n_need,
  * of the last two are UINT64_MAX.  The arrays are malloc'd (cir_free), *nblk_out long, and
  * NULL when *nblk_out == 0.
  *
+ * With ctx == NULL the rule is applied on the host with a hash map in which the first entry
+ * wins, and no GPU is needed.
+ *
  * With a context the join runs on the context's first device (cir_match_digests_dev's kernels;
  * device buffers are allocated for the call and freed after it, the seed is drawn per call, the
- * current device is restored); with ctx == NULL the same rule is applied on the host with a
- * hash map in which the first entry wins, and no GPU is needed.  Both give identical arrays.
+ * current device is restored).  So does the parse of the texts: every text is framed on the
+ * host (cir_index_frame's rules), uploaded, and its body decoded by cir_index_digests_dev's
+ * kernels straight into the join's buffers; only the run tables (32 bytes per non-empty file)
+ * come back.  A text the device declines takes the host parser, that text alone, and a call
+ * that ends before any join (a new index without blocks, a list past its limit) is decided by
+ * the host parser altogether.  Which sources are skipped, the stats, and the error code and
+ * text of a new index that does not parse are therefore the host parser's.  The device's lock
+ * is not held while a text is parsed on the host.  CIR_SOURCES_PARSE=host keeps every text on
+ * the host.
+ *
+ * Both give identical arrays, skip counts and stats ([6] and [7] aside).
  *
  * CIR_EINVAL: null arguments, or more than 2^31 - 1 pool blocks in total (pass fewer sources);
  * CIR_EPARSE / CIR_EHASHSIZE: `index` does not parse; CIR_ENOMEM.  All are decided before any
- * device work.
+ * join.
  *
  * stats: [0] blocks wanted, [1] blocks found, [2] bytes found locally, [3] pool blocks, [4]
  * sources used, [5] matches dropped because the lengths differ, [6] table slots (0 on the
@@ -617,6 +632,88 @@ int cir_block_sources(cir_ctx* ctx, const uint8_t* index, size_t len,
                       uint32_t** src_out, uint64_t** src_file_out, uint64_t** src_block_out,
                       uint64_t* nblk_out, size_t* nskipped_out,
                       uint64_t stats[CIR_SOURCES_STATS_FIELDS]);
+
+/* ---- an index's digests as an array ----------------------------------- */
+
+/* The frame of a DIRSIGNATURE.v1 index without its body.  Pure host code, no HIP call: the
+ * index parser's rules for the line structure (the text ends in '\n' and has at least two
+ * lines), the header line ("DIRSIGNATURE.v1", the hash type, an optional block_size=N, default
+ * 32768) and the footer line (non-empty hex), with that parser's error texts.  *hash_type =
+ * CIR_HASH_*, *block_size, and the body as the bytes [*body_off, *body_end) of `index`: behind
+ * the header line, before the footer line; empty, or ending in '\n'.  CIR_EINVAL: a null
+ * pointer; CIR_EPARSE as the parser would. */
+int cir_index_frame(const uint8_t* index, size_t len, int* hash_type, uint64_t* block_size,
+                    uint64_t* body_off, uint64_t* body_end);
+
+/* Bytes of device scratch cir_index_digests_dev needs for a text of len bytes.  Pure. */
+uint64_t cir_index_work_bytes(uint64_t len);
+
+/* Bytes of text per workgroup of cir_index_digests_dev's count and emit passes (4096: tests
+ * place line starts, heads and tokens across this boundary). */
+uint64_t cir_debug_index_tile_bytes(void);
+
+/* The block digests of an index, parsed on the device: index text in (d_text, len bytes, the
+ * body at [body_off, body_end) as cir_index_frame gives it), the digests of its file entries out
+ * as one flat list -- d_digests, 32 bytes per block, in index order, blocks ascending: the global
+ * block numbering of cir_check_blocks and the need list of cir_block_sources, ready for
+ * cir_match_digests_dev -- and one run record of four u64 per non-empty file in d_runs:
+ * {first, size, file, hash_off} = the global block number of its block 0, the entry's size, its
+ * file ordinal (file entries only, as in cir_link_candidates) and the offset in the text of its
+ * first hash token's leading space.  The reference has no counterpart: every consumer there
+ * parses the text on a host thread.
+ *
+ * The device takes a canonical subset of what the host parser accepts (ciruela_amd/csrc/
+ * idxscan.hpp states it: one space between tokens, no raw byte outside 0x21..0x7e, \xNN escapes
+ * that form no ".", ".." or "/", directory lines and entry heads of at most 4096 bytes, exactly
+ * ceil(size / block_size) tokens of one space and 64 hex digits) and declines everything else;
+ * it never guesses.  Status CIR_INDEX_OK means the host parser accepts the same bytes and gives
+ * the same file count, runs and digests.  A declined text goes to the host parser (cir_index_digests
+ * does that), which alone decides between success, CIR_EPARSE and CIR_EHASHSIZE.
+ *
+ * d_res (device, CIR_INDEX_RES_FIELDS u64): [0] CIR_INDEX_OK, CIR_INDEX_CAPACITY or
+ * CIR_INDEX_DECLINED, [1] file entries, [2] runs, [3] blocks, [4] the offset of the first
+ * declined line's start, or UINT64_MAX.  On CIR_INDEX_OK d_digests[0 .. 32 x [3]) and d_runs[0 ..
+ * 4 x [2]) are written.  On CIR_INDEX_CAPACITY ([3] > cap_blocks or [2] > cap_runs) the counts are
+ * exact and neither array is written; on CIR_INDEX_DECLINED the counts and the arrays mean
+ * nothing.  cap_blocks = len / 65 and cap_runs = len / 73 always suffice for a text the host
+ * parser accepts (a token is 65 bytes, the shortest line with a token 73), so a caller can
+ * allocate without a round trip; with those caps CIR_INDEX_CAPACITY is a text the host parser
+ * rejects.  Nothing is written past cap_blocks digests, cap_runs records, d_work[work_bytes) or
+ * d_res[5), and every d_res word is written by the call.
+ *
+ * Like every *_dev call it allocates nothing, synchronises nothing and runs on `stream` alone
+ * (four launches: count, scan, emit, decode; no workgroup waits for another, and no atomic is
+ * issued unless a line is declined); ctx may be NULL and is not used.
+ *
+ * CIR_EINVAL: a null d_text (with len > 0), d_digests (with cap_blocks > 0), d_runs (with cap_runs
+ * > 0), d_work or d_res; d_digests not 16-byte aligned; d_text, d_runs, d_work or d_res not
+ * 8-byte aligned; body_off > body_end; body_end > len; block_size == 0; work_bytes <
+ * cir_index_work_bytes(len); cap_blocks > 2^32 - 1; len > 2^36. */
+#define CIR_INDEX_RES_FIELDS 5
+#define CIR_INDEX_OK 0
+#define CIR_INDEX_CAPACITY 1
+#define CIR_INDEX_DECLINED 2
+int cir_index_digests_dev(cir_ctx* ctx, const uint8_t* d_text, uint64_t len, uint64_t body_off,
+                          uint64_t body_end, uint64_t block_size, uint8_t* d_digests,
+                          uint64_t cap_blocks, uint64_t* d_runs, uint64_t cap_runs, void* d_work,
+                          uint64_t work_bytes, uint64_t* d_res, void* stream);
+
+/* The host form: `index` in host memory to malloc'd arrays (cir_free; NULL when empty):
+ * *digests_out = 32 x *nblk_out bytes, *runs_out = 4 x *nruns_out u64 as above, *nfiles_out =
+ * the file entries; *hash_type = CIR_HASH_* and *block_size from the header.  With a context:
+ * cir_index_frame, one upload, cir_index_digests_dev's kernels on the context's first device,
+ * one download; a text the device declines (or whose frame does not parse) takes the host parser
+ * instead; the current device is restored.  With ctx == NULL: the host parser alone, and no GPU
+ * is needed.  Both give identical arrays and identical error codes (CIR_EPARSE, CIR_EHASHSIZE:
+ * the index does not parse; CIR_EINVAL: a null pointer; CIR_ENOMEM).
+ *
+ * stats: [0] 1 if the device parsed it, [1] 1 if the device declined and the host parsed, [2] the
+ * declined line's offset (UINT64_MAX when none was reported), [3] text bytes uploaded. */
+#define CIR_INDEX_STATS_FIELDS 4
+int cir_index_digests(cir_ctx* ctx, const uint8_t* index, size_t len, int* hash_type,
+                      uint64_t* block_size, uint8_t** digests_out, uint64_t* nblk_out,
+                      uint64_t** runs_out, size_t* nruns_out, size_t* nfiles_out,
+                      uint64_t stats[CIR_INDEX_STATS_FIELDS]);
 
 /* ---- index (DIRSIGNATURE.v1) ----------------------------------------- */
 
