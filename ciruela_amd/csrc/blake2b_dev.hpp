@@ -94,28 +94,42 @@ __device__ __forceinline__ uint64_t rotr_lh(uint32_t l, uint32_t h) {
   P##3 = rotr_lh<N>(tl3, th3);
 #define CIR_ADD4(P, Q) P##0 = P##0 + (Q##0); P##1 = P##1 + (Q##1); P##2 = P##2 + (Q##2); P##3 = P##3 + (Q##3);
 
+struct NoHook {
+  __device__ __forceinline__ void operator()() const {}
+};
+
 // 4 independent G: (a_k, b_k, c_k, d_k) with messages x_k, y_k.
+// fast() runs at the entry of each of the four fast groups (a policy; NoHook
+// adds nothing).  k_chunks passes a workgroup barrier: a SIMD issues the xors
+// at 2 cycles only while every wave it holds offers one, so its waves enter
+// each fast group together (uniform.hpp PhaseBarrier).
+template <typename Fast = NoHook>
 __device__ __forceinline__ void g4(uint64_t& a0, uint64_t& a1, uint64_t& a2, uint64_t& a3,
                                    uint64_t& b0, uint64_t& b1, uint64_t& b2, uint64_t& b3,
                                    uint64_t& c0, uint64_t& c1, uint64_t& c2, uint64_t& c3,
                                    uint64_t& d0, uint64_t& d1, uint64_t& d2, uint64_t& d3,
                                    uint64_t x0, uint64_t x1, uint64_t x2, uint64_t x3,
-                                   uint64_t y0, uint64_t y1, uint64_t y2, uint64_t y3) {
+                                   uint64_t y0, uint64_t y1, uint64_t y2, uint64_t y3,
+                                   Fast fast = Fast()) {
   uint32_t tl0, tl1, tl2, tl3, th0, th1, th2, th3;
   CIR_ADD4(a, x) CIR_ADD4(a, b)            // slow
   sched_fence();
+  fast();
   CIR_XOR4(d, a) CIR_ROT4(d, 32)          // fast (rotr 32 is a register swap)
   sched_fence();
   CIR_ADD4(c, d)                          // slow
   sched_fence();
+  fast();
   CIR_XOR4(b, c)                          // fast
   sched_fence();
   CIR_ROT4(b, 24) CIR_ADD4(a, y) CIR_ADD4(a, b)  // slow
   sched_fence();
+  fast();
   CIR_XOR4(d, a)                          // fast
   sched_fence();
   CIR_ROT4(d, 16) CIR_ADD4(c, d)          // slow
   sched_fence();
+  fast();
   CIR_XOR4(b, c)                          // fast
   sched_fence();
   CIR_ROT4(b, 63)                         // slow (runs on into the next g4's adds)
@@ -126,24 +140,28 @@ __device__ __forceinline__ void g4(uint64_t& a0, uint64_t& a1, uint64_t& a2, uin
      m[s6], m[s1], m[s3], m[s5], m[s7]);                                                       \
   g4(v0, v1, v2, v3, v5, v6, v7, v4, v10, v11, v8, v9, v15, v12, v13, v14, m[s8], m[s10],       \
      m[s12], m[s14], m[s9], m[s11], m[s13], m[s15]);
-
-struct NoHook {
-  __device__ __forceinline__ void operator()() const {}
-};
+// The same round with a fast-group policy F (compress_sm).
+#define CIR_ROUND_SM_F(F, s0, s1, s2, s3, s4, s5, s6, s7, s8, s9, s10, s11, s12, s13, s14, s15) \
+  g4(v0, v1, v2, v3, v4, v5, v6, v7, v8, v9, v10, v11, v12, v13, v14, v15, m[s0], m[s2], m[s4], \
+     m[s6], m[s1], m[s3], m[s5], m[s7], F);                                                    \
+  g4(v0, v1, v2, v3, v5, v6, v7, v4, v10, v11, v8, v9, v15, v12, v13, v14, m[s8], m[s10],       \
+     m[s12], m[s14], m[s9], m[s11], m[s13], m[s15], F);
 
 // after_col0() runs between round 0's column step (message words 0-7) and
 // its diagonal step (words 8-15): a loader can leave the second half of the
 // line's LDS reads in flight under the first G step.
-template <typename Hook = NoHook>
+// fast() runs at the entry of every fast group (g4).
+template <typename Hook = NoHook, typename Fast = NoHook>
 __device__ __forceinline__ void compress_sm(uint64_t h[8], const uint64_t m[16], uint64_t t,
-                                            bool last, Hook after_col0 = Hook()) {
+                                            bool last, Hook after_col0 = Hook(),
+                                            Fast fast = Fast()) {
   uint64_t v0 = h[0], v1 = h[1], v2 = h[2], v3 = h[3];
   uint64_t v4 = h[4], v5 = h[5], v6 = h[6], v7 = h[7];
   uint64_t v8 = CIR_IV0, v9 = CIR_IV1, v10 = CIR_IV2, v11 = CIR_IV3;
   uint64_t v12 = CIR_IV4 ^ t, v13 = CIR_IV5;
   uint64_t v14 = last ? ~CIR_IV6 : CIR_IV6, v15 = CIR_IV7;
   g4(v0, v1, v2, v3, v4, v5, v6, v7, v8, v9, v10, v11, v12, v13, v14, v15, m[0], m[2], m[4],
-     m[6], m[1], m[3], m[5], m[7]);
+     m[6], m[1], m[3], m[5], m[7], fast);
   if constexpr (!std::is_same_v<Hook, NoHook>) {
     // the column step's results are materialised here, so the compiler
     // cannot sink it past the hook's wait and branch
@@ -156,18 +174,18 @@ __device__ __forceinline__ void compress_sm(uint64_t h[8], const uint64_t m[16],
     sched_fence();
   }
   g4(v0, v1, v2, v3, v5, v6, v7, v4, v10, v11, v8, v9, v15, v12, v13, v14, m[8], m[10],
-     m[12], m[14], m[9], m[11], m[13], m[15]);
-  CIR_ROUND_SM(14, 10, 4, 8, 9, 15, 13, 6, 1, 12, 0, 2, 11, 7, 5, 3)
-  CIR_ROUND_SM(11, 8, 12, 0, 5, 2, 15, 13, 10, 14, 3, 6, 7, 1, 9, 4)
-  CIR_ROUND_SM(7, 9, 3, 1, 13, 12, 11, 14, 2, 6, 5, 10, 4, 0, 15, 8)
-  CIR_ROUND_SM(9, 0, 5, 7, 2, 4, 10, 15, 14, 1, 11, 12, 6, 8, 3, 13)
-  CIR_ROUND_SM(2, 12, 6, 10, 0, 11, 8, 3, 4, 13, 7, 5, 15, 14, 1, 9)
-  CIR_ROUND_SM(12, 5, 1, 15, 14, 13, 4, 10, 0, 7, 6, 3, 9, 2, 8, 11)
-  CIR_ROUND_SM(13, 11, 7, 14, 12, 1, 3, 9, 5, 0, 15, 4, 8, 6, 2, 10)
-  CIR_ROUND_SM(6, 15, 14, 9, 11, 3, 0, 8, 12, 2, 13, 7, 1, 4, 10, 5)
-  CIR_ROUND_SM(10, 2, 8, 4, 7, 6, 1, 5, 15, 11, 9, 14, 3, 12, 13, 0)
-  CIR_ROUND_SM(0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13, 14, 15)
-  CIR_ROUND_SM(14, 10, 4, 8, 9, 15, 13, 6, 1, 12, 0, 2, 11, 7, 5, 3)
+     m[12], m[14], m[9], m[11], m[13], m[15], fast);
+  CIR_ROUND_SM_F(fast, 14, 10, 4, 8, 9, 15, 13, 6, 1, 12, 0, 2, 11, 7, 5, 3)
+  CIR_ROUND_SM_F(fast, 11, 8, 12, 0, 5, 2, 15, 13, 10, 14, 3, 6, 7, 1, 9, 4)
+  CIR_ROUND_SM_F(fast, 7, 9, 3, 1, 13, 12, 11, 14, 2, 6, 5, 10, 4, 0, 15, 8)
+  CIR_ROUND_SM_F(fast, 9, 0, 5, 7, 2, 4, 10, 15, 14, 1, 11, 12, 6, 8, 3, 13)
+  CIR_ROUND_SM_F(fast, 2, 12, 6, 10, 0, 11, 8, 3, 4, 13, 7, 5, 15, 14, 1, 9)
+  CIR_ROUND_SM_F(fast, 12, 5, 1, 15, 14, 13, 4, 10, 0, 7, 6, 3, 9, 2, 8, 11)
+  CIR_ROUND_SM_F(fast, 13, 11, 7, 14, 12, 1, 3, 9, 5, 0, 15, 4, 8, 6, 2, 10)
+  CIR_ROUND_SM_F(fast, 6, 15, 14, 9, 11, 3, 0, 8, 12, 2, 13, 7, 1, 4, 10, 5)
+  CIR_ROUND_SM_F(fast, 10, 2, 8, 4, 7, 6, 1, 5, 15, 11, 9, 14, 3, 12, 13, 0)
+  CIR_ROUND_SM_F(fast, 0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13, 14, 15)
+  CIR_ROUND_SM_F(fast, 14, 10, 4, 8, 9, 15, 13, 6, 1, 12, 0, 2, 11, 7, 5, 3)
   sched_fence();
   h[0] = xor3(h[0], v0, v8);
   h[1] = xor3(h[1], v1, v9);

@@ -64,15 +64,55 @@ __global__ __launch_bounds__(kThreads, 5) void k_uniform_glds(const uint8_t* __r
 // and when ngen_wg == 1 the short last block (block nfull) on one lane of
 // workgroup 0 with vector loads (hash_chain_al16).  With a context the short
 // block runs in quad mode on another stream instead (launch_chunks_split).
-// 4 waves per SIMD (128-VGPR budget; 107 VGPRs, no spills): at 5 (96 VGPRs)
+// 4 waves per SIMD (128-VGPR budget, no spills): at 5 (96 VGPRs)
 // the ragged branch spilled 6 VGPRs to scratch.  4 and 5 waves run config 2
 // within 0.2 % of each other (profiles/r02/ablib_occ4_vs_occ5.log): the body
 // is issue-bound.
-__global__ __launch_bounds__(kThreads, 4) void k_chunks(const uint8_t* __restrict__ data,
-                                                         uint64_t nbytes, uint64_t bs,
-                                                         uint32_t lines, uint64_t nfull,
-                                                         uint32_t ngen_wg,
-                                                         uint8_t* __restrict__ out) {
+// Workgroups of kChunkThreads (8 waves, two per SIMD) whose waves enter every
+// fast group of the compression through one barrier (PhaseBarrier).  The
+// barriers are met by construction: the ragged workgroup leaves before the
+// first one, all threads together; every wave of every other workgroup runs
+// `lines` compressions -- a wave past the file's last whole block hashes a
+// duplicate of that block and stores nothing.
+__global__ __launch_bounds__(kChunkThreads, 4) void k_chunks(const uint8_t* __restrict__ data,
+                                                              uint64_t nbytes, uint64_t bs,
+                                                              uint32_t lines, uint64_t nfull,
+                                                              uint32_t ngen_wg,
+                                                              uint8_t* __restrict__ out) {
+  __shared__ __attribute__((aligned(16))) uint8_t lds[kChunkWaves * kWaveLds];
+  if (blockIdx.x < ngen_wg) {
+    if (threadIdx.x != 0) return;
+    uint64_t h[8];
+    hash_chain_al16(data + nfull * bs, nbytes - nfull * bs, h);  // launched only 16-B aligned
+    store_digest(out + nfull * 32u, h);
+    return;
+  }
+  if (nfull == 0) return;  // a kernel argument: the whole workgroup (never launched so)
+  const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);  // scalar
+  uint64_t blk0 = ((uint64_t)(blockIdx.x - ngen_wg) * kChunkWaves + wave) * 64u;
+  uint32_t nv = 1, nstore = 0;  // no blocks left: block nfull - 1 again, nothing stored
+  if (blk0 < nfull) {
+    nv = nstore = (uint32_t)min((uint64_t)64, nfull - blk0);
+  } else {
+    blk0 = nfull - 1;
+  }
+  if (nv >= 64)
+    uniform_glds_wave<false, PhaseBarrier>(data + blk0 * bs, bs, lines, out + blk0 * 32u,
+                                           lds + wave * kWaveLds);
+  else
+    uniform_glds_wave<true, PhaseBarrier>(data + blk0 * bs, bs, lines, out + blk0 * 32u,
+                                          lds + wave * kWaveLds, nv, nstore);
+}
+
+// k_chunks with free-running waves in kThreads workgroups (one wave per SIMD
+// each): every batch that is not whole layers of two waves per SIMD, where a
+// 512-thread workgroup would leave half of the CUs without work in the last
+// round (chunks_phase_aligned below).
+__global__ __launch_bounds__(kThreads, 4) void k_chunks_free(const uint8_t* __restrict__ data,
+                                                              uint64_t nbytes, uint64_t bs,
+                                                              uint32_t lines, uint64_t nfull,
+                                                              uint32_t ngen_wg,
+                                                              uint8_t* __restrict__ out) {
   __shared__ __attribute__((aligned(16))) uint8_t lds[kWaves * kWaveLds];
   if (blockIdx.x < ngen_wg) {
     if (threadIdx.x != 0) return;
@@ -89,7 +129,7 @@ __global__ __launch_bounds__(kThreads, 4) void k_chunks(const uint8_t* __restric
     uniform_glds_wave(data + blk0 * bs, bs, lines, out + blk0 * 32u, lds + wave * kWaveLds);
   else
     uniform_glds_wave<true>(data + blk0 * bs, bs, lines, out + blk0 * 32u, lds + wave * kWaveLds,
-                            (uint32_t)nv);
+                            (uint32_t)nv, (uint32_t)nv);
 }
 
 __global__ __launch_bounds__(kThreads, 4) void k_uniform_direct(const uint8_t* __restrict__ data,
@@ -1037,24 +1077,29 @@ hipError_t launch_sha_desc(const uint8_t* arena, const uint64_t* off, const uint
 // Register-only compressions (no memory traffic): `lines` compressions per
 // lane on a message kept in registers -- the measured VALU ceiling the bench
 // reports next to the HBM roofline (diagnostics, not part of the reference).
-__global__ __launch_bounds__(kThreads, 4) void k_compress_only(uint8_t* __restrict__ out,
-                                                              uint32_t lines) {
-  const uint64_t b = (uint64_t)blockIdx.x * kThreads + threadIdx.x;
+// Workgroups and fast-group policy of k_chunks, so the figure stays the
+// ceiling of the production body's VALU work: every wave runs `lines` (a
+// kernel argument) compressions, lanes past nlanes included; those store
+// nothing.
+__global__ __launch_bounds__(kChunkThreads, 4) void k_compress_only(uint8_t* __restrict__ out,
+                                                                   uint64_t nlanes,
+                                                                   uint32_t lines) {
+  const uint64_t b = (uint64_t)blockIdx.x * kChunkThreads + threadIdx.x;
   uint64_t h[8], m[16];
   init_state(h);
 #pragma unroll
   for (int k = 0; k < 16; ++k) m[k] = b * 0x9e3779b97f4a7c15ULL + k;
   for (uint32_t i = 0; i < lines; ++i) {
     m[0] ^= i;  // keep the message live and varying (static index: no scratch)
-    compress(h, m, (uint64_t)(i + 1) * 128u, i + 1 == lines);
+    compress_sm(h, m, (uint64_t)(i + 1) * 128u, i + 1 == lines, NoHook(), PhaseBarrier());
   }
-  store_digest(out + b * 32u, h);
+  if (b < nlanes) store_digest(out + b * 32u, h);
 }
 
 hipError_t launch_compress_only(uint64_t nlanes, uint32_t lines, uint8_t* out, hipStream_t s) {
   if (nlanes == 0) return hipSuccess;
-  hipLaunchKernelGGL(k_compress_only, dim3(grid_for(nlanes, kThreads)), dim3(kThreads), 0, s, out,
-                     lines);
+  hipLaunchKernelGGL(k_compress_only, dim3(grid_for(nlanes, kChunkThreads)), dim3(kChunkThreads),
+                     0, s, out, nlanes, lines);
   return hipGetLastError();
 }
 
@@ -1327,6 +1372,45 @@ static bool chunks_in_quad(uint64_t nblk, uint64_t bs) {
   return nblk > wave_slots && nblk * 8 <= wave_slots * 13;
 }
 
+// Does a lane-mode launch over nfull whole blocks run phase-aligned
+// (k_chunks) or free-running (k_chunks_free)?  A phase-aligned workgroup is
+// two waves on every SIMD of its CU, so the batch's last round either fills a
+// CU or leaves it empty.  In one process against free-running waves, 32 KiB
+// blocks (profiles/pairing/ab_shapes.log): whole layers of two waves per SIMD
+// win 3-7.5 % (131072, 262144, 524288, 1048576 blocks on 1024 SIMDs); half a
+// layer more loses (65536 blocks x1.63, 196608 +13 %, 327680 +7 %), and so does the
+// padded relay base, one workgroup per CU (1114113 blocks +6.6 %).  So:
+// whole layers without relay padding only.  CIR_CHUNKS_PHASE=1 / 0 (read per
+// call) forces either kernel: both take every shape (the tests run both).
+static bool chunks_phase_aligned(uint64_t nfull, uint32_t pad) {
+  if (const char* v = getenv("CIR_CHUNKS_PHASE")) {
+    if (v[0] == '1') return true;
+    if (v[0] == '0') return false;
+  }
+  return pad == 0 && nfull != 0 && nfull % (128ull * device_simds()) == 0;
+}
+
+// Workgroups of a lane-mode launch over nfull whole blocks (without the
+// ragged one).
+static uint64_t chunks_grid(uint64_t nfull, bool phase) {
+  return grid_for(grid_for(nfull, 64), phase ? kChunkWaves : kWaves);
+}
+
+static hipError_t launch_k_chunks(const uint8_t* data, uint64_t nbytes, uint64_t bs,
+                                  uint64_t nfull, uint32_t ngen_wg, uint32_t pad, uint8_t* out,
+                                  hipStream_t s) {
+  const bool phase = chunks_phase_aligned(nfull, pad);
+  const uint64_t grid = ngen_wg + chunks_grid(nfull, phase);
+  if (grid > 0x7fffffffull) return hipErrorInvalidValue;
+  if (phase)
+    hipLaunchKernelGGL(k_chunks, dim3((unsigned)grid), dim3(kChunkThreads), pad, s, data, nbytes,
+                       bs, (uint32_t)(bs / 128u), nfull, ngen_wg, out);
+  else
+    hipLaunchKernelGGL(k_chunks_free, dim3((unsigned)grid), dim3(kThreads), pad, s, data, nbytes,
+                       bs, (uint32_t)(bs / 128u), nfull, ngen_wg, out);
+  return hipGetLastError();
+}
+
 hipError_t launch_chunks(const uint8_t* data, uint64_t nbytes, uint64_t bs, uint8_t* out,
                          hipStream_t s) {
   if (nbytes == 0) return hipSuccess;
@@ -1343,11 +1427,7 @@ hipError_t launch_chunks(const uint8_t* data, uint64_t nbytes, uint64_t bs, uint
     return launch_general_chunks(data, nbytes, bs, 0, nblk, out, s);
   const uint64_t nfull = nbytes / bs;
   const uint32_t ngen_wg = nfull < nblk ? 1u : 0u;  // the short last block
-  const uint64_t grid = ngen_wg + grid_for(grid_for(nfull, 64), kWaves);
-  if (grid > 0x7fffffffull) return hipErrorInvalidValue;
-  hipLaunchKernelGGL(k_chunks, dim3((unsigned)grid), dim3(kThreads), 0, s, data, nbytes, bs,
-                     (uint32_t)(bs / 128u), nfull, ngen_wg, out);
-  return hipGetLastError();
+  return launch_k_chunks(data, nbytes, bs, nfull, ngen_wg, 0, out, s);
 }
 
 // launch_chunks with the short last block hashed in quad mode on qs,
@@ -1362,7 +1442,7 @@ hipError_t launch_chunks(const uint8_t* data, uint64_t nbytes, uint64_t bs, uint
 // 2193-2203, as descriptors +3-5 %; profiles/r02/relay/maxk/).
 constexpr uint64_t kRelayMaxK = 32;
 // With k >= 3 lane waves per SIMD the lane part is launched with
-// kRelayLanePad bytes of extra LDS per workgroup: two k_chunks workgroups
+// kRelayLanePad bytes of extra LDS per workgroup: two k_chunks_free workgroups
 // per CU (2 x 64 KiB of 160), so two lane waves per SIMD (2 x 112 VGPRs)
 // leave room for a relay wave (244) -- three would not.
 constexpr uint32_t kRelayLanePad = 32768;
@@ -1500,7 +1580,7 @@ hipError_t launch_chunks_split(const uint8_t* data, uint64_t nbytes, uint64_t bs
   const uint64_t nfull = nbytes / bs;
   const bool uni_ok = bs % 128u == 0 && (reinterpret_cast<uintptr_t>(data) & 15u) == 0 &&
                       bs / 128u <= 0xffffffffull && bs <= 0xffffffffull / 8u;
-  const uint64_t grid = grid_for(grid_for(nfull, 64), kWaves);
+  const uint64_t grid = chunks_grid(nfull, false);  // the larger of the two kernels' grids
   RelayPlan plan;
   if (relay && relay->flags && qs && qs != s && uni_ok && relay_plan(nfull, bs, plan)) {
     // k whole lane (or quad) waves per SIMD on s; the extra whole blocks
@@ -1516,9 +1596,7 @@ hipError_t launch_chunks_split(const uint8_t* data, uint64_t nbytes, uint64_t bs
                            dim3(kThreads), plan.pad, s, data, nbytes, bs, (uint64_t)0, plan.base,
                            out);
       else
-        hipLaunchKernelGGL(k_chunks, dim3((unsigned)grid_for(grid_for(plan.base, 64), kWaves)),
-                           dim3(kThreads), plan.pad, s, data, nbytes, bs, (uint32_t)(bs / 128u),
-                           plan.base, 0u, out);
+        return launch_k_chunks(data, nbytes, bs, plan.base, 0u, plan.pad, out, s);
       return hipGetLastError();
     };
     auto rest = [&]() -> hipError_t {
@@ -1546,9 +1624,7 @@ hipError_t launch_chunks_split(const uint8_t* data, uint64_t nbytes, uint64_t bs
                      out);
   e = hipGetLastError();
   if (e != hipSuccess) return e;
-  hipLaunchKernelGGL(k_chunks, dim3((unsigned)grid), dim3(kThreads), 0, s, data, nbytes, bs,
-                     (uint32_t)(bs / 128u), nfull, 0u, out);
-  e = hipGetLastError();
+  e = launch_k_chunks(data, nbytes, bs, nfull, 0u, 0, out, s);
   if (e == hipSuccess) e = hipEventRecord(join, qs);
   if (e == hipSuccess) e = hipStreamWaitEvent(s, join, 0);
   return e;

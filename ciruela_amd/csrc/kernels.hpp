@@ -6,7 +6,13 @@
 namespace cir {
 namespace dev {
 
-constexpr int kThreads = 256;  // 4 waves per workgroup
+constexpr int kThreads = 256;  // 4 waves per workgroup (every kernel but the two below)
+// k_chunks and k_compress_only: 8 waves per workgroup, two on every SIMD of
+// the CU, kept in phase by PhaseBarrier (uniform.hpp); two workgroups per CU
+// make the four waves per SIMD, 64 KiB of LDS each.  Batches that are not
+// whole layers of two waves per SIMD run k_chunks_free at kThreads
+// (kernels.hip chunks_phase_aligned).
+constexpr int kChunkThreads = 512;
 
 enum class Loader : int { kGlds = 0, kDirect = 1 };
 

@@ -10,6 +10,20 @@ namespace dev {
 
 constexpr int kWaves = kThreads / 64;
 
+constexpr int kChunkWaves = kChunkThreads / 64;  // k_chunks, k_compress_only (kernels.hpp)
+
+// The fast-group policy of the phase-aligned kernels: one workgroup barrier
+// at the entry of every fast group of the compression (96 per compression).
+// A SIMD issues v_xor_b32 at 2 cycles only while all of its waves offer one;
+// free-running waves sit at different points of the G step and the xor costs
+// a 4-cycle turn like the other class (tools/pair_ubench.hip,
+// profiles/pairing/pair_ubench.log).  s_barrier waits for no counter, so the
+// LDS-DMA of the next line stays in flight across it.
+// Every wave of a workgroup must run the same number of compressions.
+struct PhaseBarrier {
+  __device__ __forceinline__ void operator()() const { __builtin_amdgcn_s_barrier(); }
+};
+
 // cache-policy bits of the LDS-DMA loads: 2 = nt (streamed, read once;
 // MI355X_MICROARCH.md nt-weights).  A/B in-process: within 1 % of 0
 // (profiles/r01/ablib_nt_occ.log).
@@ -30,7 +44,7 @@ constexpr int kWaveLds = 8192;
 
 // One wave hashes the 64 equal blocks starting at wsrc (bs bytes each,
 // `lines` = bs / 128 message lines) into out[0 .. 64*32).
-// Register budget: k_chunks runs it at 4 waves per SIMD (107 VGPRs, no spills).
+// Register budget: k_chunks runs it at 4 waves per SIMD (110 VGPRs, no spills).
 // The per-lane DMA offsets and LDS read addresses are recomputed every line
 // from one register each (one full-rate v_xor_b32 apiece) instead of being
 // hoisted into 16 + 8 registers; the DMA base address stays scalar.
@@ -40,11 +54,19 @@ constexpr int kWaveLds = 8192;
 // bounds; their lanes hash a duplicate) and only lanes < nv store.  A file
 // whose whole-block count is not a multiple of 64 then still hashes every
 // whole block through the prefetching LDS-DMA body instead of the slower
-// general loader.
-template <bool kPartial = false>
+// general loader.  Only lanes < nstore store (nstore <= nv; 0 for a wave that
+// only keeps its workgroup's barriers company, nv = 1).
+//
+// Fast: the fast-group policy of compress_sm.  With PhaseBarrier the loop is
+// barrier-safe by construction: it runs exactly `lines` iterations (a scalar
+// kernel argument, the same for every wave of the workgroup, full or
+// partial), no iteration leaves early, and the only conditional in it (the
+// wave-uniform refill of after_col0) holds no barrier.
+template <bool kPartial = false, typename Fast = NoHook>
 __device__ __forceinline__ void uniform_glds_wave(const uint8_t* __restrict__ wsrc, uint64_t bs,
                                                   uint32_t lines, uint8_t* __restrict__ out,
-                                                  uint8_t* wl, uint32_t nv = 64) {
+                                                  uint8_t* wl, uint32_t nv = 64,
+                                                  uint32_t nstore = 64) {
   const uint32_t lane = threadIdx.x & 63u;
   // DMA lane offset: r*bs + 16*chunk, chunk = (l & 7) ^ r ^ j
   const uint32_t r = lane >> 3;
@@ -90,12 +112,15 @@ __device__ __forceinline__ void uniform_glds_wave(const uint8_t* __restrict__ ws
     // only chunks 0-3: chunks 4-7 land under it instead of the wave waiting
     // for all eight reads (round 3: config 2 -1.2 to -1.4 % per launch,
     // in-process A/B on two boxes, profiles/r03_s2/ab_overlap.log).
-    compress_sm(h, m, (uint64_t)(i + 1) * 128u, last, [&] {
-      __builtin_amdgcn_s_waitcnt(0xC07F);  // lgkmcnt(0): reads done before the refill
-      if (i + 1 < lines) issue(i + 1);
-    });
+    compress_sm(
+        h, m, (uint64_t)(i + 1) * 128u, last,
+        [&] {
+          __builtin_amdgcn_s_waitcnt(0xC07F);  // lgkmcnt(0): reads done before the refill
+          if (i + 1 < lines) issue(i + 1);
+        },
+        Fast());
   }
-  if (!kPartial || lane < nv) store_digest(out + lane * 32u, h);
+  if (!kPartial || lane < nstore) store_digest(out + lane * 32u, h);
 }
 
 }  // namespace dev

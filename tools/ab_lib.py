@@ -4,14 +4,17 @@ Usage: python tools/ab_lib.py LIB.so [LIB.so ...]
 Fills 1 M x 32 KiB once, then times cir_hash_chunks_dev of each library in
 interleaved rounds (same box, same thermal state), HIP events on one stream.
 Checks that every library produces the same digest array.
+AB_NBLK=N times N blocks instead (1114113: 17 lane waves per SIMD plus one
+block, the padded relay base of launch_chunks_split).
 """
 import ctypes
+import os
 import statistics
 import sys
 
 import torch
 
-BS, NBLK = 32768, 1 << 20
+BS, NBLK = 32768, int(os.environ.get("AB_NBLK", 1 << 20))
 
 
 def load(path):
@@ -51,7 +54,7 @@ def main():
     for k, p in enumerate(paths):
         t = times[k]
         print("%-40s median %.3f ms  min %.3f  max %.3f  GiB/s %.1f  same=%s" % (
-            p, statistics.median(t), min(t), max(t), 32 / (statistics.median(t) / 1e3),
+            p, statistics.median(t), min(t), max(t), BS * NBLK / 2.0 ** 30 / (statistics.median(t) / 1e3),
             torch.equal(outs[k], outs[0])))
 
 

@@ -9,7 +9,17 @@
 // If the clock is per XCD, an unloaded XCD keeps ~2.4 GHz beside loaded ones
 // (config 3: quad chains on their own XCDs would then run at the idle clock).
 //
+// With library paths as arguments (xcd_clock_probe LIB.so [LIB.so ...]) the
+// load is the product's own config-2 launch instead: cir_hash_chunks_dev of
+// each libciruela_amd build over 1 M x 32 KiB of random bytes, the builds in
+// turn, twice, with the probe inside each one's launches -- the clock each
+// build's k_chunks runs at, beside its time per launch.  Library mode uses
+// dlopen (add -ldl to the line below where the C library keeps it apart),
+// holds 32 GiB of device memory, and on an error just returns: the process
+// ends there, nothing is freed or destroyed first.
+//
 //   hipcc -O3 --offload-arch=gfx950 tools/xcd_clock_probe.hip -o build/xcd_clock_probe
+#include <dlfcn.h>
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdio.h>
@@ -93,7 +103,88 @@ __global__ __launch_bounds__(64) void k_probe(int iters, uint64_t* out) {
   }
 }
 
-int main() {
+// median GHz per XCD of one k_probe launch
+static void print_clocks(const std::vector<uint64_t>& h, int nprobe) {
+  std::vector<double> per[16];
+  for (int b = 0; b < nprobe; ++b) {
+    const double ghz = h[b * 4 + 2] ? (double)h[b * 4 + 1] / (double)h[b * 4 + 2] * 0.1 : 0;
+    per[h[b * 4] & 15].push_back(ghz);
+  }
+  for (int x = 0; x < 8; ++x) {
+    auto& v = per[x];
+    if (v.empty()) {
+      printf("  x%d  -  ", x);
+      continue;
+    }
+    std::sort(v.begin(), v.end());
+    printf("  x%d %.3f", x, v[v.size() / 2]);
+  }
+  printf("  GHz (median per XCD)\n");
+  fflush(stdout);
+}
+
+typedef int (*InitFn)(void**, uint32_t, uint64_t);
+typedef int (*ChunksFn)(void*, const void*, uint64_t, uint64_t, uint8_t*, void*);
+typedef int (*FillFn)(void*, uint64_t, uint64_t, uint64_t, uint64_t, void*);
+
+static int lib_mode(int nlib, char** paths) {
+  int least = 0, greatest = 0;
+  CK(hipDeviceGetStreamPriorityRange(&least, &greatest));
+  hipStream_t sl, sp;
+  CK(hipStreamCreateWithFlags(&sl, hipStreamNonBlocking));
+  CK(hipStreamCreateWithPriority(&sp, hipStreamNonBlocking, greatest));
+  const uint64_t bs = 32768, nblk = 1ull << 20, nbytes = bs * nblk;
+  const int nprobe = 256, probe_iters = 400000, launches = 24;
+  uint8_t *data, *digests;
+  uint64_t* out;
+  CK(hipMalloc(&data, nbytes));
+  CK(hipMalloc(&digests, nblk * 32));
+  CK(hipMalloc(&out, nprobe * 4 * 8));
+  std::vector<void*> ctx(nlib);
+  std::vector<ChunksFn> chunks(nlib);
+  for (int k = 0; k < nlib; ++k) {
+    void* lib = dlopen(paths[k], RTLD_NOW | RTLD_LOCAL);
+    if (!lib) {
+      fprintf(stderr, "%s\n", dlerror());
+      return 1;
+    }
+    InitFn init = (InitFn)dlsym(lib, "cir_init");
+    FillFn fill = (FillFn)dlsym(lib, "cir_fill_splitmix64_dev");
+    chunks[k] = (ChunksFn)dlsym(lib, "cir_hash_chunks_dev");
+    if (!init || !fill || !chunks[k] || init(&ctx[k], 1, 1 << 20) != 0) return 1;
+    if (k == 0 && fill(data, nbytes, 0x5EED0002, 0, 0, nullptr) != 0) return 1;
+  }
+  CK(hipDeviceSynchronize());
+  hipEvent_t e0, e1;
+  CK(hipEventCreate(&e0));
+  CK(hipEventCreate(&e1));
+  std::vector<uint64_t> h(nprobe * 4);
+  for (int pass = 0; pass < 2; ++pass)
+    for (int k = 0; k < nlib; ++k) {
+      for (int w = 0; w < 8; ++w)  // warm: the chip at this build's steady state
+        if (chunks[k](ctx[k], data, nbytes, bs, digests, sl) != 0) return 1;
+      CK(hipStreamSynchronize(sl));
+      CK(hipEventRecord(e0, sl));
+      for (int w = 0; w < launches; ++w)
+        if (chunks[k](ctx[k], data, nbytes, bs, digests, sl) != 0) return 1;
+      CK(hipEventRecord(e1, sl));
+      hipLaunchKernelGGL(k_probe, dim3(nprobe), dim3(64), 0, sp, probe_iters, out);
+      CK(hipStreamSynchronize(sp));
+      CK(hipEventSynchronize(e1));
+      float ms = 0;
+      CK(hipEventElapsedTime(&ms, e0, e1));
+      CK(hipMemcpy(h.data(), out, h.size() * 8, hipMemcpyDeviceToHost));
+      uint64_t ticks = 0;
+      for (int b = 0; b < nprobe; ++b) ticks = std::max(ticks, h[b * 4 + 2]);
+      printf("%-40s %.3f ms per launch (probe %.1f ms inside %.1f):", paths[k], ms / launches,
+             ticks * 1e-5, ms);
+      print_clocks(h, nprobe);
+    }
+  return 0;
+}
+
+int main(int argc, char** argv) {
+  if (argc > 1) return lib_mode(argc - 1, argv + 1);
   int least = 0, greatest = 0;
   CK(hipDeviceGetStreamPriorityRange(&least, &greatest));
   hipStream_t sl, sp;
@@ -135,23 +226,8 @@ int main() {
     CK(hipEventElapsedTime(&load_ms, e0, e1));
     std::vector<uint64_t> h(nprobe * 4);
     CK(hipMemcpy(h.data(), out, h.size() * 8, hipMemcpyDeviceToHost));
-    std::vector<double> per[16];
-    for (int b = 0; b < nprobe; ++b) {
-      const double ghz = h[b * 4 + 2] ? (double)h[b * 4 + 1] / (double)h[b * 4 + 2] * 0.1 : 0;
-      per[h[b * 4] & 15].push_back(ghz);
-    }
     printf("%-22s mask 0x%02x (load+probe %.1f ms):", s.name, s.mask, load_ms);
-    for (int x = 0; x < 8; ++x) {
-      auto& v = per[x];
-      if (v.empty()) {
-        printf("  x%d  -  ", x);
-        continue;
-      }
-      std::sort(v.begin(), v.end());
-      printf("  x%d %.3f", x, v[v.size() / 2]);
-    }
-    printf("  GHz (median per XCD)\n");
-    fflush(stdout);
+    print_clocks(h, nprobe);
     CK(hipEventDestroy(e0));
     CK(hipEventDestroy(e1));
   }
