@@ -19,7 +19,7 @@ LIB := ciruela_amd/libciruela_amd.so
 CLI := bin/ciruela-index
 
 SRCS_HIP := $(CSRC)/kernels.hip $(CSRC)/order.hip $(CSRC)/join.hip \
-            $(CSRC)/idxscan.hip
+            $(CSRC)/idxscan.hip $(CSRC)/extents.hip
 SRCS_CPP := $(CSRC)/runtime.cpp $(CSRC)/dirsig.cpp $(CSRC)/scan.cpp $(CSRC)/check.cpp \
             $(CSRC)/links.cpp $(CSRC)/sources.cpp $(CSRC)/idxscan.cpp $(CSRC)/registry.cpp \
             $(CSRC)/blake2b_host.cpp $(CSRC)/sha512_host.cpp

@@ -48,6 +48,11 @@ block_sources                   what fill_blocks lacks: which of the blocks it q
                                 hardlink_sources.rs:131-133)
 Context.match_digests_dev       the join behind it on the device: per needed digest the
                                 smallest ordinal of an equal digest in a pool
+block_extents                   the same answer merged into extents (one copy_file_range
+                                each) with the bitmap of what is left to fetch; the
+                                reference has no counterpart
+                                (src/daemon/tracking/progress.rs:129-170)
+Context.match_extents_dev       the mapping and the merge behind it on the device
 index_digests,                  what every consumer of an index starts with: its block
   Context.index_digests_dev     digests as one array and a run record per non-empty
                                 file, parsed on the device (the reference parses the
@@ -56,6 +61,7 @@ index_digests,                  what every consumer of an index starts with: its
 
 All hashing runs on gfx950 through the library; there is no CPU fallback.
 """
+import collections
 import ctypes
 import os
 import threading
@@ -69,6 +75,7 @@ __all__ = [
     "IndexError_", "DirError", "ReadError", "CiruelaError", "NoDevice", "sha512_256",
     "check_index", "CheckResult", "link_candidates", "check_links", "LinksResult",
     "check_blocks", "BlocksResult", "block_sources", "SourcesResult",
+    "block_extents", "ExtentsResult", "Extent",
     "index_digests", "IndexDigests",
 ]
 
@@ -313,6 +320,30 @@ class Context:
         written by the call, on `stream` alone."""
         _n.check(_n.lib.cir_match_digests_dev(self._h, d_need, n_need, d_pool, n_pool, d_table,
                                               table_slots, seed, d_match, d_nmatch, stream))
+
+    @staticmethod
+    def extents_work_bytes(n_need):
+        """cir_extents_work_bytes: the scratch match_extents_dev needs."""
+        return _n.lib.cir_extents_work_bytes(n_need)
+
+    def match_extents_dev(self, d_match, n_need, d_need_runs, n_need_runs, d_pool_runs,
+                          n_pool_runs, n_pool, block_size, d_work, work_bytes, d_res, d_want=0,
+                          d_src=0, d_file=0, d_block=0, d_fetch=0, d_extents=0, cap_extents=0,
+                          stream=0):
+        """match_digests_dev's d_match mapped back to files and merged into
+        extents on the device (cir_match_extents_dev): run tables of four u64
+        per non-empty file {first, size, file, x} (x: the source ordinal in
+        the pool's); d_res: 6 u64 {status, wanted, found, bytes, dropped,
+        extents}; d_extents: eight u64 per record {first, count, need_file,
+        need_block, src, src_file, src_block, bytes}, none written when there
+        are more than cap_extents; d_fetch: the bitmap of the wanted blocks
+        that were not found; d_src / d_file / d_block: block_sources' arrays,
+        all three or none.  d_work: extents_work_bytes(n_need) bytes.  All
+        written by the call, on `stream` alone."""
+        _n.check(_n.lib.cir_match_extents_dev(self._h, d_match, n_need, d_need_runs, n_need_runs,
+                                              d_pool_runs, n_pool_runs, n_pool, block_size,
+                                              d_want, d_src, d_file, d_block, d_fetch, d_extents,
+                                              cap_extents, d_work, work_bytes, d_res, stream))
 
     def index_digests_dev(self, d_text, length, body_off, body_end, block_size, d_digests,
                           cap_blocks, d_runs, cap_runs, d_work, work_bytes, d_res, stream=0):
@@ -853,6 +884,97 @@ def block_sources(index, sources, want=None, skip_files=None, have=None, context
     block = list((ctypes.c_uint64 * n).from_buffer_copy(raw_b)) if n else []
     return SourcesResult(index, sources, n, src, file, block,
                          dict(zip(SourcesResult.STATS_FIELDS, list(stats))), skipped.value, wbits)
+
+
+Extent = collections.namedtuple(
+    "Extent", "first count need_file need_block src src_file src_block bytes")
+
+
+class ExtentsResult:
+    """Answer of block_extents.  nblk: the index's blocks; extents: Extent
+    tuples in ascending `first` -- `count` consecutive blocks of file
+    need_file from block need_block on, whose copies are the consecutive
+    blocks of file src_file of source src from src_block on, `bytes` long in
+    all; fetch: the bitmap of the wanted blocks without a local copy (bytes,
+    laid out as BlocksResult.have: a valid `want` for a later call).
+    copies(): (dst_path, dst_offset, length, src, src_path, src_offset) per
+    extent, paths as raw bytes -- one copy_file_range each."""
+
+    __slots__ = ("nblk", "extents", "fetch", "stats", "skipped", "_index", "_sources")
+    STATS_FIELDS = SourcesResult.STATS_FIELDS + ("extents", "left_to_fetch")
+
+    def __init__(self, index, sources, nblk, extents, fetch, stats, skipped=0):
+        self._index = index      # (split into lines only when copies() is asked for)
+        self._sources = sources
+        self.nblk = nblk
+        self.extents = extents
+        self.fetch = fetch
+        self.stats = stats
+        self.skipped = skipped
+
+    @property
+    def found(self):
+        return self.stats["found"]
+
+    @property
+    def bytes_local(self):
+        return self.stats["bytes_local"]
+
+    def copies(self):
+        files, bs = _file_blocks(self._index)
+        paths = {}
+        for e in self.extents:
+            if e.src not in paths:
+                paths[e.src] = [p for p, _, _ in _file_blocks(self._sources[e.src])[0]]
+            yield (files[e.need_file][0], e.need_block * bs, e.bytes, e.src,
+                   paths[e.src][e.src_file], e.src_block * bs)
+
+    def __repr__(self):
+        return "ExtentsResult(%d extents, %d of %d wanted blocks found, %d bytes)" % (
+            len(self.extents), self.stats["found"], self.stats["wanted"],
+            self.stats["bytes_local"])
+
+
+def block_extents(index, sources, want=None, skip_files=None, have=None, context=None):
+    """block_sources' question answered as extents: the local copies of
+    `index`'s blocks in the older images whose indexes are `sources` (best
+    first), merged into maximal stretches that one copy_file_range each can
+    copy, and the bitmap of what is left to fetch.  The arguments are
+    block_sources'.  With a context the mapping and the merge run on its first
+    GPU behind the join and only the extents and the bitmap come back; without
+    one the same rule runs on the host (no default context is opened).
+    Returns an ExtentsResult; no file is read and nothing is copied."""
+    if len(index):
+        ptr, keep = _buf(index)
+    else:  # (an empty index is a parse error, not a null argument)
+        keep = ctypes.create_string_buffer(1)
+        ptr = ctypes.cast(keep, ctypes.c_void_p)
+    sources = [bytes(s) for s in sources]
+    nsrc = len(sources)
+    bufs = [ctypes.create_string_buffer(s, max(len(s), 1)) for s in sources]
+    sp = (ctypes.c_void_p * max(nsrc, 1))(*[ctypes.cast(b, ctypes.c_void_p) for b in bufs])
+    sl = (ctypes.c_size_t * max(nsrc, 1))(*[len(s) for s in sources])
+    wbits = _want_bitmap(index, want, skip_files, have)
+    wbuf = None
+    if wbits is not None:
+        wbuf = (ctypes.c_uint64 * max(len(wbits) // 8, 1)).from_buffer_copy(
+            wbits.ljust(8, b"\0"))
+    eo, fo = ctypes.c_void_p(), ctypes.c_void_p()
+    next_, nblk = ctypes.c_size_t(), ctypes.c_uint64()
+    skipped = ctypes.c_size_t()
+    stats = (ctypes.c_uint64 * _n.CIR_EXTENTS_STATS_FIELDS)()
+    _n.check(_n.lib.cir_block_extents(context.handle if context is not None else None, ptr,
+                                      len(index), sp, sl, nsrc, wbuf, ctypes.byref(eo),
+                                      ctypes.byref(next_), ctypes.byref(fo), ctypes.byref(nblk),
+                                      ctypes.byref(skipped), stats))
+    del keep
+    k = next_.value
+    raw_e = _n.take_buffer(eo.value, 8 * _n.CIR_EXTENT_WORDS * k)
+    fetch = bytes(_n.take_buffer(fo.value, 8 * ((nblk.value + 63) // 64)))
+    words = (ctypes.c_uint64 * (_n.CIR_EXTENT_WORDS * k)).from_buffer_copy(raw_e) if k else []
+    extents = [Extent(*words[8 * i:8 * i + 8]) for i in range(k)]
+    return ExtentsResult(index, sources, nblk.value, extents, fetch,
+                         dict(zip(ExtentsResult.STATS_FIELDS, list(stats))), skipped.value)
 
 
 class IndexDigests:

@@ -31,7 +31,7 @@
 //   ciruela-index blocks DIR INDEX_FILE [--list] [--disk-threads N]
 //       which blocks of INDEX_FILE the partial image in DIR already holds
 //       (cir_check_blocks); --list prints `PATH OFFSET` per missing block
-//   ciruela-index sources INDEX SRCINDEX [SRCINDEX ...] [--list] [--host]
+//   ciruela-index sources INDEX SRCINDEX [SRCINDEX ...] [--list] [--host] [--extents]
 //       what fill_blocks (src/daemon/tracking/progress.rs:129-170) need not
 //       fetch: which blocks of the new image INDEX the older images'
 //       indexes SRCINDEX (best first) list, by digest, and where
@@ -40,6 +40,10 @@
 //       --list one line per found block, `PATH OFFSET LENGTH SRC# SRCPATH
 //       SRCOFFSET` (paths escaped as in the index).  --host passes no
 //       context: the join runs on the host and no device is opened.
+//       --extents (cir_block_extents): the copies merged into extents, one
+//       line of the same form per extent (one copy_file_range each), behind
+//       a summary line that also counts the extents and the blocks left to
+//       fetch.
 #include <dirent.h>
 #include <errno.h>
 #include <fcntl.h>
@@ -65,7 +69,8 @@ static void usage() {
           "       ciruela-index links INDEX SRCDIR=SRCINDEX [SRCDIR=SRCINDEX ...]"
           " [--disk-threads N]\n"
           "       ciruela-index blocks DIR INDEX_FILE [--list] [--disk-threads N]\n"
-          "       ciruela-index sources INDEX SRCINDEX [SRCINDEX ...] [--list] [--host]\n");
+          "       ciruela-index sources INDEX SRCINDEX [SRCINDEX ...] [--list] [--host]"
+          " [--extents]\n");
 }
 
 static std::string hex(const uint8_t* p, size_t n) {
@@ -240,7 +245,7 @@ int main(int argc, char** argv) {
   uint32_t threads = 0;
   uint64_t bs = CIR_DEFAULT_BLOCK_SIZE;
   std::string index_dir;
-  bool list_blocks = false, host_only = false;
+  bool list_blocks = false, host_only = false, extents = false;
   std::vector<Job> jobs;
   std::vector<std::string> files;
   for (int i = 2; i < argc; ++i) {
@@ -272,6 +277,7 @@ int main(int argc, char** argv) {
     else if (a == "--index-dir") index_dir = val();
     else if (a == "--list" && (cmd == "blocks" || cmd == "sources")) list_blocks = true;
     else if (a == "--host" && cmd == "sources") host_only = true;
+    else if (a == "--extents" && cmd == "sources") extents = true;
     else if (a == "--append" || a == "--append-weak" || a == "--replace") {
       Job j;
       j.kind = a.substr(2);
@@ -519,6 +525,46 @@ int main(int argc, char** argv) {
     for (const std::vector<uint8_t>& v : link_indexes) {
       sidx.push_back(v.empty() ? &none : v.data());
       slen.push_back(v.size());
+    }
+    if (extents) {
+      uint64_t* ext = nullptr;
+      uint64_t* fetch = nullptr;
+      size_t next = 0, eskipped = 0;
+      uint64_t enblk = 0;
+      uint64_t est[CIR_EXTENTS_STATS_FIELDS];
+      rc = cir_block_extents(ctx, check_index.empty() ? &none : check_index.data(),
+                             check_index.size(), sidx.data(), slen.data(), sidx.size(), nullptr,
+                             &ext, &next, &fetch, &enblk, &eskipped, est);
+      if (rc) {
+        die(rc, files[0].c_str());
+        return 2;
+      }
+      printf("extents: %llu blocks, %llu found in %zu extent(s), %llu bytes found, %llu left to "
+             "fetch; %llu source index(es) used, %zu skipped\n",
+             (unsigned long long)enblk, (unsigned long long)est[1], next,
+             (unsigned long long)est[2], (unsigned long long)est[9], (unsigned long long)est[4],
+             eskipped);
+      uint64_t ibs = 0;
+      const std::vector<std::string> paths = index_file_paths(check_index, nullptr, &ibs);
+      std::vector<std::vector<std::string>> spaths(link_indexes.size());
+      std::vector<bool> loaded(link_indexes.size(), false);
+      for (size_t k = 0; k < next; ++k) {
+        const uint64_t* e = ext + CIR_EXTENT_WORDS * k;
+        const uint64_t s = e[4];
+        if (e[2] >= paths.size() || s >= link_indexes.size()) continue;
+        if (!loaded[s]) {
+          spaths[s] = index_file_paths(link_indexes[s]);
+          loaded[s] = true;
+        }
+        if (e[5] >= spaths[s].size()) continue;
+        printf("%s %llu %llu %llu %s %llu\n", paths[e[2]].c_str(),
+               (unsigned long long)(e[3] * ibs), (unsigned long long)e[7], (unsigned long long)s,
+               spaths[s][e[5]].c_str(), (unsigned long long)(e[6] * ibs));
+      }
+      fflush(stdout);
+      cir_free(ext);
+      cir_free(fetch);
+      return 0;
     }
     uint32_t* bsrc = nullptr;
     uint64_t* bfile = nullptr;

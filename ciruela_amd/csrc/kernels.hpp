@@ -228,6 +228,48 @@ hipError_t launch_index_emit(const uint8_t* text, uint64_t len, uint64_t body_of
                              uint64_t* runs, uint64_t cap_runs, uint64_t* work, uint64_t* res,
                              hipStream_t s);
 
+// Local copies merged into extents (extents.hip; cir_match_extents_dev; the
+// rule is extents.hpp): match[0 .. n_need) as launch_join leaves it and the two
+// run tables (4 u64 per non-empty file {first, size, file, x}, x = the source
+// ordinal in the pool's) to the per-block arrays (src / file / block, all or
+// none), the fetch bitmap (ceil(n_need / 64) u64, nullable), the counts and
+// the extent records (extents::kRecWords u64 each), all on `s`.  work:
+// ext_work_bytes(n_need) bytes of scratch; res: extents::kResFields u64
+// {status, wanted, found, bytes, dropped, extents}, all initialised here.
+// Unchecked: bs != 0, n_need < 2^32, n_pool <= kJoinMaxPool.
+// A tile of 2048 blocks keeps the one-workgroup scan at 2^21 totals (1024
+// steps of 2048) for 2^32 - 1 blocks, and a tile's 32 head words fit one
+// shuffle scan of a wave.
+constexpr uint32_t kExtTile = 2048;  // need blocks per workgroup of the map and emit passes
+inline uint64_t ext_tiles(uint64_t n_need) { return (n_need + kExtTile - 1) / kExtTile; }
+inline uint64_t ext_work_bytes(uint64_t n_need) {
+  return 8 * (2 * ((n_need + 63) / 64) + ext_tiles(n_need) + 2);
+}
+struct ExtentArgs {
+  const uint32_t* match;
+  uint64_t n_need;
+  const uint64_t* need_runs;
+  uint64_t n_need_runs;
+  const uint64_t* pool_runs;
+  uint64_t n_pool_runs;
+  uint64_t n_pool;
+  uint64_t bs;
+  const uint64_t* want;  // nullable
+};
+// Its two halves, for a caller that learns the extent count in between (a
+// synchronise of its own) in order to size the records: launch_extent_map =
+// the map and scan passes (every res word, the per-block arrays and the
+// bitmap are final); launch_extent_emit = the emit and finish passes, gated on
+// the scan's status in `work`; max_extents = an upper bound of res[5] (the
+// finish pass's grid).  No record at or past cap_extents is written.  tev
+// (nullable, a traced call): 3 events recorded before the map kernel, between
+// the two kernels and after the scan kernel.
+hipError_t launch_extent_map(const ExtentArgs& a, uint32_t* src, uint64_t* file, uint64_t* block,
+                             uint64_t* fetch, uint64_t cap_extents, uint64_t* work, uint64_t* res,
+                             hipStream_t s, const hipEvent_t* tev = nullptr);
+hipError_t launch_extent_emit(const ExtentArgs& a, uint64_t* ext, uint64_t cap_extents,
+                              uint64_t max_extents, uint64_t* work, uint64_t* res, hipStream_t s);
+
 // nlanes x `lines` register-only compressions (diagnostic VALU ceiling).
 hipError_t launch_compress_only(uint64_t nlanes, uint32_t lines, uint8_t* out, hipStream_t s);
 

@@ -15,6 +15,11 @@
 // parsed on the device as well (idxscan.hip, the rule idxscan.hpp): the need
 // list and the pool are decoded straight into the join's buffers and only the
 // run tables come back.
+//
+// cir_block_extents answers the same question merged into extents, with the
+// bitmap of what is left to fetch; cir_match_extents_dev is the mapping and
+// the merge behind it on the device (extents.hip, the rule extents.hpp), and
+// maps cir_block_sources' matches there too.  One flow serves both calls.
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -61,6 +66,40 @@ int match_dev_impl(const uint8_t* d_need, size_t n_need, const uint8_t* d_pool, 
     return fail(CIR_EINVAL, "table_slots must be a power of two >= cir_match_table_slots(n_pool)");
   CIR_HIP(dev::launch_join(d_need, n_need, d_pool, n_pool, d_table, table_slots, seed, d_match,
                            d_nmatch, (hipStream_t)stream));
+  return CIR_OK;
+}
+
+int match_extents_dev_impl(const uint32_t* d_match, uint64_t n_need, const uint64_t* d_need_runs,
+                           uint64_t n_need_runs, const uint64_t* d_pool_runs, uint64_t n_pool_runs,
+                           uint64_t n_pool, uint64_t bs, const uint64_t* d_want, uint32_t* d_src,
+                           uint64_t* d_file, uint64_t* d_block, uint64_t* d_fetch,
+                           uint64_t* d_extents, uint64_t cap_extents, void* d_work,
+                           uint64_t work_bytes, uint64_t* d_res, void* stream) {
+  auto addr = [](const void* p) { return reinterpret_cast<uintptr_t>(p); };
+  if ((n_need && !d_match) || (n_need_runs && !d_need_runs) || (n_pool_runs && !d_pool_runs) ||
+      (cap_extents && !d_extents) || !d_work || !d_res)
+    return fail(CIR_EINVAL, "null device pointer");
+  const int given = (d_src != nullptr) + (d_file != nullptr) + (d_block != nullptr);
+  if (given != 0 && given != 3)
+    return fail(CIR_EINVAL, "the per-block arrays are given all three or none");
+  if (addr(d_match) & 3u || addr(d_src) & 3u)
+    return fail(CIR_EINVAL, "d_match and d_src must be 4-byte aligned");
+  if ((addr(d_need_runs) | addr(d_pool_runs) | addr(d_want) | addr(d_file) | addr(d_block) |
+       addr(d_fetch) | addr(d_extents) | addr(d_work) | addr(d_res)) & 7u)
+    return fail(CIR_EINVAL,
+                "run tables, bitmaps, u64 arrays, scratch and result must be 8-byte aligned");
+  if (bs == 0) return fail(CIR_EINVAL, "block_size is 0");
+  if (n_need > 0xFFFFFFFFull) return fail(CIR_EINVAL, "more than 2^32-1 needed blocks");
+  if (n_pool > dev::kJoinMaxPool) return fail(CIR_EINVAL, "more than 2^31-1 pool blocks");
+  if (cap_extents > (1ull << 57)) return fail(CIR_EINVAL, "cap_extents x 64 bytes passes 2^63");
+  if (work_bytes < dev::ext_work_bytes(n_need))
+    return fail(CIR_EINVAL, "work_bytes is below cir_extents_work_bytes(n_need)");
+  const dev::ExtentArgs a{d_match, n_need, d_need_runs, n_need_runs, d_pool_runs,
+                          n_pool_runs, n_pool, bs, d_want};
+  hipStream_t s = (hipStream_t)stream;
+  CIR_HIP(dev::launch_extent_map(a, d_src, d_file, d_block, d_fetch, cap_extents,
+                                 (uint64_t*)d_work, d_res, s));
+  CIR_HIP(dev::launch_extent_emit(a, d_extents, cap_extents, n_need, (uint64_t*)d_work, d_res, s));
   return CIR_OK;
 }
 
@@ -139,6 +178,103 @@ bool parse_on_host() {
   return v && strcmp(v, "host") == 0;
 }
 
+// CIR_SOURCES_MAP, read per call: "host" keeps sources::map_matches (and
+// extents_of) on a host thread behind the device join, "device" runs
+// k_map_matches there whatever the size.  Unset: cir_block_extents maps on
+// the device, and so does cir_block_sources from kMapDeviceMinBlocks needed
+// blocks on.  Below that the device map's fixed cost (six more hipMalloc,
+// one more upload, three more downloads: about 0.13 ms) is more than the host
+// loop's: one source of n blocks against n, whole call, device map against
+// the parent commit's build (profiles/block_extents/size_sweep.json): n =
+// 4,000 0.42-0.45 ms against 0.33-0.34; 8,000 0.44-0.51 against 0.47-0.49, a
+// tie; 16,000 0.50-0.54 against 0.75-0.77; 128,000 1.87-1.91 against 6.73-6.76.
+constexpr uint64_t kMapDeviceMinBlocks = 16384;
+bool map_on_device(bool extents, uint64_t n_need) {
+  const char* v = getenv("CIR_SOURCES_MAP");
+  if (v && strcmp(v, "host") == 0) return false;
+  if (v && strcmp(v, "device") == 0) return true;
+  return extents || n_need >= kMapDeviceMinBlocks;
+}
+
+// Where a call's answer goes: cir_block_sources' three arrays, or
+// cir_block_extents' records and fetch bitmap.  One flow serves both.
+struct Answer {
+  bool extents = false;
+  uint32_t** src_out = nullptr;
+  uint64_t** src_file_out = nullptr;
+  uint64_t** src_block_out = nullptr;
+  uint64_t** extents_out = nullptr;
+  size_t* nextents_out = nullptr;
+  uint64_t** fetch_out = nullptr;
+  uint64_t* nblk_out = nullptr;
+  size_t* nskipped_out = nullptr;
+  uint64_t* stats = nullptr;
+  int nstats() const { return extents ? CIR_EXTENTS_STATS_FIELDS : CIR_SOURCES_STATS_FIELDS; }
+  void clear() const {
+    if (extents) {
+      *extents_out = nullptr;
+      *nextents_out = 0;
+      *fetch_out = nullptr;
+    } else {
+      *src_out = nullptr;
+      *src_file_out = nullptr;
+      *src_block_out = nullptr;
+    }
+    *nblk_out = 0;
+    if (nskipped_out) *nskipped_out = 0;
+    for (int i = 0; i < nstats(); ++i) stats[i] = 0;
+  }
+};
+
+// match[] to the answer on the host: sources::map_matches, and extents_of
+// behind it for cir_block_extents.  need.n > 0.
+int answer_on_host(const Answer& a, const sources::BlockList& need,
+                   const sources::BlockList& pool, uint64_t bs, const uint64_t* want,
+                   const uint32_t* match) {
+  const uint64_t n = need.n;
+  uint32_t* so = (uint32_t*)malloc(n * sizeof(uint32_t));
+  uint64_t* fo = (uint64_t*)malloc(n * sizeof(uint64_t));
+  uint64_t* bo = (uint64_t*)malloc(n * sizeof(uint64_t));
+  uint64_t* fetch = a.extents ? (uint64_t*)malloc((n + 63) / 64 * sizeof(uint64_t)) : nullptr;
+  auto drop = [&](int rc) {
+    free(so);
+    free(fo);
+    free(bo);
+    free(fetch);
+    return rc;
+  };
+  if (!so || !fo || !bo || (a.extents && !fetch)) return drop(fail(CIR_ENOMEM, "malloc"));
+  const sources::MapStats ms = sources::map_matches(need, pool, bs, want, match, so, fo, bo);
+  a.stats[0] = ms.wanted;
+  a.stats[1] = ms.found;
+  a.stats[2] = ms.bytes;
+  a.stats[5] = ms.dropped;
+  *a.nblk_out = n;
+  if (!a.extents) {
+    *a.src_out = so;
+    *a.src_file_out = fo;
+    *a.src_block_out = bo;
+    return CIR_OK;
+  }
+  std::vector<sources::Extent> ex;
+  a.stats[9] = sources::extents_of(need, bs, want, so, fo, bo, &ex, fetch);
+  a.stats[8] = ex.size();
+  uint64_t* rec = nullptr;
+  if (!ex.empty()) {
+    rec = (uint64_t*)malloc(ex.size() * sizeof(sources::Extent));
+    if (!rec) {
+      *a.nblk_out = 0;
+      return drop(fail(CIR_ENOMEM, "malloc"));
+    }
+    memcpy(rec, ex.data(), ex.size() * sizeof(sources::Extent));
+  }
+  *a.extents_out = rec;
+  *a.nextents_out = ex.size();
+  *a.fetch_out = fetch;
+  fetch = nullptr;
+  return drop(CIR_OK);
+}
+
 // One index text of a call with the device parse.
 struct Text {
   const uint8_t* p = nullptr;
@@ -195,7 +331,157 @@ struct StreamDrain {
 struct DevLaps {
   double frame = 0, text_upload = 0, count = 0, host_parse = 0, decode = 0, runs_download = 0;
   double upload = 0, build = 0, probe = 0, download = 0, map = 0;
+  double tables_upload = 0, scan = 0, emit = 0;  // the device map's (answer_on_device)
 };
+
+// match[] (d_match, on the device behind the join) to the answer with the
+// kernels of extents.hip, on stream s: the combined run tables go up (32
+// bytes per file; *tabs, which outlives the stream's work), k_map_matches and
+// k_extent_scan run, and then
+//   cir_block_sources   the three per-block arrays and the counts come down;
+//   cir_block_extents   the counts come down, one synchronise learns the
+//                       extent count, the records are allocated exactly,
+//                       emitted and downloaded with the fetch bitmap; the
+//                       per-block arrays are never made.
+// need.n > 0.  b: the call's device memory.
+int answer_on_device(const Answer& a, const sources::BlockList& need,
+                     const sources::BlockList& pool, uint64_t n_pool, uint64_t bs,
+                     const uint64_t* want, const uint32_t* d_match, DevSet* b,
+                     std::vector<uint64_t>* tabs, uint64_t* x_res, hipStream_t s, bool trace,
+                     DevLaps* laps) {
+  const uint64_t n = need.n, nwords = (n + 63) / 64;
+  const size_t nr = need.runs.size(), pr = pool.runs.size();
+  tabs->resize(4 * (nr + pr));
+  for (size_t i = 0; i < nr + pr; ++i) {
+    const sources::FileRun& r = i < nr ? need.runs[i] : pool.runs[i - nr];
+    uint64_t* o = tabs->data() + 4 * i;
+    o[0] = r.first;
+    o[1] = r.size;
+    o[2] = r.file;
+    o[3] = r.src;
+  }
+  uint64_t* d_tabs = nullptr;
+  uint64_t* d_want = nullptr;
+  uint64_t* d_work = nullptr;
+  uint64_t* d_xres = nullptr;
+  uint32_t* d_so = nullptr;
+  uint64_t* d_fo = nullptr;
+  uint64_t* d_bo = nullptr;
+  uint64_t* d_fetch = nullptr;
+  int rc;
+  if ((rc = b->alloc((void**)&d_tabs, 32 * (nr + pr))) ||
+      (want && (rc = b->alloc((void**)&d_want, 8 * nwords))) ||
+      (rc = b->alloc((void**)&d_work, dev::ext_work_bytes(n))) ||
+      (rc = b->alloc((void**)&d_xres, sizeof(uint64_t) * extents::kResFields)))
+    return rc;
+  if (a.extents) {
+    if ((rc = b->alloc((void**)&d_fetch, 8 * nwords))) return rc;
+  } else if ((rc = b->alloc((void**)&d_so, 4 * n)) || (rc = b->alloc((void**)&d_fo, 8 * n)) ||
+             (rc = b->alloc((void**)&d_bo, 8 * n))) {
+    return rc;
+  }
+  const auto t0 = Clock::now();
+  CIR_HIP(hipMemcpyAsync(d_tabs, tabs->data(), 32 * (nr + pr), hipMemcpyHostToDevice, s));
+  if (want) CIR_HIP(hipMemcpyAsync(d_want, want, 8 * nwords, hipMemcpyHostToDevice, s));
+  if (trace) CIR_HIP(hipStreamSynchronize(s));
+  const auto t1 = Clock::now();
+  const dev::ExtentArgs args{d_match, n, d_tabs, nr, d_tabs + 4 * nr, pr, n_pool, bs, d_want};
+  // (no cap: the count decides the allocation, not the other way round)
+  struct Events {
+    hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
+    ~Events() {
+      for (hipEvent_t e : ev)
+        if (e) (void)hipEventDestroy(e);
+    }
+  } tev;
+  if (trace)
+    for (hipEvent_t& e : tev.ev) CIR_HIP(hipEventCreate(&e));
+  CIR_HIP(dev::launch_extent_map(args, d_so, d_fo, d_bo, d_fetch, ~0ull, d_work, d_xres, s,
+                                 trace ? tev.ev : nullptr));
+  if (trace) CIR_HIP(hipStreamSynchronize(s));
+  const auto t2 = Clock::now();
+  uint32_t* so = nullptr;
+  uint64_t* fo = nullptr;
+  uint64_t* bo = nullptr;
+  uint64_t* rec = nullptr;
+  uint64_t* fetch = nullptr;
+  auto drop = [&](int code) {
+    (void)hipStreamSynchronize(s);  // (no copy is in flight into what is freed)
+    free(so);
+    free(fo);
+    free(bo);
+    free(rec);
+    free(fetch);
+    return code;
+  };
+  hipError_t e = hipSuccess;
+  if (!a.extents) {
+    so = (uint32_t*)malloc(n * sizeof(uint32_t));
+    fo = (uint64_t*)malloc(n * sizeof(uint64_t));
+    bo = (uint64_t*)malloc(n * sizeof(uint64_t));
+    if (!so || !fo || !bo) return drop(fail(CIR_ENOMEM, "malloc"));
+    if ((e = hipMemcpyAsync(so, d_so, 4 * n, hipMemcpyDeviceToHost, s)) != hipSuccess ||
+        (e = hipMemcpyAsync(fo, d_fo, 8 * n, hipMemcpyDeviceToHost, s)) != hipSuccess ||
+        (e = hipMemcpyAsync(bo, d_bo, 8 * n, hipMemcpyDeviceToHost, s)) != hipSuccess)
+      return drop(hip_fail(e, "download of the per-block arrays"));
+  }
+  if ((e = hipMemcpyAsync(x_res, d_xres, sizeof(uint64_t) * extents::kResFields,
+                          hipMemcpyDeviceToHost, s)) != hipSuccess ||
+      (e = hipStreamSynchronize(s)) != hipSuccess)
+    return drop(hip_fail(e, "download of the map's counts"));
+  const auto t3 = Clock::now();
+  auto t4 = t3;
+  if (a.extents) {
+    const uint64_t count = x_res[5];
+    fetch = (uint64_t*)malloc(nwords * sizeof(uint64_t));
+    if (count) rec = (uint64_t*)malloc(count * sizeof(sources::Extent));
+    if (!fetch || (count && !rec)) return drop(fail(CIR_ENOMEM, "malloc"));
+    uint64_t* d_ext = nullptr;
+    if (count) {
+      if ((rc = b->alloc((void**)&d_ext, count * sizeof(sources::Extent)))) return drop(rc);
+      if ((e = dev::launch_extent_emit(args, d_ext, count, count, d_work, d_xres, s)) != hipSuccess)
+        return drop(hip_fail(e, "launch_extent_emit"));
+      if (trace && (e = hipStreamSynchronize(s)) != hipSuccess) return drop(hip_fail(e, "emit"));
+      t4 = Clock::now();
+      if ((e = hipMemcpyAsync(rec, d_ext, count * sizeof(sources::Extent), hipMemcpyDeviceToHost,
+                              s)) != hipSuccess)
+        return drop(hip_fail(e, "download of the extents"));
+    }
+    if ((e = hipMemcpyAsync(fetch, d_fetch, 8 * nwords, hipMemcpyDeviceToHost, s)) != hipSuccess ||
+        (e = hipStreamSynchronize(s)) != hipSuccess)
+      return drop(hip_fail(e, "download of the fetch bitmap"));
+    *a.extents_out = rec;
+    *a.nextents_out = count;
+    *a.fetch_out = fetch;
+    a.stats[8] = count;
+    a.stats[9] = x_res[1] - x_res[2];
+  } else {
+    *a.src_out = so;
+    *a.src_file_out = fo;
+    *a.src_block_out = bo;
+  }
+  a.stats[0] = x_res[1];
+  a.stats[1] = x_res[2];
+  a.stats[2] = x_res[3];
+  a.stats[5] = x_res[4];
+  *a.nblk_out = n;
+  if (trace) {
+    laps->tables_upload = ms_between(t0, t1);
+    float f = 0;
+    if (hipEventElapsedTime(&f, tev.ev[0], tev.ev[1]) == hipSuccess) laps->map = f;
+    if (hipEventElapsedTime(&f, tev.ev[1], tev.ev[2]) == hipSuccess) laps->scan = f;
+    laps->emit = ms_between(t3, t4);
+    laps->download = ms_between(t2, t3) + ms_between(t4, Clock::now());
+    fprintf(stderr,
+            "cir extents map (block_%s): %llu blocks; tables upload %.2f ms (%zu + %zu runs), map "
+            "kernel %.3f ms, scan kernel %.3f ms, emit kernels %.3f ms, downloads %.2f ms; %llu "
+            "extents, %llu bytes downloaded\n",
+            a.extents ? "extents" : "sources", (unsigned long long)n, laps->tables_upload, nr, pr,
+            laps->map, laps->scan, laps->emit, laps->download, (unsigned long long)x_res[5],
+            (unsigned long long)(a.extents ? 64 * x_res[5] + 8 * nwords + 48 : 20 * n + 48));
+  }
+  return CIR_OK;
+}
 
 // One attempt of cir_block_sources with the texts parsed on the device.
 // force_host[k]: text k (nsrc = the new index) goes through the host parser.
@@ -211,10 +497,10 @@ struct DevLaps {
 // 0.22-0.25 ms against 0.18-0.33 ms, a tie; 2,000 0.25-0.29 against 0.64-0.75;
 // 512,000 6.8-6.9 against 132-138.  No size was found at which the host wins.
 int sources_dev_attempt(cir_ctx* ctx, std::vector<Text>& tx, size_t nsrc,
-                        std::vector<uint8_t>& force_host, const uint64_t* want,
-                        uint32_t** src_out, uint64_t** src_file_out, uint64_t** src_block_out,
-                        uint64_t* nblk_out, size_t* nskipped_out, uint64_t* stats, bool trace,
-                        DevLaps* laps) {
+                        std::vector<uint8_t>& force_host, const uint64_t* want, const Answer& ans,
+                        bool trace, DevLaps* laps) {
+  size_t* const nskipped_out = ans.nskipped_out;
+  uint64_t* const stats = ans.stats;
   Text& nw = tx[nsrc];
   const auto t0 = Clock::now();
   auto host_parse = [&](Text& t) {  // (once per text: a second attempt keeps the first's)
@@ -275,6 +561,8 @@ int sources_dev_attempt(cir_ctx* ctx, std::vector<Text>& tx, size_t nsrc,
   uint64_t* d_res = nullptr;
   uint64_t* d_runs = nullptr;
   std::vector<uint64_t> h_res(CIR_INDEX_RES_FIELDS * on_dev.size() + 1);
+  std::vector<uint64_t> tabs;  // the combined run tables, uploaded for the device map
+  uint64_t x_res[extents::kResFields] = {0, 0, 0, 0, 0, 0};
   StreamDrain drain{s};
   if (!on_dev.empty()) {
     int rc;
@@ -429,38 +717,28 @@ int sources_dev_attempt(cir_ctx* ctx, std::vector<Text>& tx, size_t nsrc,
       t.digests = std::vector<uint8_t>();
     }
   }
-  std::vector<uint32_t> match(n_need);
-  uint32_t* so = (uint32_t*)malloc(n_need * sizeof(uint32_t));
-  uint64_t* fo = (uint64_t*)malloc(n_need * sizeof(uint64_t));
-  uint64_t* bo = (uint64_t*)malloc(n_need * sizeof(uint64_t));
-  auto drop = [&](int rc) {
-    free(so);
-    free(fo);
-    free(bo);
-    return rc;
-  };
-  if (!so || !fo || !bo) return drop(fail(CIR_ENOMEM, "malloc"));
+  stats[6] = slots;
   hipError_t e = dev::launch_join(d_need, n_need, d_pool, n_pool, d_table, slots, draw_seed(),
                                   d_match, d_match + n_need, s, trace ? b.ev : nullptr);
-  if (e != hipSuccess) return drop(hip_fail(e, "launch_join"));
-  if (trace && (e = hipStreamSynchronize(s)) != hipSuccess) return drop(hip_fail(e, "join"));
+  if (e != hipSuccess) return hip_fail(e, "launch_join");
+  if (trace) CIR_HIP(hipStreamSynchronize(s));
   const auto t9 = Clock::now();
-  if ((e = hipMemcpyAsync(match.data(), d_match, n_need * sizeof(uint32_t), hipMemcpyDeviceToHost,
-                          s)) != hipSuccess ||
-      (e = hipStreamSynchronize(s)) != hipSuccess)
-    return drop(hip_fail(e, "download of the matches"));
-  const auto t10 = Clock::now();
-  stats[6] = slots;
-  const sources::MapStats ms =
-      sources::map_matches(need, pool, bs, want, match.data(), so, fo, bo);
-  stats[0] = ms.wanted;
-  stats[1] = ms.found;
-  stats[2] = ms.bytes;
-  stats[5] = ms.dropped;
-  *src_out = so;
-  *src_file_out = fo;
-  *src_block_out = bo;
-  *nblk_out = n_need;
+  auto t10 = t9;
+  const bool dev_map = map_on_device(ans.extents, n_need);
+  if (!dev_map) {
+    std::vector<uint32_t> match(n_need);
+    CIR_HIP(hipMemcpyAsync(match.data(), d_match, n_need * sizeof(uint32_t), hipMemcpyDeviceToHost,
+                           s));
+    CIR_HIP(hipStreamSynchronize(s));
+    t10 = Clock::now();
+    const int rc = answer_on_host(ans, need, pool, bs, want, match.data());
+    if (rc) return rc;
+  } else {
+    const int rc = answer_on_device(ans, need, pool, n_pool, bs, want, d_match, &b, &tabs, x_res, s,
+                                    trace, laps);
+    if (rc) return rc;
+    t10 = Clock::now();
+  }
   if (trace) {
     float f = 0;
     if (hipEventElapsedTime(&f, b.ev[0], b.ev[1]) == hipSuccess) laps->build = f;
@@ -472,8 +750,10 @@ int sources_dev_attempt(cir_ctx* ctx, std::vector<Text>& tx, size_t nsrc,
     laps->decode += ms_between(t6, t7) - upload_ms;
     laps->upload += upload_ms;
     laps->runs_download += ms_between(t7, t8);
-    laps->download = ms_between(t9, t10);
-    laps->map = ms_between(t10, Clock::now());
+    if (!dev_map) {
+      laps->download = ms_between(t9, t10);
+      laps->map = ms_between(t10, Clock::now());
+    }
     fprintf(stderr,
             "cir block_sources: %llu blocks against %llu pool blocks of %zu source(s), device; "
             "parse %.2f ms, pool %.2f ms, upload %.2f ms, build kernel %.3f ms, probe kernel "
@@ -488,13 +768,12 @@ int sources_dev_attempt(cir_ctx* ctx, std::vector<Text>& tx, size_t nsrc,
   return CIR_OK;
 }
 
-// cir_block_sources with a context: the texts are framed on the host and
-// their bodies parsed on the device, straight into the join's buffers.
+// cir_block_sources / cir_block_extents with a context: the texts are framed
+// on the host and their bodies parsed on the device, straight into the join's
+// buffers.
 int block_sources_dev(cir_ctx* ctx, const uint8_t* index, size_t len,
                       const uint8_t* const* src_index, const size_t* src_len, size_t nsrc,
-                      const uint64_t* want, uint32_t** src_out, uint64_t** src_file_out,
-                      uint64_t** src_block_out, uint64_t* nblk_out, size_t* nskipped_out,
-                      uint64_t* stats, bool trace) {
+                      const uint64_t* want, const Answer& ans, bool trace) {
   std::vector<Text> tx(nsrc + 1);
   for (size_t k = 0; k <= nsrc; ++k) {
     Text& t = tx[k];
@@ -506,31 +785,24 @@ int block_sources_dev(cir_ctx* ctx, const uint8_t* index, size_t len,
   std::vector<uint8_t> force_host(nsrc + 1, 0);
   DevLaps laps;
   for (;;) {  // (again only after a bad token: at most once per text)
-    const int rc = sources_dev_attempt(ctx, tx, nsrc, force_host, want, src_out, src_file_out,
-                                       src_block_out, nblk_out, nskipped_out, stats, trace, &laps);
+    const int rc = sources_dev_attempt(ctx, tx, nsrc, force_host, want, ans, trace, &laps);
     if (rc != kRetry) return rc;
   }
 }
 
 int block_sources_impl(cir_ctx* ctx, const uint8_t* index, size_t len,
                        const uint8_t* const* src_index, const size_t* src_len, size_t nsrc,
-                       const uint64_t* want, uint32_t** src_out, uint64_t** src_file_out,
-                       uint64_t** src_block_out, uint64_t* nblk_out, size_t* nskipped_out,
-                       uint64_t* stats) {
-  if (!index || !src_out || !src_file_out || !src_block_out || !nblk_out || !stats ||
-      (nsrc && (!src_index || !src_len)))
+                       const uint64_t* want, const Answer& ans) {
+  uint64_t* const stats = ans.stats;
+  size_t* const nskipped_out = ans.nskipped_out;
+  const bool outs = ans.extents ? ans.extents_out && ans.nextents_out && ans.fetch_out
+                                : ans.src_out && ans.src_file_out && ans.src_block_out;
+  if (!index || !outs || !ans.nblk_out || !stats || (nsrc && (!src_index || !src_len)))
     return fail(CIR_EINVAL, "null pointer");
-  *src_out = nullptr;
-  *src_file_out = nullptr;
-  *src_block_out = nullptr;
-  *nblk_out = 0;
-  if (nskipped_out) *nskipped_out = 0;
-  for (int i = 0; i < CIR_SOURCES_STATS_FIELDS; ++i) stats[i] = 0;
+  ans.clear();
   const bool trace = trace_enabled();
   if (ctx && !parse_on_host()) {
-    const int rc = block_sources_dev(ctx, index, len, src_index, src_len, nsrc, want, src_out,
-                                     src_file_out, src_block_out, nblk_out, nskipped_out, stats,
-                                     trace);
+    const int rc = block_sources_dev(ctx, index, len, src_index, src_len, nsrc, want, ans, trace);
     if (rc != kHostFlow) return rc;  // (nothing was reported yet)
   }
   const auto t0 = Clock::now();
@@ -583,27 +855,13 @@ int block_sources_impl(cir_ctx* ctx, const uint8_t* index, size_t len,
       parsed[j] = dirsig::Index();  // (its digests now live in the pool)
     }
   std::vector<uint32_t> match(need.n);
-  uint32_t* so = (uint32_t*)malloc(need.n * sizeof(uint32_t));
-  uint64_t* fo = (uint64_t*)malloc(need.n * sizeof(uint64_t));
-  uint64_t* bo = (uint64_t*)malloc(need.n * sizeof(uint64_t));
-  if (!so || !fo || !bo) {
-    free(so);
-    free(fo);
-    free(bo);
-    return fail(CIR_ENOMEM, "malloc");
-  }
   const auto t2 = Clock::now();
   Laps laps;
   double host_join_ms = 0;
   if (ctx) {
     const uint64_t slots = dev::join_table_slots(n_pool);
     const int rc = device_join(ctx, need_d, need.n, pool_d, n_pool, slots, match.data(), trace, &laps);
-    if (rc) {
-      free(so);
-      free(fo);
-      free(bo);
-      return rc;
-    }
+    if (rc) return rc;
     stats[6] = slots;
   } else {
     sources::host_join(need_d.data(), need.n, pool_d.data(), n_pool, want, match.data(),
@@ -611,16 +869,10 @@ int block_sources_impl(cir_ctx* ctx, const uint8_t* index, size_t len,
     host_join_ms = ms_between(t2, Clock::now());
   }
   const auto t3 = Clock::now();
-  const sources::MapStats ms =
-      sources::map_matches(need, pool, bs, want, match.data(), so, fo, bo);
-  stats[0] = ms.wanted;
-  stats[1] = ms.found;
-  stats[2] = ms.bytes;
-  stats[5] = ms.dropped;
-  *src_out = so;
-  *src_file_out = fo;
-  *src_block_out = bo;
-  *nblk_out = need.n;
+  {
+    const int rc = answer_on_host(ans, need, pool, bs, want, match.data());
+    if (rc) return rc;
+  }
   if (trace) {
     const double map_ms = ms_between(t3, Clock::now());
     if (ctx)
@@ -662,6 +914,50 @@ extern "C" int cir_block_sources(cir_ctx* ctx, const uint8_t* index, size_t len,
                                  uint64_t** src_file_out, uint64_t** src_block_out,
                                  uint64_t* nblk_out, size_t* nskipped_out,
                                  uint64_t stats[CIR_SOURCES_STATS_FIELDS]) try {
-  return cir::block_sources_impl(ctx, index, len, src_index, src_len, nsrc, want, src_out,
-                                 src_file_out, src_block_out, nblk_out, nskipped_out, stats);
+  cir::Answer ans;
+  ans.src_out = src_out;
+  ans.src_file_out = src_file_out;
+  ans.src_block_out = src_block_out;
+  ans.nblk_out = nblk_out;
+  ans.nskipped_out = nskipped_out;
+  ans.stats = stats;
+  return cir::block_sources_impl(ctx, index, len, src_index, src_len, nsrc, want, ans);
+} CIR_CATCH_BOUNDARY
+
+extern "C" int cir_block_extents(cir_ctx* ctx, const uint8_t* index, size_t len,
+                                 const uint8_t* const* src_index, const size_t* src_len,
+                                 size_t nsrc, const uint64_t* want, uint64_t** extents_out,
+                                 size_t* nextents_out, uint64_t** fetch_out, uint64_t* nblk_out,
+                                 size_t* nskipped_out,
+                                 uint64_t stats[CIR_EXTENTS_STATS_FIELDS]) try {
+  cir::Answer ans;
+  ans.extents = true;
+  ans.extents_out = extents_out;
+  ans.nextents_out = nextents_out;
+  ans.fetch_out = fetch_out;
+  ans.nblk_out = nblk_out;
+  ans.nskipped_out = nskipped_out;
+  ans.stats = stats;
+  return cir::block_sources_impl(ctx, index, len, src_index, src_len, nsrc, want, ans);
+} CIR_CATCH_BOUNDARY
+
+extern "C" uint64_t cir_extents_work_bytes(uint64_t n_need) {
+  return cir::dev::ext_work_bytes(n_need);
+}
+
+extern "C" uint64_t cir_debug_extent_tile_blocks(void) { return cir::dev::kExtTile; }
+
+extern "C" int cir_match_extents_dev(cir_ctx* ctx, const uint32_t* d_match, uint64_t n_need,
+                                     const uint64_t* d_need_runs, uint64_t n_need_runs,
+                                     const uint64_t* d_pool_runs, uint64_t n_pool_runs,
+                                     uint64_t n_pool, uint64_t block_size, const uint64_t* d_want,
+                                     uint32_t* d_src, uint64_t* d_file, uint64_t* d_block,
+                                     uint64_t* d_fetch, uint64_t* d_extents, uint64_t cap_extents,
+                                     void* d_work, uint64_t work_bytes, uint64_t* d_res,
+                                     void* stream) try {
+  (void)ctx;  // no scratch of the context's, no side streams
+  return cir::match_extents_dev_impl(d_match, n_need, d_need_runs, n_need_runs, d_pool_runs,
+                                     n_pool_runs, n_pool, block_size, d_want, d_src, d_file,
+                                     d_block, d_fetch, d_extents, cap_extents, d_work, work_bytes,
+                                     d_res, stream);
 } CIR_CATCH_BOUNDARY

@@ -1,7 +1,9 @@
 // cir_block_sources' host side, header-only and free of HIP: the need list and
 // the pool of two or more parsed indexes, the host join and the mapping of a
-// pool ordinal back to (source, file, block).  Compiled alone by
-// tools/sources_fuzz.cpp (with dirsig.cpp) under the sanitizers.
+// pool ordinal back to (source, file, block), and the merge of those into
+// extents (cir_block_extents; the continuation rule is extents.hpp).  Compiled
+// alone by tools/sources_fuzz.cpp and tools/extents_fuzz.cpp (with dirsig.cpp)
+// under the sanitizers.
 //
 // The rule (include/ciruela_blockhash.h, cir_block_sources): the need list is
 // the new index's file entries in index order, blocks ascending; the pool is
@@ -20,6 +22,7 @@
 #include <vector>
 
 #include "dirsig.hpp"
+#include "extents.hpp"
 
 namespace cir {
 namespace sources {
@@ -184,6 +187,51 @@ inline MapStats map_matches(const BlockList& need, const BlockList& pool, uint64
     }
   }
   return st;
+}
+
+// One extent of cir_block_extents: `count` consecutive blocks of one need file
+// whose copies are consecutive blocks of one source file (extents.hpp).
+struct Extent {
+  uint64_t first, count, need_file, need_block, src, src_file, src_block, bytes;
+};
+static_assert(sizeof(Extent) == 8 * extents::kRecWords, "an extent record is eight u64");
+
+// map_matches' arrays to extents, in ascending `first`, and to the bitmap of
+// the wanted blocks that were not found (fetch: ceil(need.n / 64) words, all
+// written here; returns how many bits are set).  The continuation test is
+// extents::cont, the one the kernels use.
+inline uint64_t extents_of(const BlockList& need, uint64_t bs, const uint64_t* want,
+                           const uint32_t* src, const uint64_t* file, const uint64_t* block,
+                           std::vector<Extent>* out, uint64_t* fetch) {
+  const uint64_t nwords = (need.n + 63) / 64;
+  for (uint64_t w = 0; w < nwords; ++w) fetch[w] = 0;
+  uint64_t left = 0;
+  for (size_t r = 0; r < need.runs.size(); ++r) {
+    const FileRun& run = need.runs[r];
+    const uint64_t nb = extents::blocks_of(run.size, bs);
+    bool open = false;  // out->back() ends at block b - 1 of this run
+    for (uint64_t b = 0; b < nb; ++b) {
+      const uint64_t g = run.first + b;
+      const bool found = src[g] != kNone;
+      const bool wanted = !want || (want[g >> 6] >> (g & 63) & 1);
+      if (wanted && !found) {
+        fetch[g >> 6] |= 1ull << (g & 63);
+        ++left;
+      }
+      const uint64_t end = b * bs + block_len(run.size, bs, b);
+      if (open && extents::cont(extents::kFound, r, src[g - 1], file[g - 1], block[g - 1],
+                                found ? extents::kFound : 0, r, src[g], file[g], block[g])) {
+        Extent& e = out->back();
+        ++e.count;
+        e.bytes = extents::extent_bytes(e.need_block, end, bs);
+      } else if (found) {
+        out->push_back(Extent{g, 1, run.file, b, src[g], file[g], block[g],
+                              extents::extent_bytes(b, end, bs)});
+      }
+      open = found;
+    }
+  }
+  return left;
 }
 
 }  // namespace sources

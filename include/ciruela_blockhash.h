@@ -44,6 +44,12 @@
  *       CIR_SOURCES_PARSE=host cir_block_sources with a context parses the index
  *                              texts on the host, as before the device parse
  *                              (cir_index_digests_dev) existed (A/B measurement);
+ *       CIR_SOURCES_MAP=host   cir_block_sources / cir_block_extents with a context
+ *                              map the join's matches back to files on a host
+ *                              thread; =device: with cir_match_extents_dev's
+ *                              kernels.  Unset: cir_block_extents on the device,
+ *                              cir_block_sources on the device from 16,384
+ *                              needed blocks on;
  *       CIR_DEBUG_SPLIT=k      (tests) every opened GPU appears k times.
  *       CIR_DEBUG_STRIPE_BLOCKS=n  (tests) a scan over several devices deals
  *                              stripes of n blocks (default: one staging
@@ -614,7 +620,10 @@ int cir_match_digests_dev(cir_ctx* ctx, const uint8_t* d_need, size_t n_need,
  * the host parser altogether.  Which sources are skipped, the stats, and the error code and
  * text of a new index that does not parse are therefore the host parser's.  The device's lock
  * is not held while a text is parsed on the host.  CIR_SOURCES_PARSE=host keeps every text on
- * the host.
+ * the host.  From 16,384 needed blocks on, the matches are mapped back to (source, file, block)
+ * on the device as well (cir_match_extents_dev's k_map_matches behind the join, on the same
+ * stream; the combined run tables go up, the three arrays come down); smaller calls, and every
+ * call under CIR_SOURCES_MAP=host, keep that loop on a host thread.
  *
  * Both give identical arrays, skip counts and stats ([6] and [7] aside).
  *
@@ -632,6 +641,100 @@ int cir_block_sources(cir_ctx* ctx, const uint8_t* index, size_t len,
                       uint32_t** src_out, uint64_t** src_file_out, uint64_t** src_block_out,
                       uint64_t* nblk_out, size_t* nskipped_out,
                       uint64_t stats[CIR_SOURCES_STATS_FIELDS]);
+
+/* ---- local copies as extents ------------------------------------------ */
+
+/* Bytes of device scratch cir_match_extents_dev needs for n_need blocks (two bitmaps and one
+ * u64 per tile).  Pure. */
+uint64_t cir_extents_work_bytes(uint64_t n_need);
+
+/* Need blocks per workgroup of cir_match_extents_dev's map and emit passes (2048: tests place
+ * extent heads and tails across this boundary).  Pure. */
+uint64_t cir_debug_extent_tile_blocks(void);
+
+/* The matches of cir_match_digests_dev mapped back to files and merged into extents, device-
+ * resident: what a caller copies with one copy_file_range per extent instead of walking 20 bytes
+ * per block.  The reference has no counterpart (fill_blocks queues every block, src/daemon/
+ * tracking/progress.rs:129-170).  The rule is ciruela_amd/csrc/extents.hpp, one text for the
+ * kernels, the host path and its fuzz.
+ *
+ * Inputs: d_match[g] for g < n_need as cir_match_digests_dev leaves it; a need run table and a
+ * pool run table of four u64 per non-empty file {first, size, file, x}, `first` ascending.  In
+ * the need table x is ignored, so the table cir_index_digests_dev writes fits as it is.  In the
+ * pool table `first` is a pool ordinal across all sources and x (its low 32 bits) the source
+ * ordinal.  n_pool, block_size, and d_want (may be NULL = every block; the bitmap layout of
+ * cir_block_sources' want, ceil(n_need / 64) words).
+ *
+ * Per block g: its need run is the last one with first <= g; if there is none, or g - first >=
+ * ceil(size / block_size), the block lies in no file and is neither wanted nor found.  Otherwise
+ * it is wanted iff its want bit is set.  A wanted block with d_match[g] = j < n_pool whose pool
+ * run covers j is found iff the two blocks' lengths min(bs, size - block x bs) are equal; unequal
+ * lengths count as dropped and no second candidate is looked for (cir_block_sources' rule).
+ * Block g continues block g - 1 iff both are found, lie in the same need run, have the same src
+ * and src_file, and src_block(g) == src_block(g - 1) + 1.  An extent is a maximal stretch of
+ * blocks so joined: a need-file boundary breaks it, and so does a source-file or source boundary
+ * (even where the pool ordinals are consecutive), an unwanted or dropped block, and two need
+ * blocks that match the same pool block.
+ *
+ * Outputs.  d_src / d_file / d_block (device, n_need entries each; all three or all NULL): as
+ * cir_block_sources' arrays.  d_fetch (device u64 x ceil(n_need / 64), may be NULL): bit (g & 63)
+ * of word g >> 6 = 1 iff block g is wanted and not found; every word is written, bits at and
+ * past n_need as 0 -- the layout of cir_check_blocks' bitmap and of `want`.  d_extents (device,
+ * eight u64 per record, cap_extents records): {first, count, need_file, need_block, src,
+ * src_file, src_block, bytes} in ascending `first`; first = the global number of the extent's
+ * first block, need_block and src_block = block numbers inside their files, bytes = min(size,
+ * (need_block + count) x bs) - need_block x bs.  d_res (device u64 x CIR_EXTENTS_RES_FIELDS):
+ * [0] CIR_EXTENTS_OK or CIR_EXTENTS_CAPACITY, [1] wanted, [2] found, [3] bytes found, [4]
+ * dropped, [5] extents; every word is written by the call.  On CIR_EXTENTS_CAPACITY ([5] >
+ * cap_extents) the counts, the per-block arrays and the bitmap are exact and written, and no
+ * extent record is.  d_work: work_bytes >= cir_extents_work_bytes(n_need) of device scratch.
+ *
+ * Like every *_dev call it allocates nothing, synchronises nothing and runs on `stream` alone
+ * (four launches: map, scan, emit, finish; no workgroup waits for another; every loop is bounded
+ * by an argument); ctx may be NULL and is not used.  Whatever the run tables and d_match hold
+ * (unsorted, overlapping, `first` past n_need, sizes of 2^64 - 1, ordinals >= n_pool), nothing
+ * is read or written outside the arrays as sized by the arguments, and no record at or past
+ * cap_extents is written: such input gives an unspecified answer, not a fault.
+ *
+ * CIR_EINVAL: a NULL d_match (with n_need > 0), run table (with its count > 0), d_extents (with
+ * cap_extents > 0), d_work or d_res; per-block arrays given in part; d_match or d_src not 4-byte
+ * aligned, any other pointer not 8-byte aligned; block_size == 0; n_need > 2^32 - 1; n_pool >
+ * 2^31 - 1; cap_extents > 2^57; work_bytes < cir_extents_work_bytes(n_need). */
+#define CIR_EXTENT_WORDS 8
+#define CIR_EXTENTS_RES_FIELDS 6
+#define CIR_EXTENTS_OK 0
+#define CIR_EXTENTS_CAPACITY 1
+int cir_match_extents_dev(cir_ctx* ctx, const uint32_t* d_match, uint64_t n_need,
+                          const uint64_t* d_need_runs, uint64_t n_need_runs,
+                          const uint64_t* d_pool_runs, uint64_t n_pool_runs, uint64_t n_pool,
+                          uint64_t block_size, const uint64_t* d_want,
+                          uint32_t* d_src, uint64_t* d_file, uint64_t* d_block, uint64_t* d_fetch,
+                          uint64_t* d_extents, uint64_t cap_extents,
+                          void* d_work, uint64_t work_bytes, uint64_t* d_res, void* stream);
+
+/* cir_block_sources' question answered as extents: the inputs, the skip rules and the errors are
+ * cir_block_sources'.  *extents_out = malloc'd records of CIR_EXTENT_WORDS u64 as above
+ * (cir_free; NULL when *nextents_out == 0); *fetch_out = the malloc'd bitmap of the wanted blocks
+ * without a local copy, ceil(*nblk_out / 64) words (cir_free; NULL when *nblk_out == 0): what is
+ * left to fetch, and the `want` of a later call.
+ *
+ * With a context the device flow of cir_block_sources runs up to the join; then the combined run
+ * tables go up (32 bytes per non-empty file) and cir_match_extents_dev's kernels run behind the
+ * join on the same stream.  One synchronise learns the extent count, the records are allocated
+ * exactly, emitted and downloaded with the bitmap; the per-block arrays never leave the device
+ * (they are not even made).  With ctx == NULL the host applies the same rule (map_matches and
+ * extents_of in ciruela_amd/csrc/sources.hpp), and no GPU is needed.  Both give identical
+ * output.  CIR_SOURCES_MAP=host, read per call, keeps the mapping on a host thread behind the
+ * device join.
+ *
+ * stats: cir_block_sources' eight fields, [8] extents, [9] blocks left to fetch. */
+#define CIR_EXTENTS_STATS_FIELDS 10
+int cir_block_extents(cir_ctx* ctx, const uint8_t* index, size_t len,
+                      const uint8_t* const* src_index, const size_t* src_len, size_t nsrc,
+                      const uint64_t* want,
+                      uint64_t** extents_out, size_t* nextents_out, uint64_t** fetch_out,
+                      uint64_t* nblk_out, size_t* nskipped_out,
+                      uint64_t stats[CIR_EXTENTS_STATS_FIELDS]);
 
 /* ---- an index's digests as an array ----------------------------------- */
 
