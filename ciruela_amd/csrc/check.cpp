@@ -36,6 +36,12 @@
 // with openat(O_DIRECTORY | O_NOFOLLOW) below the root fd, never by a path
 // -- and reads only if fstat shows the same file.  Each packer holds one
 // directory fd and each reader one directory and one file fd.
+//
+// The three entry points share everything that is not their policy: the
+// slot's layout and the walk through the block ranges (pack.hpp), and below
+// the index's layout (load_index), the directory cache, the readers
+// (run_reads), the deal of stripes to devices (run_striped) and the rotation
+// over a device's slots (rotate_slots).
 #include <errno.h>
 #include <fcntl.h>
 #include <limits.h>
@@ -53,6 +59,7 @@
 
 #include "bits.hpp"
 #include "dirsig.hpp"
+#include "pack.hpp"
 #include "runtime.hpp"
 #include "stripes.hpp"
 
@@ -60,8 +67,6 @@ namespace cir {
 namespace {
 
 constexpr uint64_t kNone = ~0ull;
-// (scan.cpp's read piece: `threads` readers stay busy on large files)
-constexpr uint64_t kReadPiece = 4ull << 20;
 
 // The fds the check itself holds, and their peak (stats[5]).
 struct FdCount {
@@ -85,55 +90,109 @@ struct FdCount {
 // One file entry of the index, in index order.
 struct Item {
   size_t entry = 0;        // index into Index::entries
-  size_t dir = 0;          // index into Image::dirs
+  size_t dir = 0;          // index into Layout::dirs
   std::string name;        // the entry's name in its directory
   uint64_t size = 0;
   uint64_t nblk = 0;
   uint64_t first_blk = 0;  // global index of block 0 (an empty file: the next file's)
 };
 
-struct Failure {
-  size_t item = SIZE_MAX;
-  uint64_t blk = kNone;  // second half of the key
-  int kind = CIR_CHECK_OK;
-  int err = 0;
-  uint64_t bad_blk = kNone;  // the first bad block, when that is what failed
-  bool before(size_t it, uint64_t b) const { return item < it || (item == it && blk < b); }
-};
+using Dirs = std::vector<std::vector<std::string>>;
 
-struct Image {
-  const dirsig::Index* idx = nullptr;
+// What every entry point makes of its index before it touches a file.
+struct Layout {
+  dirsig::Index idx;
   uint64_t bs = 0;
   int ht = CIR_HASH_BLAKE2B_256;
-  int root = -1;
-  std::vector<std::vector<std::string>> dirs;  // a directory line's components below the root
-  std::vector<Item> items;
+  Dirs dirs;                // a directory line's components below the root
+  std::vector<Item> items;  // every file entry, in index order
   uint64_t nblk_total = 0;
   FdCount fds;
-  // the smallest failure reported so far
-  std::mutex mu;
-  Failure best;
-  std::atomic<uint64_t> n_files{0}, n_blocks{0}, n_bytes{0}, n_batches{0}, n_empty{0};
-
-  void report(const Failure& f) {
-    std::lock_guard<std::mutex> lk(mu);
-    if (f.before(best.item, best.blk)) best = f;
+  // an image root (open_image), closed with the layout when it is ours
+  int root = -1;
+  bool own_root = false;
+  ~Layout() {
+    if (own_root) fds.close(root);
   }
-  // a failure is known below (it, b): nothing from there on can be the verdict
-  bool decided_before(size_t it, uint64_t b) {
-    std::lock_guard<std::mutex> lk(mu);
-    return best.before(it, b);
-  }
-  // the non-empty file that holds global block g
-  size_t item_of(uint64_t g) const {
-    size_t i = std::upper_bound(items.begin(), items.end(), g,
-                                [](uint64_t b, const Item& x) { return b < x.first_blk; }) -
-               items.begin();
-    // (empty files share the next file's first_blk and sort before it: the
-    // last item whose first_blk <= g is the file itself)
-    return i - 1;
+  const uint8_t* digests(const Item& it, uint64_t fblk) const {
+    return idx.entries[it.entry].hashes.data() + 32 * fblk;
   }
 };
+
+// Parse and validate the index; the entries' places: directory lines as
+// components, files with the global index of their first block.
+int load_index(const uint8_t* index, size_t len, Layout* t) {
+  dirsig::Index& idx = t->idx;
+  std::string err;
+  if (!dirsig::parse(index, len, &idx, &err)) return parse_fail(idx.bad_hash_size, err);
+  if (dirsig::digest_len(idx.header.hash) != 32)
+    return fail(CIR_EHASHSIZE, "hash size is unsupported");
+  if (idx.header.block_size > 0xffffffffull)
+    return fail(CIR_EINVAL, "block_size must be in 1 .. 2^32-1");
+  t->bs = idx.header.block_size;
+  t->ht = idx.header.hash == dirsig::HashType::kSha512_256 ? CIR_HASH_SHA512_256
+                                                            : CIR_HASH_BLAKE2B_256;
+  for (size_t e = 0; e < idx.entries.size(); ++e) {
+    const dirsig::Entry& en = idx.entries[e];
+    if (en.kind == dirsig::EntryKind::kDir) {
+      std::vector<std::string> comps;
+      size_t i = 0;
+      while (i < en.path.size()) {
+        size_t j = en.path.find('/', i);
+        if (j == std::string::npos) j = en.path.size();
+        if (j > i) comps.push_back(en.path.substr(i, j - i));
+        i = j + 1;
+      }
+      t->dirs.push_back(std::move(comps));
+    } else if (en.kind == dirsig::EntryKind::kFile) {
+      if (t->dirs.empty()) return fail(CIR_EPARSE, "error parsing index: entry before a directory");
+      Item it;
+      it.entry = e;
+      it.dir = t->dirs.size() - 1;
+      it.name = en.path.substr(en.path.find_last_of('/') + 1);
+      it.size = en.size;
+      it.nblk = en.hashes.size() / 32;
+      it.first_blk = t->nblk_total;
+      t->nblk_total += it.nblk;
+      t->items.push_back(std::move(it));
+    }
+    // symlink entries are the caller's to create (commit.rs:118-126)
+  }
+  return CIR_OK;
+}
+
+// An image root by (dirfd, name-or-null): below dirfd by name (ours to
+// close), or dirfd itself when it is a directory.  -1 with *err.
+int open_root(FdCount& fds, int dirfd, const char* name, int* err) {
+  *err = 0;
+  if (name) {
+    const int fd = fds.took(::openat(dirfd, name, O_RDONLY | O_DIRECTORY | O_CLOEXEC));
+    if (fd < 0) *err = errno;
+    return fd;
+  }
+  struct stat st;
+  if (::fstat(dirfd, &st) != 0) {
+    *err = errno;
+    return -1;
+  }
+  if (!S_ISDIR(st.st_mode)) {
+    *err = ENOTDIR;
+    return -1;
+  }
+  return dirfd;
+}
+
+// The one root of cir_check_index and cir_check_blocks.
+int open_image(Layout& t, int dirfd, const char* dir) {
+  int e = 0;
+  t.root = open_root(t.fds, dirfd, dir, &e);
+  if (t.root >= 0) {
+    t.own_root = dir != nullptr;
+    return CIR_OK;
+  }
+  return dir ? fail(CIR_EIO, std::string("error opening image ") + dir + ": " + strerror(e))
+             : fail(CIR_EIO, "image root fd is not a directory");
+}
 
 // A directory below the root, opened one component at a time, never through
 // a symlink.  No components: the root fd itself (not ours to close).
@@ -143,7 +202,7 @@ struct DirFd {
   int err = 0;  // errno when fd < 0
 };
 
-DirFd open_dir_at(FdCount& fds, int root, const std::vector<std::string>& comps) {
+DirFd open_dir(FdCount& fds, int root, const std::vector<std::string>& comps) {
   DirFd d;
   d.fd = root;
   for (const std::string& c : comps) {
@@ -163,16 +222,35 @@ DirFd open_dir_at(FdCount& fds, int root, const std::vector<std::string>& comps)
   return d;
 }
 
-DirFd open_dir(Image& im, const std::vector<std::string>& comps) {
-  return open_dir_at(im.fds, im.root, comps);
-}
-
-void close_dir_at(FdCount& fds, DirFd& d) {
+void close_dir(FdCount& fds, DirFd& d) {
   if (d.own) fds.close(d.fd);
   d = DirFd();
 }
 
-void close_dir(Image& im, DirFd& d) { close_dir_at(im.fds, d); }
+// The directory (of one root) a packer or a reader keeps while the next file
+// needs the same one: at most one directory fd at a time.
+class DirCache {
+ public:
+  explicit DirCache(Layout& t) : t_(t) {}
+  ~DirCache() { close_dir(t_.fds, d_); }
+  DirCache(const DirCache&) = delete;
+  DirCache& operator=(const DirCache&) = delete;
+  const DirFd& of(int root, size_t dir) {
+    if (root_ != root || dir_ != dir) {
+      close_dir(t_.fds, d_);
+      d_ = open_dir(t_.fds, root, t_.dirs[dir]);
+      root_ = root;
+      dir_ = dir;
+    }
+    return d_;
+  }
+
+ private:
+  Layout& t_;
+  DirFd d_;
+  int root_ = -1;
+  size_t dir_ = SIZE_MAX;
+};
 
 // What the packer saw of a file it is about to pack.
 struct Seen {
@@ -183,16 +261,16 @@ struct Seen {
 // openat + fstat of a listed non-empty file: 0 with *fd_out open, or the
 // failure's kind with *err.  (O_NONBLOCK: a fifo in the file's place fails
 // the fstat test below instead of blocking the open.)
-int open_listed_at(FdCount& fds, const DirFd& d, const Item& it, int* fd_out, struct stat* st,
-                   int* err) {
+int open_listed(FdCount& fds, const DirFd& d, const std::string& name, int* fd_out,
+                struct stat* st, int* err) {
   *fd_out = -1;
   *err = 0;
   if (d.fd < 0) {
     *err = d.err;
     return CIR_CHECK_READ;
   }
-  const int fd = fds.took(
-      ::openat(d.fd, it.name.c_str(), O_RDONLY | O_NOFOLLOW | O_CLOEXEC | O_NONBLOCK));
+  const int fd =
+      fds.took(::openat(d.fd, name.c_str(), O_RDONLY | O_NOFOLLOW | O_CLOEXEC | O_NONBLOCK));
   if (fd < 0) {
     *err = errno;
     return CIR_CHECK_READ;
@@ -211,9 +289,203 @@ int open_listed_at(FdCount& fds, const DirFd& d, const Item& it, int* fd_out, st
   return CIR_CHECK_OK;
 }
 
-int open_listed(Image& im, const DirFd& d, const Item& it, int* fd_out, struct stat* st, int* err) {
-  return open_listed_at(im.fds, d, it, fd_out, st, err);
+// One piece of a packed file for a reader: where to open the file again,
+// what it must then be, and what to read of it.
+struct ReadJob {
+  int root;  // below this fd, in Layout::dirs[dir], by name
+  size_t dir;
+  const std::string* name;
+  Seen seen;
+  uint64_t min_len, max_len;  // the length the reopened file may have
+  uint64_t file_off, len;
+  uint8_t* dst;
+  size_t tag;  // the caller's
+};
+
+// Read the batch's jobs on `threads` readers, each with a directory of its
+// own kept across the jobs that share it.  A job that fails goes to
+// on_fail(job index, errno) on the reader's thread: ESTALE when the file is
+// not the one that was packed or has another length than allowed, ENODATA
+// when it shrank under the read.  With `skip_after` the readers pass over
+// the jobs after *skip_after (on_fail may lower it); without it every job
+// is tried.
+template <class Fail>
+void run_reads(Layout& t, const std::vector<ReadJob>& jobs, unsigned threads, Fail on_fail,
+               const std::atomic<size_t>* skip_after = nullptr) {
+  std::atomic<size_t> next{0};
+  const bool nt = stage_copy_nt();
+  auto worker = [&] {
+    DirCache dir(t);
+    for (;;) {
+      const size_t i = next.fetch_add(1);
+      if (i >= jobs.size() || (skip_after && i > skip_after->load())) break;
+      const ReadJob& j = jobs[i];
+      int fd = -1, e = 0;
+      struct stat st;
+      bool ok =
+          open_listed(t.fds, dir.of(j.root, j.dir), *j.name, &fd, &st, &e) == CIR_CHECK_OK;
+      if (ok && (st.st_dev != j.seen.dev || st.st_ino != j.seen.ino ||
+                 (uint64_t)st.st_size < j.min_len || (uint64_t)st.st_size > j.max_len)) {
+        ok = false;
+        e = ESTALE;
+      }
+      uint64_t got = 0;
+      while (ok && got < j.len) {
+        const ssize_t r =
+            pread_staged(fd, j.dst + got, j.len - got, (off_t)(j.file_off + got), nt);
+        if (r < 0 && errno == EINTR) continue;
+        if (r <= 0) {
+          ok = false;
+          e = r == 0 ? ENODATA : errno;
+          break;
+        }
+        got += (uint64_t)r;
+      }
+      t.fds.close(fd);
+      if (!ok) on_fail(i, e);
+    }
+  };
+  parallel_run(std::max(1u, std::min<unsigned>(threads, (unsigned)jobs.size())), worker);
 }
+
+// The global block order [0, nblk_total) over the context's devices:
+// fn(device index, device, reader threads, its block ranges) on one device
+// with the whole order, or on each of several with the stripes dealt to it
+// round-robin (as hash_files deals them), each on a thread of its own with
+// threads / devices readers.  The first failure in device order is returned.
+template <class Fn>
+int run_striped(cir_ctx* ctx, uint64_t nblk_total, uint64_t bs, unsigned threads, Fn fn) {
+  if (nblk_total == 0) return CIR_OK;  // nothing for a device
+  if (threads == 0) threads = host_copy_threads(ctx->devs.size());
+  const size_t nd = (size_t)std::min<uint64_t>(ctx->devs.size(), nblk_total);
+  if (nd <= 1) return fn((size_t)0, *ctx->devs[0], threads, BlockRanges{{0, nblk_total}});
+  uint64_t stripe = std::max<uint64_t>(1, ctx->staging / bs);
+  if (const char* e = getenv("CIR_DEBUG_STRIPE_BLOCKS"))  // tests: stripes of a few blocks
+    if (atoll(e) > 0) stripe = (uint64_t)atoll(e);
+  const StripePrefix order(nblk_total, stripe);
+  std::vector<BlockRanges> dev_ranges(nd);
+  for (size_t st = 0; st < order.stripes(); ++st)
+    dev_ranges[st % nd].push_back({st * stripe, st * stripe + order.stripe_len(st)});
+  const unsigned per = std::max(1u, threads / (unsigned)nd);
+  std::vector<int> rcs(nd, 0);
+  std::vector<std::string> errs(nd);
+  fan_out(nd, [&](size_t i) {
+    if (dev_ranges[i].empty()) return;
+    rcs[i] = fn(i, *ctx->devs[i], per, dev_ranges[i]);
+    if (rcs[i]) errs[i] = cir_last_error();
+  });
+  for (size_t i = 0; i < nd; ++i)
+    if (rcs[i]) return fail(rcs[i], errs[i]);
+  return CIR_OK;
+}
+
+// CIR_TRACE: where a device's host thread spent a call.  (No clock is read
+// when it is off.)
+struct Laps {
+  using Clock = std::chrono::steady_clock;
+  const bool on;
+  double wait = 0, pack = 0, read = 0, submit = 0;  // ms
+  uint64_t batches = 0;
+  Clock::time_point t0;
+  explicit Laps(bool trace) : on(trace) {}
+  void start() {
+    if (on) t0 = Clock::now();
+  }
+  void lap(double& acc) {
+    if (!on) return;
+    const Clock::time_point t1 = Clock::now();
+    acc += std::chrono::duration<double, std::milli>(t1 - t0).count();
+    t0 = t1;
+  }
+};
+
+// One pipeline on device d: its slots in turn, each waited for and retired
+// (retire(k, slot)) when it is in flight, then -- while more() -- offered for
+// packing: pack(k, slot) says whether it packed anything, read(k, slot) fills
+// the slot and submit(k, slot) sends it (or not: what it submits it leaves
+// busy).  `ensure` is the Device member that sizes the mode's own buffers of
+// a slot.  Runs until nothing is left and nothing is in flight.
+template <class More, class Retire, class Pack, class Read, class Submit>
+int rotate_slots(Device& d, SlotSizes& sz, int (Device::*ensure)(Slot&), Laps& laps, More more,
+                 Retire retire, Pack pack, Read read, Submit submit) {
+  std::lock_guard<std::mutex> lk(d.mu);
+  DeviceGuard guard;
+  CIR_HIP(hipSetDevice(d.id));
+  SlotDrain drain{d};  // an early return leaves no slot busy
+  auto busy = [&] {
+    for (const Slot& s : d.slot)
+      if (s.busy) return true;
+    return false;
+  };
+  int k = 0;
+  while (more() || busy()) {
+    Slot& s = d.slot[k];
+    laps.start();
+    if (s.busy) {
+      const int rc = slot_wait(d, s);
+      if (rc) return rc;
+      retire(k, s);
+    }
+    laps.lap(laps.wait);
+    if (more()) {
+      int rc = d.ensure_slot(s, sz.cap, sz.cap_blk);
+      if (rc) return rc;
+      rc = (d.*ensure)(s);
+      if (rc) return rc;
+      const bool packed = pack(k, s);
+      sz.offered();
+      laps.lap(laps.pack);
+      if (packed) {
+        read(k, s);
+        laps.lap(laps.read);
+        rc = submit(k, s);
+        if (rc) return rc;
+        laps.lap(laps.submit);
+        ++laps.batches;
+      }
+    }
+    k = (k + 1) % Device::kSlots;
+  }
+  return CIR_OK;
+}
+
+// ---- cir_check_index ------------------------------------------------------
+
+struct Failure {
+  size_t item = SIZE_MAX;
+  uint64_t blk = kNone;  // second half of the key
+  int kind = CIR_CHECK_OK;
+  int err = 0;
+  uint64_t bad_blk = kNone;  // the first bad block, when that is what failed
+  bool before(size_t it, uint64_t b) const { return item < it || (item == it && blk < b); }
+};
+
+struct Image : Layout {
+  // the smallest failure reported so far
+  std::mutex mu;
+  Failure best;
+  std::atomic<uint64_t> n_files{0}, n_blocks{0}, n_bytes{0}, n_batches{0}, n_empty{0};
+
+  void report(size_t item, uint64_t blk, int kind, int err, uint64_t bad_blk = kNone) {
+    std::lock_guard<std::mutex> lk(mu);
+    const Failure f{item, blk, kind, err, bad_blk};
+    if (f.before(best.item, best.blk)) best = f;
+  }
+  // a failure is known below (it, b): nothing from there on can be the verdict
+  bool decided_before(size_t it, uint64_t b) {
+    std::lock_guard<std::mutex> lk(mu);
+    return best.before(it, b);
+  }
+  // the non-empty file that holds global block g
+  size_t item_of(uint64_t g) const {
+    size_t i = std::upper_bound(items.begin(), items.end(), g,
+                                [](uint64_t b, const Item& x) { return b < x.first_blk; }) -
+               items.begin();
+    // (empty files share the next file's first_blk and sort before it: the
+    // last item whose first_blk <= g is the file itself)
+    return i - 1;
+  }
+};
 
 // A size-0 entry (commit.rs:57-90): absent passes (the caller creates it),
 // present it must be an empty regular file.
@@ -239,7 +511,7 @@ int examine_empty(const DirFd& d, const Item& it, int* err) {
 int examine_file(Image& im, const DirFd& d, const Item& it, Seen* seen, int* err) {
   int fd = -1;
   struct stat st;
-  const int kind = open_listed(im, d, it, &fd, &st, err);
+  const int kind = open_listed(im.fds, d, it.name, &fd, &st, err);
   if (kind) return kind;
   im.fds.close(fd);
   if ((uint64_t)st.st_size != it.size) return CIR_CHECK_CHECKSUM;
@@ -248,270 +520,122 @@ int examine_file(Image& im, const DirFd& d, const Item& it, Seen* seen, int* err
   return CIR_CHECK_OK;
 }
 
-struct ReadJob {
-  size_t item;
-  Seen seen;
-  uint64_t file_off, len;
-  uint8_t* dst;
-  uint64_t seg_blk;  // the batch's block index where this item's segment starts
-  uint64_t seg_pos;  // and its byte offset in the slot
-};
-
-// Read the batch's jobs on `threads` readers.  Returns the index of the first
-// job (in job order, whatever the timing: a reader skips only jobs after a
-// failed one) that failed, with its errno, or jobs.size().
-size_t run_reads(Image& im, const std::vector<ReadJob>& jobs, unsigned threads, int* err_out) {
-  std::atomic<size_t> next{0}, first_bad{jobs.size()};
-  std::mutex mu;
-  int first_err = 0;
-  const bool nt = stage_copy_nt();
-  auto worker = [&] {
-    DirFd d;  // this reader's directory, kept across the jobs that share it
-    size_t d_dir = SIZE_MAX;
-    for (;;) {
-      const size_t i = next.fetch_add(1);
-      if (i >= jobs.size() || i > first_bad.load()) break;
-      const ReadJob& j = jobs[i];
-      const Item& it = im.items[j.item];
-      if (d_dir != it.dir) {
-        close_dir(im, d);
-        d = open_dir(im, im.dirs[it.dir]);
-        d_dir = it.dir;
-      }
-      int fd = -1, e = 0;
-      struct stat st;
-      bool ok = open_listed(im, d, it, &fd, &st, &e) == CIR_CHECK_OK;
-      if (ok && (st.st_dev != j.seen.dev || st.st_ino != j.seen.ino ||
-                 (uint64_t)st.st_size != it.size)) {
-        ok = false;  // not the file that was packed
-        e = ESTALE;
-      }
-      uint64_t got = 0;
-      while (ok && got < j.len) {
-        const ssize_t r =
-            pread_staged(fd, j.dst + got, j.len - got, (off_t)(j.file_off + got), nt);
-        if (r < 0 && errno == EINTR) continue;
-        if (r <= 0) {
-          ok = false;
-          e = r == 0 ? ENODATA : errno;  // the file shrank under the read
-          break;
-        }
-        got += (uint64_t)r;
-      }
-      im.fds.close(fd);
-      if (!ok) {
-        std::lock_guard<std::mutex> lk(mu);
-        if (i < first_bad.load()) {
-          first_bad.store(i);
-          first_err = e;
-        }
-      }
-    }
-    close_dir(im, d);
-  };
-  parallel_run(std::max(1u, std::min<unsigned>(threads, (unsigned)jobs.size())), worker);
-  *err_out = first_err;
-  return first_bad.load();
-}
-
-using BlockRanges = std::vector<std::pair<uint64_t, uint64_t>>;
-
-// hash_range (scan.cpp) in check mode: the block ranges `ranges` (increasing)
-// on device d, with the entries each range owns -- those whose first block
-// lies in it, the trailing empty files with the last range -- examined in
-// order as the packer reaches them.  Every failure goes to im.report().
+// The block ranges `ranges` (increasing) on device d, with the entries each
+// range owns -- those whose first block lies in it, the trailing empty files
+// with the last range -- examined in order as the packer reaches them.  Every
+// failure goes to im.report().
 int check_range(cir_ctx* ctx, Device& d, Image& im, unsigned threads, const BlockRanges& ranges) {
-  if (ranges.empty()) return CIR_OK;
-  std::lock_guard<std::mutex> lk(d.mu);
-  DeviceGuard guard;
-  CIR_HIP(hipSetDevice(d.id));
-  SlotDrain drain{d};  // an early return leaves no slot busy
   const std::vector<Item>& items = im.items;
-  const uint64_t bs = im.bs;
   uint64_t seg = 0;
-  for (const Item& it : items) seg = std::max(seg, std::min<uint64_t>(it.size, bs));
-  const uint64_t cap = (std::max<uint64_t>(ctx->staging, seg + 16) + 15) & ~15ull;
-  const uint64_t cap_blk = std::max<uint64_t>(cap / 512, 4096);
-  uint64_t fill = scan_ramp() ? std::max<uint64_t>(seg + 16, cap >> 3) : cap;
-
-  size_t ri = 0;
-  uint64_t b0 = 0, b1 = 0;
-  size_t ii = 0;           // the item being packed
-  uint64_t fblk = 0;       // its next block
-  size_t examined = SIZE_MAX;  // the item whose host-side look passed (in this range)
-  Seen seen;
-  bool stopped = false;    // nothing further is packed
-  DirFd cur;               // the packer's directory
-  size_t cur_dir = SIZE_MAX;
-  struct CloseCur {
-    Image& im;
-    DirFd& d;
-    ~CloseCur() { close_dir(im, d); }
-  } close_cur{im, cur};
-  auto dir_of = [&](const Item& it) -> const DirFd& {
-    if (cur_dir != it.dir) {
-      close_dir(im, cur);
-      cur = open_dir(im, im.dirs[it.dir]);
-      cur_dir = it.dir;
-    }
-    return cur;
+  for (const Item& it : items) seg = std::max(seg, std::min<uint64_t>(it.size, im.bs));
+  SlotSizes sz = slot_sizes(ctx->staging, seg, scan_ramp());
+  RangeCursor cur(
+      items.size(), [&](size_t i) { return std::make_pair(items[i].first_blk, items[i].nblk); },
+      ranges, im.nblk_total);
+  Seen seen;             // of the item whose host-side look passed (cur.looked)
+  bool stopped = false;  // nothing further is packed
+  DirCache dir(im);      // the packer's directory
+  // the batch being packed: its first global block, and where each of its
+  // runs starts (ReadJob::tag names the run)
+  struct Seg {
+    size_t item;
+    uint64_t blk, pos;
   };
-  auto start_range = [&](size_t r) {
-    ri = r;
-    b0 = ranges[r].first;
-    b1 = ranges[r].second;
-    // the first item at or past b0, or the file b0 falls inside
-    ii = std::lower_bound(items.begin(), items.end(), b0,
-                          [](const Item& x, uint64_t b) { return x.first_blk < b; }) -
-         items.begin();
-    fblk = 0;
-    if (ii > 0 && items[ii - 1].first_blk + items[ii - 1].nblk > b0) {
-      --ii;
-      fblk = b0 - items[ii].first_blk;
-    }
-    examined = SIZE_MAX;
-  };
-  // is items[ii] (from block fblk on) this range's to look at?
-  auto here = [&] {
-    if (ii >= items.size()) return false;
-    const uint64_t at = items[ii].first_blk + fblk;
-    return at < b1 || (b1 == im.nblk_total && at == b1 && items[ii].nblk == 0);
-  };
+  Batch b;
+  uint64_t first = 0, new_files = 0, file_bytes = 0;
+  std::vector<ReadJob> jobs;
+  std::vector<Seg> segs;
+  // (another device's failure below everything left here ends this one)
   auto more = [&] {
-    if (stopped) return false;
-    while (!here()) {
-      if (ri + 1 >= ranges.size()) return false;
-      start_range(ri + 1);
+    if (stopped || !cur.more()) return false;
+    if (im.decided_before(cur.ui, cur.at())) stopped = true;
+    return !stopped;
+  };
+  auto retire = [&](int, Slot& s) {
+    const uint64_t bad = s.h_cell[0];
+    if (bad == kNone) return;
+    im.report(im.item_of(bad), bad, CIR_CHECK_CHECKSUM, 0, bad);
+    stopped = true;  // what is still in flight lies above it and is only drained
+  };
+  auto pack = [&](int, Slot& s) {
+    b = Batch();
+    first = cur.at();
+    new_files = file_bytes = 0;
+    jobs.clear();
+    segs.clear();
+    while (!stopped && cur.here() && b.n < sz.cap_blk) {
+      const Item& it = items[cur.ui];
+      const DirFd& dfd = dir.of(im.root, it.dir);
+      int err = 0;
+      int kind = CIR_CHECK_OK;
+      if (it.nblk == 0)
+        kind = examine_empty(dfd, it, &err);
+      else if (cur.looked != cur.ui)
+        kind = examine_file(im, dfd, it, &seen, &err);
+      if (kind) {
+        im.report(cur.ui, cur.at(), kind, err);
+        stopped = true;
+        break;
+      }
+      if (it.nblk == 0) {
+        im.n_empty.fetch_add(1);
+        cur.advance(0);
+        continue;
+      }
+      cur.looked = cur.ui;
+      const uint64_t fblk = cur.fblk;
+      const Run r = pack_run(b, sz.fill, sz.cap_blk, im.bs, it.size, fblk, cur.left(), s.h_off,
+                             s.h_len);
+      if (!r.take) break;
+      // the index's digests of these blocks, in block order (nothing comes
+      // back through h_out in this mode: it carries them up)
+      memcpy(s.h_out + 32 * r.at, im.digests(it, fblk), 32 * r.take);
+      cut_pieces(jobs, ReadJob{im.root, it.dir, &it.name, seen, it.size, it.size, fblk * im.bs,
+                               r.bytes, s.h_data + r.pos, segs.size()});
+      segs.push_back({cur.ui, r.at, r.pos});
+      if (fblk == 0) ++new_files;
+      file_bytes += r.bytes;
+      cur.advance(r.take);
     }
-    return true;
+    return b.n > 0;
   };
-  auto busy = [&] {
-    for (const Slot& s : d.slot)
-      if (s.busy) return true;
-    return false;
-  };
-  auto fail_here = [&](int kind, int err) {
-    Failure f;
-    f.item = ii;
-    f.blk = items[ii].first_blk + fblk;
-    f.kind = kind;
-    f.err = err;
-    im.report(f);
+  // The first job (in job order, whatever the timing: a reader skips only
+  // jobs after a failed one) that fails makes READ at its file: the batch
+  // keeps the blocks before that run (any of them may still be the verdict),
+  // nothing further is packed.
+  auto read = [&](int, Slot&) {
+    std::atomic<size_t> bad{jobs.size()};
+    std::mutex mu;
+    int bad_err = 0;
+    run_reads(
+        im, jobs, threads,
+        [&](size_t i, int e) {
+          std::lock_guard<std::mutex> lk(mu);
+          if (i < bad.load()) {
+            bad.store(i);
+            bad_err = e;
+          }
+        },
+        &bad);
+    if (bad.load() == jobs.size()) return;
+    const Seg& g = segs[jobs[bad.load()].tag];
+    im.report(g.item, first + g.blk, CIR_CHECK_READ, bad_err);
     stopped = true;
+    b.n = g.blk;
+    b.used = g.pos;
   };
-  start_range(0);
-  constexpr int kS = Device::kSlots;
-  int k = 0;
-  while (more() || busy()) {
-    Slot& s = d.slot[k];
-    if (s.busy) {
-      int rc = slot_wait(d, s);
-      if (rc) return rc;
-      const uint64_t first = s.h_cell[0];
-      if (first != kNone) {
-        Failure f;
-        f.item = im.item_of(first);
-        f.blk = first;
-        f.kind = CIR_CHECK_CHECKSUM;
-        f.bad_blk = first;
-        im.report(f);
-        stopped = true;  // what is still in flight lies above it and is only drained
-      }
-    }
-    // (another device's failure below everything left here ends this one)
-    if (more() && im.decided_before(ii, items[ii].first_blk + fblk)) stopped = true;
-    if (more()) {
-      int rc = d.ensure_slot(s, cap, cap_blk);
-      if (rc) return rc;
-      rc = d.ensure_check(s);
-      if (rc) return rc;
-      std::vector<ReadJob> jobs;
-      uint64_t pos = 0, n = 0, used = 0;
-      const uint64_t first = items[ii].first_blk + fblk;
-      uint64_t new_files = 0, file_bytes = 0;
-      while (!stopped && here() && n < cap_blk) {
-        const Item& it = items[ii];
-        const DirFd& dfd = dir_of(it);
-        if (it.nblk == 0) {
-          int err = 0;
-          const int kind = examine_empty(dfd, it, &err);
-          if (kind) {
-            fail_here(kind, err);
-            break;
-          }
-          im.n_empty.fetch_add(1);
-          ++ii;
-          continue;
-        }
-        if (examined != ii) {
-          int err = 0;
-          const int kind = examine_file(im, dfd, it, &seen, &err);
-          if (kind) {
-            fail_here(kind, err);
-            break;
-          }
-          examined = ii;
-        }
-        const uint64_t left_blk = std::min<uint64_t>(it.nblk - fblk, b1 - (it.first_blk + fblk));
-        pos = (pos + 15) & ~15ull;
-        if (pos + std::min<uint64_t>(bs, it.size - fblk * bs) > fill) break;
-        uint64_t take = std::min<uint64_t>(left_blk, cap_blk - n);
-        take = std::min<uint64_t>(take, std::max<uint64_t>((fill - pos) / bs, 1));
-        const uint64_t off0 = fblk * bs;
-        const uint64_t bytes = std::min<uint64_t>(take * bs, it.size - off0);
-        if (pos + bytes > fill) break;
-        for (uint64_t j = 0; j < take; ++j) {
-          s.h_off[n + j] = pos + j * bs;
-          s.h_len[n + j] = (uint32_t)std::min<uint64_t>(bs, it.size - off0 - j * bs);
-        }
-        // the index's digests of these blocks, in block order (nothing comes
-        // back through h_out in this mode: it carries them up)
-        memcpy(s.h_out + 32 * n, im.idx->entries[it.entry].hashes.data() + 32 * fblk, 32 * take);
-        for (uint64_t piece = 0; piece < bytes; piece += kReadPiece)
-          jobs.push_back({ii, seen, off0 + piece, std::min<uint64_t>(kReadPiece, bytes - piece),
-                          s.h_data + pos + piece, n, pos});
-        if (fblk == 0) ++new_files;
-        file_bytes += bytes;
-        pos += bytes;
-        used = pos;
-        n += take;
-        fblk += take;
-        if (fblk == it.nblk) {
-          ++ii;
-          fblk = 0;
-        }
-      }
-      fill = std::min(cap, fill * 2);
-      if (n > 0) {
-        int rerr = 0;
-        const size_t bad = run_reads(im, jobs, threads, &rerr);
-        if (bad < jobs.size()) {
-          // READ at that file: the batch keeps the blocks before its segment
-          // (any of them may still be the verdict), nothing further is packed
-          const ReadJob& j = jobs[bad];
-          Failure f;
-          f.item = j.item;
-          f.blk = first + j.seg_blk;
-          f.kind = CIR_CHECK_READ;
-          f.err = rerr;
-          im.report(f);
-          stopped = true;
-          n = j.seg_blk;
-          used = j.seg_pos;
-        }
-      }
-      if (n > 0) {
-        rc = slot_submit_check(d, s, std::max<uint64_t>(used, 16), n, im.ht, first);
-        if (rc) return rc;
-        im.n_files.fetch_add(new_files);
-        im.n_blocks.fetch_add(n);
-        im.n_bytes.fetch_add(file_bytes);
-        im.n_batches.fetch_add(1);
-      }
-    }
-    k = (k + 1) % kS;
-  }
-  return CIR_OK;
+  auto submit = [&](int, Slot& s) -> int {
+    if (b.n == 0) return CIR_OK;
+    const int rc = slot_submit_check(d, s, std::max<uint64_t>(b.used, 16), b.n, im.ht, first);
+    if (rc) return rc;
+    im.n_files.fetch_add(new_files);
+    im.n_blocks.fetch_add(b.n);
+    im.n_bytes.fetch_add(file_bytes);
+    im.n_batches.fetch_add(1);
+    return CIR_OK;
+  };
+  Laps laps(false);  // (this pipeline prints no trace line)
+  return rotate_slots(d, sz, &Device::ensure_check, laps, more, retire, pack, read, submit);
 }
 
 int check_impl(cir_ctx* ctx, int dirfd, const char* dir, const uint8_t* index, size_t len,
@@ -524,120 +648,35 @@ int check_impl(cir_ctx* ctx, int dirfd, const char* dir, const uint8_t* index, s
   *path_len = 0;
   for (int i = 0; i < CIR_CHECK_STATS_FIELDS; ++i) stats[i] = 0;
   stats[7] = kNone;
-  dirsig::Index idx;
-  std::string err;
-  if (!dirsig::parse(index, len, &idx, &err))
-    return idx.bad_hash_size ? fail(CIR_EHASHSIZE, "hash size is unsupported: " + err)
-                             : fail(CIR_EPARSE, "error parsing index: " + err);
-  if (dirsig::digest_len(idx.header.hash) != 32)
-    return fail(CIR_EHASHSIZE, "hash size is unsupported");
-  if (idx.header.block_size > 0xffffffffull)
-    return fail(CIR_EINVAL, "block_size must be in 1 .. 2^32-1");
   Image im;
-  im.idx = &idx;
-  im.bs = idx.header.block_size;
-  im.ht = idx.header.hash == dirsig::HashType::kSha512_256 ? CIR_HASH_SHA512_256
-                                                            : CIR_HASH_BLAKE2B_256;
-  // the entries' places: directory lines as components, files with the
-  // global index of their first block
-  for (size_t e = 0; e < idx.entries.size(); ++e) {
-    const dirsig::Entry& en = idx.entries[e];
-    if (en.kind == dirsig::EntryKind::kDir) {
-      std::vector<std::string> comps;
-      size_t i = 0;
-      while (i < en.path.size()) {
-        size_t j = en.path.find('/', i);
-        if (j == std::string::npos) j = en.path.size();
-        if (j > i) comps.push_back(en.path.substr(i, j - i));
-        i = j + 1;
-      }
-      im.dirs.push_back(std::move(comps));
-    } else if (en.kind == dirsig::EntryKind::kFile) {
-      if (im.dirs.empty()) return fail(CIR_EPARSE, "error parsing index: entry before a directory");
-      Item it;
-      it.entry = e;
-      it.dir = im.dirs.size() - 1;
-      it.name = en.path.substr(en.path.rfind('/') + 1);
-      it.size = en.size;
-      it.nblk = en.hashes.size() / 32;
-      it.first_blk = im.nblk_total;
-      im.nblk_total += it.nblk;
-      im.items.push_back(std::move(it));
-    }
-    // symlink entries are the caller's to create (commit.rs:118-126)
-  }
-  struct CloseRoot {
-    Image& im;
-    bool own = false;
-    ~CloseRoot() {
-      if (own) im.fds.close(im.root);
-    }
-  } close_root{im};
-  if (dir) {
-    im.root = im.fds.took(::openat(dirfd, dir, O_RDONLY | O_DIRECTORY | O_CLOEXEC));
-    if (im.root < 0)
-      return fail(CIR_EIO, std::string("error opening image ") + dir + ": " + strerror(errno));
-    close_root.own = true;
-  } else {
-    struct stat st;
-    if (::fstat(dirfd, &st) != 0 || !S_ISDIR(st.st_mode))
-      return fail(CIR_EIO, "image root fd is not a directory");
-    im.root = dirfd;
-  }
-  if (threads == 0) threads = host_copy_threads(ctx->devs.size());
-
-  int rc = CIR_OK;
-  const size_t nd = std::min<size_t>(ctx->devs.size(), (size_t)std::max<uint64_t>(im.nblk_total, 1));
+  int rc = load_index(index, len, &im);
+  if (rc) return rc;
+  rc = open_image(im, dirfd, dir);
+  if (rc) return rc;
   if (im.nblk_total == 0) {
     // only size-0 entries (or none): nothing for a device
-    DirFd cur;
-    size_t cur_dir = SIZE_MAX;
+    DirCache cur(im);
     for (size_t i = 0; i < im.items.size(); ++i) {
       const Item& it = im.items[i];
-      if (cur_dir != it.dir) {
-        close_dir(im, cur);
-        cur = open_dir(im, im.dirs[it.dir]);
-        cur_dir = it.dir;
-      }
       int e = 0;
-      const int kind = examine_empty(cur, it, &e);
+      const int kind = examine_empty(cur.of(im.root, it.dir), it, &e);
       if (kind) {
-        Failure f;
-        f.item = i;
-        f.blk = 0;
-        f.kind = kind;
-        f.err = e;
-        im.report(f);
+        im.report(i, 0, kind, e);
         break;
       }
       im.n_empty.fetch_add(1);
     }
-    close_dir(im, cur);
-  } else if (nd <= 1) {
-    rc = check_range(ctx, *ctx->devs[0], im, threads, {{0, im.nblk_total}});
   } else {
-    uint64_t stripe = std::max<uint64_t>(1, ctx->staging / im.bs);
-    if (const char* e = getenv("CIR_DEBUG_STRIPE_BLOCKS"))  // tests: stripes of a few blocks
-      if (atoll(e) > 0) stripe = (uint64_t)atoll(e);
-    const StripePrefix order(im.nblk_total, stripe);
-    std::vector<BlockRanges> dev_ranges(nd);
-    for (size_t st = 0; st < order.stripes(); ++st)
-      dev_ranges[st % nd].push_back({st * stripe, st * stripe + order.stripe_len(st)});
-    const unsigned per = std::max(1u, threads / (unsigned)nd);
-    std::vector<int> rcs(nd, 0);
-    std::vector<std::string> errs(nd);
-    fan_out(nd, [&](size_t i) {
-      rcs[i] = check_range(ctx, *ctx->devs[i], im, per, dev_ranges[i]);
-      if (rcs[i]) errs[i] = cir_last_error();
-    });
-    for (size_t i = 0; i < nd && !rc; ++i)
-      if (rcs[i]) rc = fail(rcs[i], errs[i]);
+    rc = run_striped(ctx, im.nblk_total, im.bs, threads,
+                     [&](size_t, Device& d, unsigned per, const BlockRanges& ranges) {
+                       return check_range(ctx, d, im, per, ranges);
+                     });
   }
   stats[5] = im.fds.peak.load();
   if (rc) return rc;
   const Failure& f = im.best;
   if (f.kind != CIR_CHECK_OK) {
-    const std::string& p = idx.entries[im.items[f.item].entry].path;
+    const std::string& p = im.idx.entries[im.items[f.item].entry].path;
     uint8_t* out = (uint8_t*)malloc(p.size() + 1);
     if (!out) return fail(CIR_ENOMEM, "malloc");
     memcpy(out, p.data(), p.size());
@@ -677,17 +716,13 @@ struct Cand {
   uint64_t first_blk = 0;  // global index of block 0 in the work order
 };
 
-struct Links {
-  const dirsig::Index* idx = nullptr;
-  uint64_t bs = 0;
-  int ht = CIR_HASH_BLAKE2B_256;
-  std::vector<std::vector<std::string>> dirs;
-  std::vector<Item> items;  // every file entry, in index order
-  std::vector<int> root;    // per source: its fd, or -1 with root_err
+// (Layout::nblk_total and Item::first_blk count every file entry's blocks;
+// the candidates' blocks are counted by Cand::first_blk and nblk_cand.)
+struct Links : Layout {
+  std::vector<int> roots;   // per source: its fd, or -1 with root_err
   std::vector<int> root_err;
   std::vector<Cand> cands;  // the non-empty candidates below a root that opened, in work order
-  uint64_t nblk_total = 0;
-  FdCount fds;
+  uint64_t nblk_cand = 0;
   std::mutex mu;
   uint8_t* kind = nullptr;  // per candidate of the caller
   int32_t* err = nullptr;
@@ -705,29 +740,7 @@ struct Links {
       kind[out] = (uint8_t)k;
     }
   }
-  bool exe(const Item& it) const { return idx->entries[it.entry].exe; }
-};
-
-// A directory of one source root, kept while the next candidate needs the same.
-struct LinkDir {
-  DirFd d;
-  uint32_t src = UINT32_MAX;
-  size_t dir = SIZE_MAX;
-  const DirFd& of(Links& L, const Cand& c) {
-    const Item& it = L.items[c.item];
-    if (src != c.src || dir != it.dir) {
-      close_dir_at(L.fds, d);
-      d = open_dir_at(L.fds, L.root[c.src], L.dirs[it.dir]);
-      src = c.src;
-      dir = it.dir;
-    }
-    return d;
-  }
-  void close(Links& L) {
-    close_dir_at(L.fds, d);
-    src = UINT32_MAX;
-    dir = SIZE_MAX;
-  }
+  bool exe(const Item& it) const { return idx.entries[it.entry].exe; }
 };
 
 // The packer's look at a candidate (try_hardlink without the read): READ,
@@ -736,7 +749,7 @@ struct LinkDir {
 int examine_link(Links& L, const DirFd& d, const Item& it, Seen* seen, int* err) {
   int fd = -1;
   struct stat st;
-  const int kind = open_listed_at(L.fds, d, it, &fd, &st, err);
+  const int kind = open_listed(L.fds, d, it.name, &fd, &st, err);
   if (kind) return kind;
   L.fds.close(fd);
   if ((uint64_t)st.st_size != it.size) return CIR_CHECK_CHECKSUM;
@@ -746,218 +759,92 @@ int examine_link(Links& L, const DirFd& d, const Item& it, Seen* seen, int* err)
   return CIR_CHECK_OK;
 }
 
-struct LinkJob {
-  size_t cand;  // index into Links::cands
-  Seen seen;
-  uint64_t file_off, len;
-  uint8_t* dst;
-};
-
-// Read the batch's jobs on `threads` readers.  Every job is tried; a failed
-// one makes READ of its own candidate and of nothing else (its bytes in the
-// slot are then whatever they are: READ wins over what the compare finds).
-void run_link_reads(Links& L, const std::vector<LinkJob>& jobs, unsigned threads) {
-  std::atomic<size_t> next{0};
-  const bool nt = stage_copy_nt();
-  auto worker = [&] {
-    LinkDir dir;
-    for (;;) {
-      const size_t i = next.fetch_add(1);
-      if (i >= jobs.size()) break;
-      const LinkJob& j = jobs[i];
-      const Cand& c = L.cands[j.cand];
-      const Item& it = L.items[c.item];
-      int fd = -1, e = 0;
-      struct stat st;
-      bool ok = open_listed_at(L.fds, dir.of(L, c), it, &fd, &st, &e) == CIR_CHECK_OK;
-      if (ok && (st.st_dev != j.seen.dev || st.st_ino != j.seen.ino ||
-                 (uint64_t)st.st_size != it.size)) {
-        ok = false;  // not the file that was packed
-        e = ESTALE;
-      }
-      uint64_t got = 0;
-      while (ok && got < j.len) {
-        const ssize_t r =
-            pread_staged(fd, j.dst + got, j.len - got, (off_t)(j.file_off + got), nt);
-        if (r < 0 && errno == EINTR) continue;
-        if (r <= 0) {
-          ok = false;
-          e = r == 0 ? ENODATA : errno;  // the file shrank under the read
-          break;
-        }
-        got += (uint64_t)r;
-      }
-      L.fds.close(fd);
-      if (!ok) L.report(c.out, CIR_CHECK_READ, e);
-    }
-    dir.close(L);
-  };
-  parallel_run(std::max(1u, std::min<unsigned>(threads, (unsigned)jobs.size())), worker);
-}
-
 // check_range for the candidates: the block ranges `ranges` (increasing, of
 // the work order's global blocks) on device d.  A candidate is examined by
 // every range that holds some of its blocks; what fails the look is reported
 // and its blocks in the range are passed over.
 int links_range(cir_ctx* ctx, Device& d, Links& L, unsigned threads, const BlockRanges& ranges) {
-  if (ranges.empty()) return CIR_OK;
-  std::lock_guard<std::mutex> lk(d.mu);
-  DeviceGuard guard;
-  CIR_HIP(hipSetDevice(d.id));
-  SlotDrain drain{d};  // an early return leaves no slot busy
   const std::vector<Cand>& cands = L.cands;
-  const uint64_t bs = L.bs;
   uint64_t seg = 0;
-  for (const Cand& c : cands) seg = std::max(seg, std::min<uint64_t>(L.items[c.item].size, bs));
-  const uint64_t cap = (std::max<uint64_t>(ctx->staging, seg + 16) + 15) & ~15ull;
-  const uint64_t cap_blk = std::max<uint64_t>(cap / 512, 4096);
-  uint64_t fill = scan_ramp() ? std::max<uint64_t>(seg + 16, cap >> 3) : cap;
-
-  size_t ri = 0;
-  uint64_t b0 = 0, b1 = 0;
-  size_t ci = 0;               // the candidate being packed
-  uint64_t fblk = 0;           // its next block
-  size_t examined = SIZE_MAX;  // the candidate whose look passed (in this range)
-  Seen seen;
-  LinkDir cur;  // the packer's directory
-  struct CloseCur {
-    Links& L;
-    LinkDir& d;
-    ~CloseCur() { d.close(L); }
-  } close_cur{L, cur};
-  constexpr int kS = Device::kSlots;
-  std::vector<size_t> seg_cand[kS];  // per slot in flight: each segment's candidate (Cand::out)
-  auto start_range = [&](size_t r) {
-    ri = r;
-    b0 = ranges[r].first;
-    b1 = ranges[r].second;
-    ci = std::lower_bound(cands.begin(), cands.end(), b0,
-                          [](const Cand& x, uint64_t b) { return x.first_blk < b; }) -
-         cands.begin();
-    fblk = 0;
-    if (ci > 0 && cands[ci - 1].first_blk + L.items[cands[ci - 1].item].nblk > b0) {
-      --ci;
-      fblk = b0 - cands[ci].first_blk;
-    }
-    examined = SIZE_MAX;
+  for (const Cand& c : cands) seg = std::max(seg, std::min<uint64_t>(L.items[c.item].size, L.bs));
+  SlotSizes sz = slot_sizes(ctx->staging, seg, scan_ramp());
+  RangeCursor cur(
+      cands.size(),
+      [&](size_t i) { return std::make_pair(cands[i].first_blk, L.items[cands[i].item].nblk); },
+      ranges, L.nblk_cand);
+  Seen seen;        // of the candidate whose look passed (cur.looked)
+  DirCache dir(L);  // the packer's directory
+  std::vector<size_t> seg_cand[Device::kSlots];  // per slot in flight: each segment's Cand::out
+  Batch b;
+  uint64_t file_bytes = 0;
+  std::vector<ReadJob> jobs;
+  auto retire = [&](int k, Slot& s) {
+    uint32_t nbad = 0;
+    memcpy(&nbad, s.h_seg_res, 4);
+    if (!nbad) return;
+    const uint8_t* flags = s.h_seg_res + kSegResHead;
+    for (size_t g = 0; g < seg_cand[k].size(); ++g)
+      if (flags[g]) L.report(seg_cand[k][g], CIR_CHECK_CHECKSUM, 0);
   };
-  auto here = [&] { return ci < cands.size() && cands[ci].first_blk + fblk < b1; };
-  auto more = [&] {
-    while (!here()) {
-      if (ri + 1 >= ranges.size()) return false;
-      start_range(ri + 1);
-    }
-    return true;
-  };
-  auto busy = [&] {
-    for (const Slot& s : d.slot)
-      if (s.busy) return true;
-    return false;
-  };
-  start_range(0);
-  // CIR_TRACE: where this device's host thread spent the call
-  const bool trace = trace_enabled();
-  using Clock = std::chrono::steady_clock;
-  double t_wait = 0, t_pack = 0, t_read = 0, t_submit = 0;
-  uint64_t n_batches = 0;
-  auto lap = [&](Clock::time_point& t0, double& acc) {
-    if (!trace) return;
-    const Clock::time_point t1 = Clock::now();
-    acc += std::chrono::duration<double, std::milli>(t1 - t0).count();
-    t0 = t1;
-  };
-  int k = 0;
-  while (more() || busy()) {
-    Slot& s = d.slot[k];
-    Clock::time_point t0 = trace ? Clock::now() : Clock::time_point();
-    if (s.busy) {
-      int rc = slot_wait(d, s);
-      if (rc) return rc;
-      uint32_t nbad = 0;
-      memcpy(&nbad, s.h_seg_res, 4);
-      if (nbad) {
-        const uint8_t* flags = s.h_seg_res + kSegResHead;
-        for (size_t g = 0; g < seg_cand[k].size(); ++g)
-          if (flags[g]) L.report(seg_cand[k][g], CIR_CHECK_CHECKSUM, 0);
-      }
-    }
-    lap(t0, t_wait);
-    if (more()) {
-      int rc = d.ensure_slot(s, cap, cap_blk);
-      if (rc) return rc;
-      rc = d.ensure_links(s);
-      if (rc) return rc;
-      std::vector<LinkJob> jobs;
-      std::vector<size_t>& segs = seg_cand[k];
-      segs.clear();
-      uint64_t pos = 0, n = 0, used = 0, file_bytes = 0;
-      while (here() && n < cap_blk) {
-        const Cand& c = cands[ci];
-        const Item& it = L.items[c.item];
-        const uint64_t left_blk = std::min<uint64_t>(it.nblk - fblk, b1 - (c.first_blk + fblk));
-        if (examined != ci) {
-          int err = 0;
-          const int kind = examine_link(L, cur.of(L, c), it, &seen, &err);
-          if (kind) {
-            L.report(c.out, kind, err);
-            fblk += left_blk;  // its blocks in this range are passed over
-            if (fblk == it.nblk) {
-              ++ci;
-              fblk = 0;
-            }
-            continue;
-          }
-          examined = ci;
+  auto pack = [&](int k, Slot& s) {
+    std::vector<size_t>& segs = seg_cand[k];
+    segs.clear();
+    jobs.clear();
+    b = Batch();
+    file_bytes = 0;
+    while (cur.here() && b.n < sz.cap_blk) {
+      const Cand& c = cands[cur.ui];
+      const Item& it = L.items[c.item];
+      if (cur.looked != cur.ui) {
+        int err = 0;
+        const int kind = examine_link(L, dir.of(L.roots[c.src], it.dir), it, &seen, &err);
+        if (kind) {
+          L.report(c.out, kind, err);
+          cur.advance(cur.left());  // its blocks in this range are passed over
+          continue;
         }
-        pos = (pos + 15) & ~15ull;
-        if (pos + std::min<uint64_t>(bs, it.size - fblk * bs) > fill) break;
-        uint64_t take = std::min<uint64_t>(left_blk, cap_blk - n);
-        take = std::min<uint64_t>(take, std::max<uint64_t>((fill - pos) / bs, 1));
-        const uint64_t off0 = fblk * bs;
-        const uint64_t bytes = std::min<uint64_t>(take * bs, it.size - off0);
-        if (pos + bytes > fill) break;
-        for (uint64_t j = 0; j < take; ++j) {
-          s.h_off[n + j] = pos + j * bs;
-          s.h_len[n + j] = (uint32_t)std::min<uint64_t>(bs, it.size - off0 - j * bs);
-        }
-        // the entry's digests of these blocks travel up through h_out
-        memcpy(s.h_out + 32 * n, L.idx->entries[it.entry].hashes.data() + 32 * fblk, 32 * take);
-        for (uint64_t piece = 0; piece < bytes; piece += kReadPiece)
-          jobs.push_back({ci, seen, off0 + piece, std::min<uint64_t>(kReadPiece, bytes - piece),
-                          s.h_data + pos + piece});
-        file_bytes += bytes;
-        pos += bytes;
-        used = pos;
-        n += take;
-        fblk += take;
-        s.h_seg_end[segs.size()] = (uint32_t)n;  // (at most one segment per block: <= cap_blk)
-        segs.push_back(c.out);
-        if (fblk == it.nblk) {
-          ++ci;
-          fblk = 0;
-        }
+        cur.looked = cur.ui;
       }
-      fill = std::min(cap, fill * 2);
-      lap(t0, t_pack);
-      if (n > 0) {
-        run_link_reads(L, jobs, threads);
-        lap(t0, t_read);
-        rc = slot_submit_links(d, s, std::max<uint64_t>(used, 16), n, L.ht, segs.size());
-        if (rc) return rc;
-        lap(t0, t_submit);
-        ++n_batches;
-        L.n_blocks.fetch_add(n);
-        L.n_bytes.fetch_add(file_bytes);
-        L.n_batches.fetch_add(1);
-      }
+      const uint64_t fblk = cur.fblk;
+      const Run r =
+          pack_run(b, sz.fill, sz.cap_blk, L.bs, it.size, fblk, cur.left(), s.h_off, s.h_len);
+      if (!r.take) break;
+      // the entry's digests of these blocks travel up through h_out
+      memcpy(s.h_out + 32 * r.at, L.digests(it, fblk), 32 * r.take);
+      // a failed read makes READ of its own candidate and of nothing else (its
+      // bytes in the slot are then whatever they are: READ wins over what the
+      // compare finds)
+      cut_pieces(jobs, ReadJob{L.roots[c.src], it.dir, &it.name, seen, it.size, it.size,
+                               fblk * L.bs, r.bytes, s.h_data + r.pos, c.out});
+      s.h_seg_end[segs.size()] = (uint32_t)b.n;  // (at most one segment per block: <= cap_blk)
+      segs.push_back(c.out);
+      file_bytes += r.bytes;
+      cur.advance(r.take);
     }
-    k = (k + 1) % kS;
-  }
-  if (trace)
+    return b.n > 0;
+  };
+  auto read = [&](int, Slot&) {
+    run_reads(L, jobs, threads,
+              [&](size_t i, int e) { L.report(jobs[i].tag, CIR_CHECK_READ, e); });
+  };
+  auto submit = [&](int k, Slot& s) -> int {
+    const int rc = slot_submit_links(d, s, std::max<uint64_t>(b.used, 16), b.n, L.ht,
+                                     seg_cand[k].size());
+    if (rc) return rc;
+    L.n_blocks.fetch_add(b.n);
+    L.n_bytes.fetch_add(file_bytes);
+    L.n_batches.fetch_add(1);
+    return CIR_OK;
+  };
+  Laps laps(trace_enabled());
+  const int rc = rotate_slots(
+      d, sz, &Device::ensure_links, laps, [&] { return cur.more(); }, retire, pack, read, submit);
+  if (rc) return rc;
+  if (laps.on)
     fprintf(stderr,
             "cir check_links dev %d: %llu batches; packer's look and segment table %.2f ms, "
             "reads %.2f ms, submit %.2f ms, waiting for results and flags %.2f ms\n",
-            d.id, (unsigned long long)n_batches, t_pack, t_read, t_submit, t_wait);
+            d.id, (unsigned long long)laps.batches, laps.pack, laps.read, laps.submit, laps.wait);
   return CIR_OK;
 }
 
@@ -975,43 +862,9 @@ int links_impl(cir_ctx* ctx, const uint8_t* index, size_t len, const int* src_di
   };
   for (size_t i = 0; i < nlinks; ++i)
     if (link_src[i] >= nsrc) return fail(CIR_EINVAL, "link_src names no source root");
-  dirsig::Index idx;
-  std::string perr;
-  if (!dirsig::parse(index, len, &idx, &perr))
-    return idx.bad_hash_size ? fail(CIR_EHASHSIZE, "hash size is unsupported: " + perr)
-                             : fail(CIR_EPARSE, "error parsing index: " + perr);
-  if (dirsig::digest_len(idx.header.hash) != 32)
-    return fail(CIR_EHASHSIZE, "hash size is unsupported");
-  if (idx.header.block_size > 0xffffffffull)
-    return fail(CIR_EINVAL, "block_size must be in 1 .. 2^32-1");
   Links L;
-  L.idx = &idx;
-  L.bs = idx.header.block_size;
-  L.ht = idx.header.hash == dirsig::HashType::kSha512_256 ? CIR_HASH_SHA512_256
-                                                           : CIR_HASH_BLAKE2B_256;
-  for (size_t e = 0; e < idx.entries.size(); ++e) {
-    const dirsig::Entry& en = idx.entries[e];
-    if (en.kind == dirsig::EntryKind::kDir) {
-      std::vector<std::string> comps;
-      size_t i = 0;
-      while (i < en.path.size()) {
-        size_t j = en.path.find('/', i);
-        if (j == std::string::npos) j = en.path.size();
-        if (j > i) comps.push_back(en.path.substr(i, j - i));
-        i = j + 1;
-      }
-      L.dirs.push_back(std::move(comps));
-    } else if (en.kind == dirsig::EntryKind::kFile) {
-      if (L.dirs.empty()) return fail(CIR_EPARSE, "error parsing index: entry before a directory");
-      Item it;
-      it.entry = e;
-      it.dir = L.dirs.size() - 1;
-      it.name = en.path.substr(en.path.rfind('/') + 1);
-      it.size = en.size;
-      it.nblk = en.hashes.size() / 32;
-      L.items.push_back(std::move(it));
-    }
-  }
+  const int prc = load_index(index, len, &L);
+  if (prc) return prc;
   for (size_t i = 0; i < nlinks; ++i)
     if (link_file[i] >= L.items.size())
       return fail(CIR_EINVAL, "link_file is past the last file entry");
@@ -1023,36 +876,20 @@ int links_impl(cir_ctx* ctx, const uint8_t* index, size_t len, const int* src_di
   L.err = errs.data();
   for (size_t i = 0; i < nlinks; ++i) kind_out[i] = CIR_CHECK_OK;
   // the roots some candidate names
-  L.root.assign(nsrc, -1);
+  L.roots.assign(nsrc, -1);
   L.root_err.assign(nsrc, 0);
-  std::vector<char> own(nsrc, 0), used(nsrc, 0);
+  std::vector<char> used(nsrc, 0);
   struct CloseRoots {
     Links& L;
-    std::vector<char>& own;
+    const char* const* src_dir;
     ~CloseRoots() {
-      for (size_t j = 0; j < own.size(); ++j)
-        if (own[j]) L.fds.close(L.root[j]);
+      for (size_t j = 0; j < L.roots.size(); ++j)
+        if (src_dir[j]) L.fds.close(L.roots[j]);
     }
-  } close_roots{L, own};
+  } close_roots{L, src_dir};
   for (size_t i = 0; i < nlinks; ++i) used[link_src[i]] = 1;
-  for (size_t j = 0; j < nsrc; ++j) {
-    if (!used[j]) continue;
-    if (src_dir[j]) {
-      L.root[j] = L.fds.took(::openat(src_dirfd[j], src_dir[j], O_RDONLY | O_DIRECTORY | O_CLOEXEC));
-      if (L.root[j] < 0)
-        L.root_err[j] = errno;
-      else
-        own[j] = 1;
-    } else {
-      struct stat st;
-      if (::fstat(src_dirfd[j], &st) != 0)
-        L.root_err[j] = errno;
-      else if (!S_ISDIR(st.st_mode))
-        L.root_err[j] = ENOTDIR;
-      else
-        L.root[j] = src_dirfd[j];
-    }
-  }
+  for (size_t j = 0; j < nsrc; ++j)
+    if (used[j]) L.roots[j] = open_root(L.fds, src_dirfd[j], src_dir[j], &L.root_err[j]);
   // the work order: by root, then by index order
   std::vector<size_t> order(nlinks);
   for (size_t i = 0; i < nlinks; ++i) order[i] = i;
@@ -1060,58 +897,35 @@ int links_impl(cir_ctx* ctx, const uint8_t* index, size_t len, const int* src_di
     return link_src[a] != link_src[b] ? link_src[a] < link_src[b] : link_file[a] < link_file[b];
   });
   {
-    LinkDir cur;
+    DirCache cur(L);
     for (size_t i : order) {
       Cand c;
       c.item = (size_t)link_file[i];
       c.src = link_src[i];
       c.out = i;
       const Item& it = L.items[c.item];
-      if (L.root[c.src] < 0) {
+      if (L.roots[c.src] < 0) {
         L.report(i, CIR_CHECK_READ, L.root_err[c.src]);
       } else if (it.nblk == 0) {
         // a size-0 candidate: an empty regular file of the right mode, seen by the host alone
         Seen seen;
         int e = 0;
-        const int kind = examine_link(L, cur.of(L, c), it, &seen, &e);
+        const int kind = examine_link(L, cur.of(L.roots[c.src], it.dir), it, &seen, &e);
         if (kind) L.report(i, kind, e);
         ++stats[7];
       } else {
-        c.first_blk = L.nblk_total;
-        L.nblk_total += it.nblk;
+        c.first_blk = L.nblk_cand;
+        L.nblk_cand += it.nblk;
         L.cands.push_back(c);
       }
     }
-    cur.close(L);
   }
-  if (threads == 0) threads = host_copy_threads(ctx->devs.size());
   const double ms_roots = ms_since(t_roots);
   const auto t_pipe = std::chrono::steady_clock::now();
-
-  int rc = CIR_OK;
-  const size_t nd = std::min<size_t>(ctx->devs.size(), (size_t)std::max<uint64_t>(L.nblk_total, 1));
-  if (L.nblk_total == 0) {
-    // nothing for a device
-  } else if (nd <= 1) {
-    rc = links_range(ctx, *ctx->devs[0], L, threads, {{0, L.nblk_total}});
-  } else {
-    uint64_t stripe = std::max<uint64_t>(1, ctx->staging / L.bs);
-    if (const char* e = getenv("CIR_DEBUG_STRIPE_BLOCKS"))  // tests: stripes of a few blocks
-      if (atoll(e) > 0) stripe = (uint64_t)atoll(e);
-    const StripePrefix sp(L.nblk_total, stripe);
-    std::vector<BlockRanges> dev_ranges(nd);
-    for (size_t st = 0; st < sp.stripes(); ++st)
-      dev_ranges[st % nd].push_back({st * stripe, st * stripe + sp.stripe_len(st)});
-    const unsigned per = std::max(1u, threads / (unsigned)nd);
-    std::vector<int> rcs(nd, 0);
-    std::vector<std::string> es(nd);
-    fan_out(nd, [&](size_t i) {
-      rcs[i] = links_range(ctx, *ctx->devs[i], L, per, dev_ranges[i]);
-      if (rcs[i]) es[i] = cir_last_error();
-    });
-    for (size_t i = 0; i < nd && !rc; ++i)
-      if (rcs[i]) rc = fail(rcs[i], es[i]);
-  }
+  const int rc = run_striped(ctx, L.nblk_cand, L.bs, threads,
+                             [&](size_t, Device& d, unsigned per, const BlockRanges& ranges) {
+                               return links_range(ctx, d, L, per, ranges);
+                             });
   stats[6] = L.fds.peak.load();
   if (trace_enabled())
     fprintf(stderr,
@@ -1150,16 +964,8 @@ int links_impl(cir_ctx* ctx, const uint8_t* index, size_t len, const int* src_di
 // What the looks and the reads found of a file.
 constexpr uint8_t kLookAbsent = 1, kLookBlocked = 2, kLookShort = 4, kLookLong = 8;
 
-struct Blocks {
-  const dirsig::Index* idx = nullptr;
-  uint64_t bs = 0;
-  int ht = CIR_HASH_BLAKE2B_256;
-  int root = -1;
-  std::vector<std::vector<std::string>> dirs;
-  std::vector<Item> items;   // every file entry, in index order
-  std::vector<size_t> work;  // the non-empty ones (indices into items), in index order
-  uint64_t nblk_total = 0;
-  FdCount fds;
+struct Blocks : Layout {
+  std::vector<size_t> work;  // the non-empty entries (indices into items), in index order
   std::mutex mu;
   // what the looks and the reads found of each file (kLook* bits), and the
   // errno of the first thing that blocked it
@@ -1184,7 +990,7 @@ bool examine_block_file(Blocks& B, const DirFd& d, size_t item, Seen* seen, uint
   const Item& it = B.items[item];
   int fd = -1, e = 0;
   struct stat st;
-  if (open_listed_at(B.fds, d, it, &fd, &st, &e) != CIR_CHECK_OK) {
+  if (open_listed(B.fds, d, it.name, &fd, &st, &e) != CIR_CHECK_OK) {
     B.report(item, look_of_errno(e), e);
     return false;
   }
@@ -1216,60 +1022,6 @@ void examine_block_empty(Blocks& B, const DirFd& d, size_t item) {
     B.report(item, kLookLong);
 }
 
-struct BlockJob {
-  size_t item;
-  Seen seen;
-  uint64_t seen_len;  // the file's length at the packer's look
-  uint64_t file_off, len;
-  uint8_t* dst;
-};
-
-// Read the batch's jobs on `threads` readers.  Every job is tried; a failed
-// one blocks its own file and nothing else.
-void run_block_reads(Blocks& B, const std::vector<BlockJob>& jobs, unsigned threads) {
-  std::atomic<size_t> next{0};
-  const bool nt = stage_copy_nt();
-  auto worker = [&] {
-    DirFd d;  // this reader's directory, kept across the jobs that share it
-    size_t d_dir = SIZE_MAX;
-    for (;;) {
-      const size_t i = next.fetch_add(1);
-      if (i >= jobs.size()) break;
-      const BlockJob& j = jobs[i];
-      const Item& it = B.items[j.item];
-      if (d_dir != it.dir) {
-        close_dir_at(B.fds, d);
-        d = open_dir_at(B.fds, B.root, B.dirs[it.dir]);
-        d_dir = it.dir;
-      }
-      int fd = -1, e = 0;
-      struct stat st;
-      bool ok = open_listed_at(B.fds, d, it, &fd, &st, &e) == CIR_CHECK_OK;
-      if (ok && (st.st_dev != j.seen.dev || st.st_ino != j.seen.ino ||
-                 (uint64_t)st.st_size < j.seen_len)) {
-        ok = false;  // not the file that was packed, or it shrank
-        e = ESTALE;
-      }
-      uint64_t got = 0;
-      while (ok && got < j.len) {
-        const ssize_t r =
-            pread_staged(fd, j.dst + got, j.len - got, (off_t)(j.file_off + got), nt);
-        if (r < 0 && errno == EINTR) continue;
-        if (r <= 0) {
-          ok = false;
-          e = r == 0 ? ENODATA : errno;  // the file shrank under the read
-          break;
-        }
-        got += (uint64_t)r;
-      }
-      B.fds.close(fd);
-      if (!ok) B.report(j.item, kLookBlocked, e);
-    }
-    close_dir_at(B.fds, d);
-  };
-  parallel_run(std::max(1u, std::min<unsigned>(threads, (unsigned)jobs.size())), worker);
-}
-
 // One run of packed blocks: `count` blocks from block `at` of the batch are
 // the global blocks from `global` on.
 struct BitRun {
@@ -1282,180 +1034,89 @@ struct BitRun {
 // file is looked at by every range that holds some of its blocks.
 int blocks_range(cir_ctx* ctx, Device& d, Blocks& B, unsigned threads, const BlockRanges& ranges,
                  uint64_t* have) {
-  if (ranges.empty()) return CIR_OK;
-  std::lock_guard<std::mutex> lk(d.mu);
-  DeviceGuard guard;
-  CIR_HIP(hipSetDevice(d.id));
-  SlotDrain drain{d};  // an early return leaves no slot busy
   const std::vector<size_t>& work = B.work;
   const uint64_t bs = B.bs;
   uint64_t seg = 0;
   for (size_t w : work) seg = std::max(seg, std::min<uint64_t>(B.items[w].size, bs));
-  const uint64_t cap = (std::max<uint64_t>(ctx->staging, seg + 16) + 15) & ~15ull;
-  const uint64_t cap_blk = std::max<uint64_t>(cap / 512, 4096);
-  uint64_t fill = scan_ramp() ? std::max<uint64_t>(seg + 16, cap >> 3) : cap;
-
-  size_t ri = 0;
-  uint64_t b0 = 0, b1 = 0;
-  size_t wi = 0;               // the file being packed (index into work)
-  uint64_t fblk = 0;           // its next block
-  size_t examined = SIZE_MAX;  // the file whose look passed (in this range)
-  Seen seen;
-  uint64_t cur_len = 0;        // its length at that look
-  DirFd cur;                   // the packer's directory
-  size_t cur_dir = SIZE_MAX;
-  struct CloseCur {
-    Blocks& B;
-    DirFd& d;
-    ~CloseCur() { close_dir_at(B.fds, d); }
-  } close_cur{B, cur};
-  auto dir_of = [&](const Item& it) -> const DirFd& {
-    if (cur_dir != it.dir) {
-      close_dir_at(B.fds, cur);
-      cur = open_dir_at(B.fds, B.root, B.dirs[it.dir]);
-      cur_dir = it.dir;
-    }
-    return cur;
+  SlotSizes sz = slot_sizes(ctx->staging, seg, scan_ramp());
+  RangeCursor cur(
+      work.size(),
+      [&](size_t i) { return std::make_pair(B.items[work[i]].first_blk, B.items[work[i]].nblk); },
+      ranges, B.nblk_total);
+  Seen seen;             // of the file whose look passed (cur.looked)
+  uint64_t cur_len = 0;  // and its length at that look
+  DirCache dir(B);       // the packer's directory
+  std::vector<BitRun> runs[Device::kSlots];  // per slot in flight
+  Batch b;
+  uint64_t file_bytes = 0;
+  std::vector<ReadJob> jobs;
+  auto retire = [&](int k, Slot& s) {
+    const uint64_t* bits = reinterpret_cast<const uint64_t*>(s.h_bits + kBitsResHead);
+    for (const BitRun& r : runs[k]) copy_bits(have, r.global, bits, r.at, r.count);
   };
-  constexpr int kS = Device::kSlots;
-  std::vector<BitRun> runs[kS];  // per slot in flight
-  auto start_range = [&](size_t r) {
-    ri = r;
-    b0 = ranges[r].first;
-    b1 = ranges[r].second;
-    wi = std::lower_bound(work.begin(), work.end(), b0,
-                          [&](size_t x, uint64_t b) { return B.items[x].first_blk < b; }) -
-         work.begin();
-    fblk = 0;
-    if (wi > 0 && B.items[work[wi - 1]].first_blk + B.items[work[wi - 1]].nblk > b0) {
-      --wi;
-      fblk = b0 - B.items[work[wi]].first_blk;
-    }
-    examined = SIZE_MAX;
-  };
-  auto here = [&] { return wi < work.size() && B.items[work[wi]].first_blk + fblk < b1; };
-  auto more = [&] {
-    while (!here()) {
-      if (ri + 1 >= ranges.size()) return false;
-      start_range(ri + 1);
-    }
-    return true;
-  };
-  auto busy = [&] {
-    for (const Slot& s : d.slot)
-      if (s.busy) return true;
-    return false;
-  };
-  start_range(0);
-  // CIR_TRACE: where this device's host thread spent the call
-  const bool trace = trace_enabled();
-  using Clock = std::chrono::steady_clock;
-  double t_wait = 0, t_pack = 0, t_read = 0, t_submit = 0;
-  uint64_t n_batches = 0;
-  auto lap = [&](Clock::time_point& t0, double& acc) {
-    if (!trace) return;
-    const Clock::time_point t1 = Clock::now();
-    acc += std::chrono::duration<double, std::milli>(t1 - t0).count();
-    t0 = t1;
-  };
-  int k = 0;
-  while (more() || busy()) {
-    Slot& s = d.slot[k];
-    Clock::time_point t0 = trace ? Clock::now() : Clock::time_point();
-    if (s.busy) {
-      int rc = slot_wait(d, s);
-      if (rc) return rc;
-      const uint64_t* bits = reinterpret_cast<const uint64_t*>(s.h_bits + kBitsResHead);
-      for (const BitRun& r : runs[k]) copy_bits(have, r.global, bits, r.at, r.count);
-    }
-    lap(t0, t_wait);
-    if (more()) {
-      int rc = d.ensure_slot(s, cap, cap_blk);
-      if (rc) return rc;
-      rc = d.ensure_blocks(s);
-      if (rc) return rc;
-      std::vector<BlockJob> jobs;
-      std::vector<BitRun>& rs = runs[k];
-      rs.clear();
-      uint64_t pos = 0, n = 0, used = 0, file_bytes = 0;
-      while (here() && n < cap_blk) {
-        const size_t item = work[wi];
-        const Item& it = B.items[item];
-        const uint64_t in_range = std::min<uint64_t>(it.nblk - fblk, b1 - (it.first_blk + fblk));
-        // its blocks in this range are passed over (their bits stay 0)
-        auto pass_over = [&] {
-          B.n_unread.fetch_add(in_range);
-          fblk += in_range;
-          if (fblk == it.nblk) {
-            ++wi;
-            fblk = 0;
-          }
-        };
-        if (examined != wi) {
-          if (!examine_block_file(B, dir_of(it), item, &seen, &cur_len)) {
-            pass_over();
-            continue;
-          }
-          examined = wi;
-        }
-        // the blocks that lie wholly inside the length the packer saw
-        const uint64_t avail = cur_len >= it.size ? it.nblk : cur_len / bs;
-        if (fblk >= avail) {
-          pass_over();
-          continue;
-        }
-        const uint64_t left_blk = std::min<uint64_t>(avail - fblk, in_range);
-        pos = (pos + 15) & ~15ull;
-        if (pos + std::min<uint64_t>(bs, it.size - fblk * bs) > fill) break;
-        uint64_t take = std::min<uint64_t>(left_blk, cap_blk - n);
-        take = std::min<uint64_t>(take, std::max<uint64_t>((fill - pos) / bs, 1));
-        const uint64_t off0 = fblk * bs;
-        const uint64_t bytes = std::min<uint64_t>(take * bs, it.size - off0);
-        if (pos + bytes > fill) break;
-        for (uint64_t j = 0; j < take; ++j) {
-          s.h_off[n + j] = pos + j * bs;
-          s.h_len[n + j] = (uint32_t)std::min<uint64_t>(bs, it.size - off0 - j * bs);
-        }
-        // the entry's digests of these blocks travel up through h_out
-        memcpy(s.h_out + 32 * n, B.idx->entries[it.entry].hashes.data() + 32 * fblk, 32 * take);
-        for (uint64_t piece = 0; piece < bytes; piece += kReadPiece)
-          jobs.push_back({item, seen, cur_len, off0 + piece,
-                          std::min<uint64_t>(kReadPiece, bytes - piece), s.h_data + pos + piece});
-        if (!rs.empty() && rs.back().at + rs.back().count == n &&
-            rs.back().global + rs.back().count == it.first_blk + fblk)
-          rs.back().count += take;  // (neighbouring files, both complete: one run)
-        else
-          rs.push_back({n, it.first_blk + fblk, take});
-        file_bytes += bytes;
-        pos += bytes;
-        used = pos;
-        n += take;
-        fblk += take;
-        if (fblk == it.nblk) {
-          ++wi;
-          fblk = 0;
-        }
+  auto pack = [&](int k, Slot& s) {
+    std::vector<BitRun>& rs = runs[k];
+    rs.clear();
+    jobs.clear();
+    b = Batch();
+    file_bytes = 0;
+    while (cur.here() && b.n < sz.cap_blk) {
+      const size_t item = work[cur.ui];
+      const Item& it = B.items[item];
+      const uint64_t in_range = cur.left();
+      // the blocks that lie wholly inside the length the packer saw; the
+      // others of this range are passed over (their bits stay 0), and so are
+      // all of them when the look fails
+      uint64_t avail = 0;
+      if (cur.looked == cur.ui ||
+          examine_block_file(B, dir.of(B.root, it.dir), item, &seen, &cur_len)) {
+        cur.looked = cur.ui;
+        avail = cur_len >= it.size ? it.nblk : cur_len / bs;
       }
-      fill = std::min(cap, fill * 2);
-      lap(t0, t_pack);
-      if (n > 0) {
-        run_block_reads(B, jobs, threads);
-        lap(t0, t_read);
-        rc = slot_submit_blocks(d, s, std::max<uint64_t>(used, 16), n, B.ht);
-        if (rc) return rc;
-        lap(t0, t_submit);
-        ++n_batches;
-        B.n_bytes.fetch_add(file_bytes);
-        B.n_batches.fetch_add(1);
+      const uint64_t fblk = cur.fblk;
+      if (fblk >= avail) {
+        B.n_unread.fetch_add(in_range);
+        cur.advance(in_range);
+        continue;
       }
+      const Run r = pack_run(b, sz.fill, sz.cap_blk, bs, it.size, fblk,
+                             std::min<uint64_t>(avail - fblk, in_range), s.h_off, s.h_len);
+      if (!r.take) break;
+      // the entry's digests of these blocks travel up through h_out
+      memcpy(s.h_out + 32 * r.at, B.digests(it, fblk), 32 * r.take);
+      // (a file that grew is fine; one that is another file, or shorter than
+      // the packer saw it, blocks itself and nothing else)
+      cut_pieces(jobs, ReadJob{B.root, it.dir, &it.name, seen, cur_len, UINT64_MAX, fblk * bs,
+                               r.bytes, s.h_data + r.pos, item});
+      if (!rs.empty() && rs.back().at + rs.back().count == r.at &&
+          rs.back().global + rs.back().count == it.first_blk + fblk)
+        rs.back().count += r.take;  // (neighbouring files, both complete: one run)
+      else
+        rs.push_back({r.at, it.first_blk + fblk, r.take});
+      file_bytes += r.bytes;
+      cur.advance(r.take);
     }
-    k = (k + 1) % kS;
-  }
-  if (trace)
+    return b.n > 0;
+  };
+  auto read = [&](int, Slot&) {
+    run_reads(B, jobs, threads, [&](size_t i, int e) { B.report(jobs[i].tag, kLookBlocked, e); });
+  };
+  auto submit = [&](int, Slot& s) -> int {
+    const int rc = slot_submit_blocks(d, s, std::max<uint64_t>(b.used, 16), b.n, B.ht);
+    if (rc) return rc;
+    B.n_bytes.fetch_add(file_bytes);
+    B.n_batches.fetch_add(1);
+    return CIR_OK;
+  };
+  Laps laps(trace_enabled());
+  const int rc = rotate_slots(
+      d, sz, &Device::ensure_blocks, laps, [&] { return cur.more(); }, retire, pack, read, submit);
+  if (rc) return rc;
+  if (laps.on)
     fprintf(stderr,
             "cir check_blocks dev %d: %llu batches; packer's look and run table %.2f ms, "
             "reads %.2f ms, submit %.2f ms, waiting for results and bit runs %.2f ms\n",
-            d.id, (unsigned long long)n_batches, t_pack, t_read, t_submit, t_wait);
+            d.id, (unsigned long long)laps.batches, laps.pack, laps.read, laps.submit, laps.wait);
   return CIR_OK;
 }
 
@@ -1474,68 +1135,17 @@ int blocks_impl(cir_ctx* ctx, int dirfd, const char* dir, const uint8_t* index, 
   auto ms_since = [](std::chrono::steady_clock::time_point t) {
     return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t).count();
   };
-  dirsig::Index idx;
-  std::string perr;
-  if (!dirsig::parse(index, len, &idx, &perr))
-    return idx.bad_hash_size ? fail(CIR_EHASHSIZE, "hash size is unsupported: " + perr)
-                             : fail(CIR_EPARSE, "error parsing index: " + perr);
-  if (dirsig::digest_len(idx.header.hash) != 32)
-    return fail(CIR_EHASHSIZE, "hash size is unsupported");
-  if (idx.header.block_size > 0xffffffffull)
-    return fail(CIR_EINVAL, "block_size must be in 1 .. 2^32-1");
   Blocks B;
-  B.idx = &idx;
-  B.bs = idx.header.block_size;
-  B.ht = idx.header.hash == dirsig::HashType::kSha512_256 ? CIR_HASH_SHA512_256
-                                                           : CIR_HASH_BLAKE2B_256;
-  for (size_t e = 0; e < idx.entries.size(); ++e) {
-    const dirsig::Entry& en = idx.entries[e];
-    if (en.kind == dirsig::EntryKind::kDir) {
-      std::vector<std::string> comps;
-      size_t i = 0;
-      while (i < en.path.size()) {
-        size_t j = en.path.find('/', i);
-        if (j == std::string::npos) j = en.path.size();
-        if (j > i) comps.push_back(en.path.substr(i, j - i));
-        i = j + 1;
-      }
-      B.dirs.push_back(std::move(comps));
-    } else if (en.kind == dirsig::EntryKind::kFile) {
-      if (B.dirs.empty()) return fail(CIR_EPARSE, "error parsing index: entry before a directory");
-      Item it;
-      it.entry = e;
-      it.dir = B.dirs.size() - 1;
-      it.name = en.path.substr(en.path.rfind('/') + 1);
-      it.size = en.size;
-      it.nblk = en.hashes.size() / 32;
-      it.first_blk = B.nblk_total;
-      B.nblk_total += it.nblk;
-      if (it.nblk) B.work.push_back(B.items.size());
-      B.items.push_back(std::move(it));
-    }
-  }
+  int rc = load_index(index, len, &B);
+  if (rc) return rc;
+  const size_t nfiles = B.items.size();
+  for (size_t i = 0; i < nfiles; ++i)
+    if (B.items[i].nblk) B.work.push_back(i);
   // ---- nothing above touched a file or a device
   const double ms_parse = ms_since(t_start);
   const auto t_empty = std::chrono::steady_clock::now();
-  struct CloseRoot {
-    Blocks& B;
-    bool own = false;
-    ~CloseRoot() {
-      if (own) B.fds.close(B.root);
-    }
-  } close_root{B};
-  if (dir) {
-    B.root = B.fds.took(::openat(dirfd, dir, O_RDONLY | O_DIRECTORY | O_CLOEXEC));
-    if (B.root < 0)
-      return fail(CIR_EIO, std::string("error opening image ") + dir + ": " + strerror(errno));
-    close_root.own = true;
-  } else {
-    struct stat st;
-    if (::fstat(dirfd, &st) != 0 || !S_ISDIR(st.st_mode))
-      return fail(CIR_EIO, "image root fd is not a directory");
-    B.root = dirfd;
-  }
-  const size_t nfiles = B.items.size();
+  rc = open_image(B, dirfd, dir);
+  if (rc) return rc;
   const size_t nwords = (size_t)((B.nblk_total + 63) / 64);
   B.look.assign(nfiles, 0);
   B.err.assign(nfiles, 0);
@@ -1556,55 +1166,22 @@ int blocks_impl(cir_ctx* ctx, int dirfd, const char* dir, const uint8_t* index, 
     return fail(CIR_ENOMEM, "malloc");
   // the size-0 entries, by the host alone
   {
-    DirFd cur;
-    size_t cur_dir = SIZE_MAX;
-    for (size_t i = 0; i < nfiles; ++i) {
-      const Item& it = B.items[i];
-      if (it.nblk) continue;
-      if (cur_dir != it.dir) {
-        close_dir_at(B.fds, cur);
-        cur = open_dir_at(B.fds, B.root, B.dirs[it.dir]);
-        cur_dir = it.dir;
-      }
-      examine_block_empty(B, cur, i);
-    }
-    close_dir_at(B.fds, cur);
+    DirCache cur(B);
+    for (size_t i = 0; i < nfiles; ++i)
+      if (!B.items[i].nblk) examine_block_empty(B, cur.of(B.root, B.items[i].dir), i);
   }
-  if (threads == 0) threads = host_copy_threads(ctx->devs.size());
   const double ms_empty = ms_since(t_empty);
   const auto t_pipe = std::chrono::steady_clock::now();
-
-  int rc = CIR_OK;
-  const size_t nd = std::min<size_t>(ctx->devs.size(), (size_t)std::max<uint64_t>(B.nblk_total, 1));
-  if (B.nblk_total == 0) {
-    // nothing for a device
-  } else if (nd <= 1) {
-    rc = blocks_range(ctx, *ctx->devs[0], B, threads, {{0, B.nblk_total}}, outs.have);
-  } else {
-    uint64_t stripe = std::max<uint64_t>(1, ctx->staging / B.bs);
-    if (const char* e = getenv("CIR_DEBUG_STRIPE_BLOCKS"))  // tests: stripes of a few blocks
-      if (atoll(e) > 0) stripe = (uint64_t)atoll(e);
-    const StripePrefix sp(B.nblk_total, stripe);
-    std::vector<BlockRanges> dev_ranges(nd);
-    for (size_t st = 0; st < sp.stripes(); ++st)
-      dev_ranges[st % nd].push_back({st * stripe, st * stripe + sp.stripe_len(st)});
-    const unsigned per = std::max(1u, threads / (unsigned)nd);
-    std::vector<int> rcs(nd, 0);
-    std::vector<std::string> es(nd);
-    // a bitmap per device (stripes do not end on word boundaries); device 0
-    // writes into the result itself
-    std::vector<std::vector<uint64_t>> part(nd);
-    for (size_t i = 1; i < nd; ++i) part[i].assign(nwords, 0);
-    fan_out(nd, [&](size_t i) {
-      rcs[i] = blocks_range(ctx, *ctx->devs[i], B, per, dev_ranges[i],
-                            i ? part[i].data() : outs.have);
-      if (rcs[i]) es[i] = cir_last_error();
-    });
-    for (size_t i = 0; i < nd && !rc; ++i)
-      if (rcs[i]) rc = fail(rcs[i], es[i]);
-    for (size_t i = 1; i < nd; ++i)
-      for (size_t w = 0; w < nwords; ++w) outs.have[w] |= part[i][w];
-  }
+  // a bitmap per device (stripes do not end on word boundaries); device 0
+  // writes into the result itself
+  std::vector<std::vector<uint64_t>> part(ctx->devs.size());
+  rc = run_striped(ctx, B.nblk_total, B.bs, threads,
+                   [&](size_t i, Device& d, unsigned per, const BlockRanges& ranges) {
+                     if (i) part[i].assign(nwords, 0);
+                     return blocks_range(ctx, d, B, per, ranges, i ? part[i].data() : outs.have);
+                   });
+  for (const std::vector<uint64_t>& p : part)
+    for (size_t w = 0; w < p.size(); ++w) outs.have[w] |= p[w];
   stats[8] = B.fds.peak.load();
   if (trace_enabled())
     fprintf(stderr,

@@ -34,6 +34,7 @@
 
 #include "blake2b_host.hpp"
 #include "dirsig.hpp"
+#include "pack.hpp"
 #include "sha512_host.hpp"
 #include "stripes.hpp"
 #include "runtime.hpp"
@@ -302,10 +303,6 @@ static int walk(const std::string& real, const std::string& vpath, unsigned thre
   return emit_plan(root, plan, files);
 }
 
-// Read jobs are cut into pieces of at most this size so that `threads`
-// readers stay busy on trees of large files.
-constexpr uint64_t kReadPiece = 4ull << 20;
-
 static bool trace_on() { return trace_enabled(); }
 
 static double now_ms() {
@@ -387,7 +384,6 @@ using Progress = std::function<int(uint64_t done_blk)>;
 // appended to ctx->stats as a row (include/ciruela_blockhash.h), times in ms
 // since scan_t0 on the host clock; the device's copy stream gets a reference
 // event at the start that maps its HIP event times onto that clock.
-using BlockRanges = std::vector<std::pair<uint64_t, uint64_t>>;
 static int hash_range(cir_ctx* ctx, Device& d, size_t di, const std::vector<ScanFile>& files,
                       uint64_t bs, unsigned threads, int ht, DigestBuf& digests,
                       const BlockRanges& ranges,
@@ -410,18 +406,10 @@ static int hash_range(cir_ctx* ctx, Device& d, size_t di, const std::vector<Scan
     ref_ms = now_ms() - scan_t0;
   }
   std::vector<std::array<double, kScanBatchFields>> rows;
-  // A slot holds at least one block; a block is never longer than the
-  // largest file, so a huge block size over small files does not grow the
-  // slots to the block size.  (A multiple of 16: segments start 16-byte
-  // aligned.)
+  // the slots' sizes and the batches' layout: pack.hpp
   uint64_t seg = 0;
   for (const ScanFile& f : files) seg = std::max(seg, std::min<uint64_t>(f.size, bs));
-  const uint64_t cap = (std::max<uint64_t>(ctx->staging, seg + 16) + 15) & ~15ull;
-  const uint64_t cap_blk = std::max<uint64_t>(cap / 512, 4096);
-  // the first batches ramp up (1/8, 1/4, 1/2 of a slot, then whole slots):
-  // the first upload starts after a short read instead of a whole slot's,
-  // and each read still finishes within the previous upload
-  uint64_t fill = scan_ramp() ? std::max<uint64_t>(seg + 16, cap >> 3) : cap;
+  SlotSizes sz = slot_sizes(ctx->staging, seg, scan_ramp());
   size_t ri = 0;  // the range being packed
   uint64_t b0 = 0, b1 = 0;
   size_t fi = 0;
@@ -495,37 +483,24 @@ static int hash_range(cir_ctx* ctx, Device& d, size_t di, const std::vector<Scan
     const bool clock = trace_on() || stats;
     const double t_wait1 = clock ? now_ms() : 0;
     if (more()) {
-      int rc = d.ensure_slot(s, cap, cap_blk);
+      int rc = d.ensure_slot(s, sz.cap, sz.cap_blk);
       if (rc) return rc;
       std::vector<ReadJob> jobs;
-      uint64_t pos = 0, n = 0;
-      uint64_t used = 0;  // end of the last segment packed (pos may be aligned past it)
+      Batch b;
       const uint64_t first = files[fi].first_blk + fblk;
-      while (more_here() && n < cap_blk) {
+      while (more_here() && b.n < sz.cap_blk) {
         const ScanFile& f = files[fi];
         const uint64_t left_blk = std::min<uint64_t>((f.size + bs - 1) / bs - fblk,
                                                      b1 - (f.first_blk + fblk));
-        pos = (pos + 15) & ~15ull;
-        if (pos + std::min<uint64_t>(bs, f.size - fblk * bs) > fill) break;
         // as many whole blocks of this file as fit
-        uint64_t take = std::min<uint64_t>(left_blk, cap_blk - n);
-        take = std::min<uint64_t>(take, std::max<uint64_t>((fill - pos) / bs, 1));
-        const uint64_t off0 = fblk * bs;
-        const uint64_t bytes = std::min<uint64_t>(take * bs, f.size - off0);
-        if (pos + bytes > fill) break;
-        for (uint64_t j = 0; j < take; ++j) {
-          s.h_off[n + j] = pos + j * bs;
-          s.h_len[n + j] = (uint32_t)std::min<uint64_t>(bs, f.size - off0 - j * bs);
-        }
-        for (uint64_t piece = 0; piece < bytes; piece += kReadPiece)
-          jobs.push_back({fi, off0 + piece, std::min<uint64_t>(kReadPiece, bytes - piece),
-                          s.h_data + pos + piece});
-        pos += bytes;
-        used = pos;
-        n += take;
-        fblk += take;
+        const Run r =
+            pack_run(b, sz.fill, sz.cap_blk, bs, f.size, fblk, left_blk, s.h_off, s.h_len);
+        if (!r.take) break;
+        cut_pieces(jobs, ReadJob{fi, fblk * bs, r.bytes, s.h_data + r.pos});
+        fblk += r.take;
       }
-      fill = std::min(cap, fill * 2);
+      sz.offered();
+      const uint64_t used = b.used, n = b.n;
       const double t_read0 = clock ? now_ms() : 0;
       rc = run_reads(jobs, files, threads);
       if (rc) return rc;
