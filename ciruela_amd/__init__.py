@@ -53,6 +53,12 @@ block_extents                   the same answer merged into extents (one copy_fi
                                 reference has no counterpart
                                 (src/daemon/tracking/progress.rs:129-170)
 Context.match_extents_dev       the mapping and the merge behind it on the device
+block_repeats                   what is left after that: blocks whose digest another block
+                                of the same image carries are copied inside the image
+                                instead of fetched twice; the reference has no
+                                counterpart (src/daemon/tracking/progress.rs:129-170)
+Context.match_repeats_dev       the join behind it on the device: per wanted block the
+                                leader of its digest among the image's own blocks
 index_digests,                  what every consumer of an index starts with: its block
   Context.index_digests_dev     digests as one array and a run record per non-empty
                                 file, parsed on the device (the reference parses the
@@ -76,6 +82,7 @@ __all__ = [
     "check_index", "CheckResult", "link_candidates", "check_links", "LinksResult",
     "check_blocks", "BlocksResult", "block_sources", "SourcesResult",
     "block_extents", "ExtentsResult", "Extent",
+    "block_repeats", "RepeatsResult",
     "index_digests", "IndexDigests",
 ]
 
@@ -344,6 +351,19 @@ class Context:
                                               d_pool_runs, n_pool_runs, n_pool, block_size,
                                               d_want, d_src, d_file, d_block, d_fetch, d_extents,
                                               cap_extents, d_work, work_bytes, d_res, stream))
+
+    def match_repeats_dev(self, d_digests, n, d_table, table_slots, seed, d_match, d_want=0,
+                          d_present=0, d_nmatch=0, stream=0):
+        """The join behind block_repeats on device-resident digests
+        (cir_match_repeats_dev): d_match[g] (device u32) = 2^32-1 when block g
+        is not wanted or leads its digest, else the leader L as an ordinal of
+        a pool of 2n -- L when it is present, n + L when it is a wanted block;
+        *d_nmatch (device u32, optional) = how many are repeats.  d_want /
+        d_present: bitmaps (u64 words, optional).  d_table: table_slots u32 of
+        scratch (a power of two >= match_table_slots(n)) that the call
+        initialises.  All written by the call, on `stream` alone."""
+        _n.check(_n.lib.cir_match_repeats_dev(self._h, d_digests, n, d_want, d_present, d_table,
+                                              table_slots, seed, d_match, d_nmatch, stream))
 
     def index_digests_dev(self, d_text, length, body_off, body_end, block_size, d_digests,
                           cap_blocks, d_runs, cap_runs, d_work, work_bytes, d_res, stream=0):
@@ -975,6 +995,99 @@ def block_extents(index, sources, want=None, skip_files=None, have=None, context
     extents = [Extent(*words[8 * i:8 * i + 8]) for i in range(k)]
     return ExtentsResult(index, sources, nblk.value, extents, fetch,
                          dict(zip(ExtentsResult.STATS_FIELDS, list(stats))), skipped.value)
+
+
+class RepeatsResult:
+    """Answer of block_repeats.  nblk: the index's blocks; extents: Extent
+    tuples in ascending `first`, as block_extents', with both files in the
+    same index: src is the source's class, 0 = present (copy at once), 1 =
+    fetched (copy after the fetch); fetch: the bitmap of the wanted blocks
+    that are not repeats (bytes, laid out as BlocksResult.have: a valid `want`
+    for any sibling call).  copies(): (dst_path, dst_offset, length,
+    src_class, src_path, src_offset) per extent, paths as raw bytes -- one
+    copy_file_range each."""
+
+    __slots__ = ("nblk", "extents", "fetch", "stats", "_index")
+    STATS_FIELDS = ("wanted", "repeats", "bytes_repeated", "took_part", "present",
+                    "dropped_length", "table_slots", "on_device", "extents", "left_to_fetch")
+
+    def __init__(self, index, nblk, extents, fetch, stats):
+        self._index = index      # (split into lines only when copies() is asked for)
+        self.nblk = nblk
+        self.extents = extents
+        self.fetch = fetch
+        self.stats = stats
+
+    @property
+    def repeats(self):
+        return self.stats["repeats"]
+
+    @property
+    def bytes_repeated(self):
+        return self.stats["bytes_repeated"]
+
+    def copies(self):
+        files, bs = _file_blocks(self._index)
+        for e in self.extents:
+            yield (files[e.need_file][0], e.need_block * bs, e.bytes, e.src,
+                   files[e.src_file][0], e.src_block * bs)
+
+    def __repr__(self):
+        return "RepeatsResult(%d extents, %d of %d wanted blocks repeat, %d bytes)" % (
+            len(self.extents), self.stats["repeats"], self.stats["wanted"],
+            self.stats["bytes_repeated"])
+
+
+def _bitmap_words(bits, nwords):
+    """A bitmap given as bytes as the nwords u64 words the library reads (None
+    stays None); a short one is padded with zeros."""
+    if bits is None:
+        return None
+    nbytes = 8 * max(nwords, 1)
+    return (ctypes.c_uint64 * (nbytes // 8)).from_buffer_copy(
+        bytes(bits)[:nbytes].ljust(nbytes, b"\0"))
+
+
+def block_repeats(index, want=None, present=None, context=None):
+    """Which blocks of `index` need not be fetched because the same image
+    holds, or will fetch, a block with the same digest (a vendored directory,
+    one file under two paths, a zero-filled file).  want: the bitmap of the
+    blocks still to be obtained (bytes, bit g & 7 of byte g >> 3, whole u64
+    words; None = all), for example block_extents' fetch; present: the bitmap
+    of the blocks that are in the new directory or will be before any copy is
+    made (None = none; a bit in both means wanted).  With a context the parse,
+    the join and the merge run on its first GPU; without one the same rule
+    runs on the host (no default context is opened).  Returns a RepeatsResult;
+    no file is read and nothing is copied."""
+    if len(index):
+        ptr, keep = _buf(index)
+    else:  # (an empty index is a parse error, not a null argument)
+        keep = ctypes.create_string_buffer(1)
+        ptr = ctypes.cast(keep, ctypes.c_void_p)
+    nwords = 0
+    if want is not None or present is not None:
+        try:
+            files, bs = _file_blocks(index)
+            bs = bs or DEFAULT_BLOCK_SIZE
+            nwords = (sum((size + bs - 1) // bs for _, size, _ in files) + 63) // 64
+        except (ValueError, IndexError):
+            pass  # (not an index: the library says so before it reads a bitmap)
+    wbuf, pbuf = _bitmap_words(want, nwords), _bitmap_words(present, nwords)
+    eo, fo = ctypes.c_void_p(), ctypes.c_void_p()
+    next_, nblk = ctypes.c_size_t(), ctypes.c_uint64()
+    stats = (ctypes.c_uint64 * _n.CIR_REPEATS_STATS_FIELDS)()
+    _n.check(_n.lib.cir_block_repeats(context.handle if context is not None else None, ptr,
+                                      len(index), wbuf, pbuf, ctypes.byref(eo),
+                                      ctypes.byref(next_), ctypes.byref(fo), ctypes.byref(nblk),
+                                      stats))
+    del keep
+    k = next_.value
+    raw_e = _n.take_buffer(eo.value, 8 * _n.CIR_EXTENT_WORDS * k)
+    fetch = bytes(_n.take_buffer(fo.value, 8 * ((nblk.value + 63) // 64)))
+    words = (ctypes.c_uint64 * (_n.CIR_EXTENT_WORDS * k)).from_buffer_copy(raw_e) if k else []
+    extents = [Extent(*words[8 * i:8 * i + 8]) for i in range(k)]
+    return RepeatsResult(index, nblk.value, extents, fetch,
+                         dict(zip(RepeatsResult.STATS_FIELDS, list(stats))))
 
 
 class IndexDigests:

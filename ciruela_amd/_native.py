@@ -58,6 +58,8 @@ CIR_EXTENTS_RES_FIELDS = 6
 CIR_EXTENT_WORDS = 8
 CIR_EXTENTS_OK = 0
 CIR_EXTENTS_CAPACITY = 1
+CIR_REPEATS_STATS_FIELDS = 10
+CIR_REPEATS_MAX_BLOCKS = (1 << 30) - 1
 CIR_INDEX_RES_FIELDS = 5
 CIR_INDEX_STATS_FIELDS = 4
 CIR_INDEX_OK = 0
@@ -186,6 +188,11 @@ _SIGS = {
     "cir_block_extents": (ctypes.c_int, [c_vp, c_vp, ctypes.c_size_t, ctypes.POINTER(c_vp),
                                          c_sizep, ctypes.c_size_t, c_u64p, ctypes.POINTER(c_vp),
                                          c_sizep, ctypes.POINTER(c_vp), c_u64p, c_sizep, c_u64p]),
+    "cir_match_repeats_dev": (ctypes.c_int, [c_vp, c_vp, ctypes.c_size_t, c_vp, c_vp, c_vp,
+                                             ctypes.c_uint64, ctypes.c_uint64, c_vp, c_vp, c_vp]),
+    "cir_block_repeats": (ctypes.c_int, [c_vp, c_vp, ctypes.c_size_t, c_u64p, c_u64p,
+                                         ctypes.POINTER(c_vp), c_sizep, ctypes.POINTER(c_vp),
+                                         c_u64p, c_u64p]),
     "cir_index_frame": (ctypes.c_int, [c_vp, ctypes.c_size_t, ctypes.POINTER(ctypes.c_int), c_u64p,
                                        c_u64p, c_u64p]),
     "cir_index_work_bytes": (ctypes.c_uint64, [ctypes.c_uint64]),

@@ -44,6 +44,14 @@
 //       line of the same form per extent (one copy_file_range each), behind
 //       a summary line that also counts the extents and the blocks left to
 //       fetch.
+//   ciruela-index repeats INDEX [--host]
+//       what is left after that: which blocks of INDEX carry a digest that an
+//       earlier block of INDEX carries, so that they are copied inside the
+//       image instead of fetched twice (cir_block_repeats with every block
+//       wanted and none present; no file is read).  Prints one summary line --
+//       blocks, repeats, extents, bytes, left to fetch -- and one line per
+//       extent, `PATH OFFSET LENGTH CLASS SRCPATH SRCOFFSET` (CLASS 1: the
+//       source block is one of those fetched).  --host opens no device.
 #include <dirent.h>
 #include <errno.h>
 #include <fcntl.h>
@@ -70,7 +78,8 @@ static void usage() {
           " [--disk-threads N]\n"
           "       ciruela-index blocks DIR INDEX_FILE [--list] [--disk-threads N]\n"
           "       ciruela-index sources INDEX SRCINDEX [SRCINDEX ...] [--list] [--host]"
-          " [--extents]\n");
+          " [--extents]\n"
+          "       ciruela-index repeats INDEX [--host]\n");
 }
 
 static std::string hex(const uint8_t* p, size_t n) {
@@ -276,7 +285,7 @@ int main(int argc, char** argv) {
     }
     else if (a == "--index-dir") index_dir = val();
     else if (a == "--list" && (cmd == "blocks" || cmd == "sources")) list_blocks = true;
-    else if (a == "--host" && cmd == "sources") host_only = true;
+    else if (a == "--host" && (cmd == "sources" || cmd == "repeats")) host_only = true;
     else if (a == "--extents" && cmd == "sources") extents = true;
     else if (a == "--append" || a == "--append-weak" || a == "--replace") {
       Job j;
@@ -287,7 +296,7 @@ int main(int argc, char** argv) {
       }
       jobs.push_back(j);
     } else if ((cmd == "hash" || cmd == "check" || cmd == "links" || cmd == "blocks" ||
-                cmd == "sources") &&
+                cmd == "sources" || cmd == "repeats") &&
                a.size() &&
                a[0] != '-') {
       files.push_back(a);
@@ -329,10 +338,15 @@ int main(int argc, char** argv) {
       if (!read_file(files[i], &link_indexes.back())) return 2;
     }
   }
+  if (cmd == "repeats" && files.size() != 1) {
+    usage();
+    return 2;
+  }
   std::vector<std::string> inputs = cmd == "links" ? link_dirs : files;
-  if (cmd == "sources") inputs.clear();  // (indexes only: nothing is staged)
+  if (cmd == "sources" || cmd == "repeats") inputs.clear();  // (indexes only: nothing is staged)
   std::vector<uint8_t> check_index;
-  if (cmd == "sources" && !read_file(files[0], &check_index)) return 2;
+  // (read, and a missing one reported, before any device is opened)
+  if ((cmd == "sources" || cmd == "repeats") && !read_file(files[0], &check_index)) return 2;
   if (cmd == "links" && !read_file(files[0], &check_index)) return 2;
   if (cmd == "check" || cmd == "blocks") {
     // the index is read (and a missing one reported) before any device is
@@ -611,6 +625,34 @@ int main(int argc, char** argv) {
     cir_free(bsrc);
     cir_free(bfile);
     cir_free(bblock);
+  } else if (cmd == "repeats") {
+    static const uint8_t none = 0;
+    uint64_t* ext = nullptr;
+    uint64_t* fetch = nullptr;
+    size_t next = 0;
+    uint64_t nblk = 0;
+    uint64_t st[CIR_REPEATS_STATS_FIELDS];
+    rc = cir_block_repeats(ctx, check_index.empty() ? &none : check_index.data(),
+                           check_index.size(), nullptr, nullptr, &ext, &next, &fetch, &nblk, st);
+    if (rc) {
+      die(rc, files[0].c_str());
+      return 2;
+    }
+    printf("repeats: %llu blocks, %llu repeat in %zu extent(s), %llu bytes, %llu left to fetch\n",
+           (unsigned long long)nblk, (unsigned long long)st[1], next, (unsigned long long)st[2],
+           (unsigned long long)st[9]);
+    uint64_t ibs = 0;
+    const std::vector<std::string> paths = index_file_paths(check_index, nullptr, &ibs);
+    for (size_t k = 0; k < next; ++k) {
+      const uint64_t* e = ext + CIR_EXTENT_WORDS * k;
+      if (e[2] >= paths.size() || e[5] >= paths.size()) continue;
+      printf("%s %llu %llu %llu %s %llu\n", paths[e[2]].c_str(), (unsigned long long)(e[3] * ibs),
+             (unsigned long long)e[7], (unsigned long long)e[4], paths[e[5]].c_str(),
+             (unsigned long long)(e[6] * ibs));
+    }
+    fflush(stdout);
+    cir_free(ext);
+    cir_free(fetch);
   } else if (cmd == "sync") {
     if (jobs.empty()) {
       usage();

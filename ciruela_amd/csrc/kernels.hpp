@@ -270,6 +270,21 @@ hipError_t launch_extent_map(const ExtentArgs& a, uint32_t* src, uint64_t* file,
 hipError_t launch_extent_emit(const ExtentArgs& a, uint64_t* ext, uint64_t cap_extents,
                               uint64_t max_extents, uint64_t* work, uint64_t* res, hipStream_t s);
 
+// Join of one digest list with itself (repeats.hip; cir_match_repeats_dev; the
+// rule is repeats.hpp): match[g] = UINT32_MAX when block g is not wanted or is
+// its digest's leader, else the leader as an ordinal of a pool of 2n (L when
+// it is present, n + L when it is wanted); *nmatch (device u32, nullable) =
+// how many are not UINT32_MAX.  want / present: bitmaps of ceil(n / 64) u64,
+// nullable.  `table` is table_slots u32 of scratch (a power of two >=
+// join_table_slots(n)), initialised here; every match[0 .. n) and the count
+// are written here, all on `s`.  n <= kRepeatMaxBlocks; digests 16-B aligned.
+// tev (nullable, a traced cir_block_repeats): 3 events as launch_join's.
+constexpr uint64_t kRepeatMaxBlocks = 0x3FFFFFFFull;
+hipError_t launch_repeat_join(const uint8_t* digests, uint64_t n, const uint64_t* want,
+                              const uint64_t* present, uint32_t* table, uint64_t table_slots,
+                              uint64_t seed, uint32_t* match, uint32_t* nmatch, hipStream_t s,
+                              const hipEvent_t* tev = nullptr);
+
 // nlanes x `lines` register-only compressions (diagnostic VALU ceiling).
 hipError_t launch_compress_only(uint64_t nlanes, uint32_t lines, uint8_t* out, hipStream_t s);
 

@@ -23,13 +23,11 @@
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
-#include <sys/random.h>
 
-#include <chrono>
-#include <random>
 #include <string>
 #include <vector>
 
+#include "devcall.hpp"
 #include "dirsig.hpp"
 #include "idxscan.hpp"
 #include "runtime.hpp"
@@ -40,13 +38,6 @@ namespace {
 
 static_assert(sources::kMaxPool == dev::kJoinMaxPool && sources::kNone == dev::kJoinEmpty,
               "the host rule and the device join share their limits");
-
-uint64_t draw_seed() {
-  uint64_t s = 0;
-  if (getrandom(&s, sizeof s, 0) == (ssize_t)sizeof s) return s;
-  std::random_device rd;
-  return ((uint64_t)rd() << 32) ^ rd();
-}
 
 int match_dev_impl(const uint8_t* d_need, size_t n_need, const uint8_t* d_pool, size_t n_pool,
                    uint32_t* d_table, uint64_t table_slots, uint64_t seed, uint32_t* d_match,
@@ -115,11 +106,6 @@ struct DevBufs {
   }
 };
 
-using Clock = std::chrono::steady_clock;
-double ms_between(Clock::time_point a, Clock::time_point b) {
-  return std::chrono::duration<double, std::milli>(b - a).count();
-}
-
 struct Laps {
   double upload = 0, build = 0, probe = 0, download = 0;
 };
@@ -169,13 +155,6 @@ int device_join(cir_ctx* ctx, const std::vector<uint8_t>& need, uint64_t n_need,
     laps->download = ms_between(t2, Clock::now());
   }
   return CIR_OK;
-}
-
-// CIR_SOURCES_PARSE=host: with a context, parse every text on the host as
-// before the device parse existed (A/B measurement).
-bool parse_on_host() {
-  const char* v = getenv("CIR_SOURCES_PARSE");
-  return v && strcmp(v, "host") == 0;
 }
 
 // CIR_SOURCES_MAP, read per call: "host" keeps sources::map_matches (and
@@ -295,38 +274,9 @@ struct Text {
   std::vector<idxscan::Run> runs;     // device path: its run table
 };
 
-struct DevSet {
-  std::vector<void*> p;
-  hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
-  ~DevSet() {
-    for (void* q : p)
-      if (q) (void)hipFree(q);
-    for (hipEvent_t e : ev)
-      if (e) (void)hipEventDestroy(e);
-  }
-  int alloc(void** out, size_t bytes) {
-    void* q = nullptr;
-    if (hipMalloc(&q, bytes ? bytes : 16) != hipSuccess) {
-      (void)hipGetLastError();
-      return fail(CIR_ENOMEM, "hipMalloc of the call's buffers");
-    }
-    p.push_back(q);
-    *out = q;
-    return CIR_OK;
-  }
-};
-
 // What an attempt returns besides a CIR_* code (none of those is positive).
 constexpr int kRetry = 1;     // again, with more texts on the host
 constexpr int kHostFlow = 2;  // the host flow decides this call
-
-// Waits for the stream on scope exit: declared behind the host buffers that
-// asynchronous copies write, so none is destroyed with a copy in flight on an
-// error return.
-struct StreamDrain {
-  hipStream_t s;
-  ~StreamDrain() { (void)hipStreamSynchronize(s); }
-};
 
 struct DevLaps {
   double frame = 0, text_upload = 0, count = 0, host_parse = 0, decode = 0, runs_download = 0;

@@ -594,7 +594,7 @@ int cir_match_digests_dev(cir_ctx* ctx, const uint8_t* d_need, size_t n_need,
  * order (the flavour of scan_links' break at :143).  Then the two blocks' lengths, min(bs,
  * size - block * bs) on either side, are compared: if they differ the source index lies or a
  * digest collided, the block is reported as not found and counted in stats[5], and no second
- * candidate is looked for.  Matches inside `index` itself are not looked for.
+ * candidate is looked for.  Matches inside `index` itself are cir_block_repeats' (below).
  *
  * want (may be NULL = every block): a bitmap over the global blocks, bit (g & 63) of word
  * g >> 6, ceil(nblk / 64) words; bits at and past nblk are ignored.  The caller clears the
@@ -735,6 +735,110 @@ int cir_block_extents(cir_ctx* ctx, const uint8_t* index, size_t len,
                       uint64_t** extents_out, size_t* nextents_out, uint64_t** fetch_out,
                       uint64_t* nblk_out, size_t* nskipped_out,
                       uint64_t stats[CIR_EXTENTS_STATS_FIELDS]);
+
+/* ---- blocks repeated inside one image --------------------------------- */
+
+/* The join behind cir_block_repeats, device-resident: which of the n blocks of one index
+ * (d_digests, 32 bytes each, in the global block numbering of cir_check_blocks -- what
+ * cir_index_digests_dev writes) carry a digest that another participating block of the same
+ * index carries, and which block stands for it.  The reference has no counterpart: fill_blocks
+ * queues one Block per (path, offset) (src/daemon/tracking/progress.rs:129-170), so a digest
+ * that occurs twice inside the image is fetched twice.  The rule is ciruela_amd/csrc/
+ * repeats.hpp, one text for the kernels, the host path and its fuzz.
+ *
+ * d_want / d_present (device u64 x ceil(n / 64), each may be NULL): bitmaps, bit (g & 63) of word
+ * g >> 6, bits at and past n ignored.  Block g is wanted when d_want is NULL or its bit is set;
+ * present when it is not wanted, d_present is not NULL and its bit is set (a bit in both means
+ * wanted); a block that is neither takes no part, neither as a source nor as a destination.  A
+ * present block's key is g, a wanted block's 2^31 + g, and the leader of a digest is the block
+ * with the smallest key among the participating blocks with that digest over all 32 bytes: a
+ * present holder beats any wanted one, and among equals the first in index order wins.
+ *
+ * d_match[g] (device u32 x n) = UINT32_MAX when g is not wanted or is its own leader; otherwise
+ * the leader L as an ordinal of a pool of 2n: L when the leader is present, n + L when it is a
+ * wanted block (which will be fetched).  *d_nmatch (device u32, may be NULL) = the number of
+ * entries that are not UINT32_MAX.  So d_match feeds cir_match_extents_dev as it is, with the
+ * need run table twice as the pool's -- the first copy with x = 0, the second with every `first`
+ * raised by n and x = 1, n_pool = 2n: an extent's src is then 0 for a present source and 1 for a
+ * fetched one, and src_file a file ordinal of the same index.
+ *
+ * d_table is table_slots u32 of device scratch that the call initialises itself (table_slots a
+ * power of two >= cir_match_table_slots(n): the table holds at most n entries); the home slot
+ * and the seed are cir_match_digests_dev's, and the result does not depend on the seed.  Like
+ * every *_dev call it allocates nothing, synchronises nothing and runs on `stream` alone (one
+ * memset and two launches, build and probe; no lane waits for another's write and every loop is
+ * bounded by table_slots); ctx may be NULL and is not used.  Every d_match[0 .. n) and the count
+ * are written by the call, nothing past them and nothing past d_table[table_slots); n == 0
+ * writes only the count.
+ *
+ * CIR_EINVAL, decided before any HIP call: a NULL d_digests or d_match with n > 0; a NULL
+ * d_table; d_digests not 16-byte aligned; a bitmap not 8-byte aligned; d_match, d_table or
+ * d_nmatch not 4-byte aligned; table_slots not a power of two or below
+ * cir_match_table_slots(n); n > CIR_REPEATS_MAX_BLOCKS (2n must stay within
+ * cir_match_extents_dev's 2^31 - 1, and 2^31 + g clear of UINT32_MAX). */
+#define CIR_REPEATS_MAX_BLOCKS 0x3FFFFFFF /* 2^30 - 1 */
+int cir_match_repeats_dev(cir_ctx* ctx, const uint8_t* d_digests, size_t n,
+                          const uint64_t* d_want, const uint64_t* d_present,
+                          uint32_t* d_table, uint64_t table_slots, uint64_t seed,
+                          uint32_t* d_match, uint32_t* d_nmatch, void* stream);
+
+/* Which blocks of a new image need not be fetched because the same image holds, or will fetch,
+ * a block with the same digest: a vendored copy of a directory, one shared object under two
+ * paths, a zero-filled file, a file kept under an old and a new name.  The last digest join of
+ * the download path: cir_check_links covers whole files, cir_check_blocks what a partial
+ * directory holds, cir_block_extents the copies in older images; what they leave in the fetch
+ * bitmap is still queued by position.  No file is read and nothing is copied.
+ *
+ * want / present (each may be NULL): the bitmaps of cir_match_repeats_dev over the global blocks
+ * of `index`, ceil(nblk / 64) words.  want: the blocks still to be obtained, for example
+ * cir_block_extents' fetch_out.  present: blocks that are in the new directory, or will be
+ * before any copy below is made -- hardlinked files, cir_check_blocks' 1-bits, blocks covered by
+ * cir_block_extents' extents.
+ *
+ * A wanted block whose digest's leader (above) is another block L is a repeat: it is obtained by
+ * copying block L of the same image.  The two blocks' lengths min(bs, size - block x bs) are
+ * compared first: if they differ the index lies or a digest collided, the block is counted in
+ * stats[5], stays in the fetch bitmap, and no second candidate is looked for (cir_block_sources'
+ * rule).  Repeats are merged into extents exactly as cir_match_extents_dev merges copies: a
+ * stretch continues while the blocks are consecutive repeats inside one file whose leaders are
+ * consecutive blocks of one file and of one class, all present or all fetched; two repeats of
+ * the same leader break it, so a zero-filled file of k blocks gives one fetched block and k - 1
+ * one-block extents.  A leader is never a repeat, so no block is both a source and a
+ * destination: extents of one class can be applied in any order, and a copy inside one file
+ * never overlaps.  With nothing dropped, the blocks left to fetch have pairwise distinct
+ * digests, none of them a present block's.
+ *
+ * *extents_out = malloc'd records of CIR_EXTENT_WORDS u64 as cir_block_extents', ascending
+ * `first` (cir_free; NULL when *nextents_out == 0): src = 0 when the source block is present
+ * (copy at once, after the local copies), 1 when it is fetched (copy after the fetch); src_file
+ * = a file ordinal of `index`.  *fetch_out = the malloc'd bitmap of the wanted blocks that are
+ * not repeats, ceil(*nblk_out / 64) words (cir_free; NULL when *nblk_out == 0): a valid `want`
+ * for any sibling call.
+ *
+ * With ctx == NULL the host parser and a hash map in which the smaller key wins apply the rule,
+ * then map_matches and extents_of of ciruela_amd/csrc/sources.hpp; no GPU is needed.  With a
+ * context the call runs on the context's first device under that device's lock (buffers are
+ * allocated for the call and freed after it, the seed is drawn per call, the current device is
+ * restored): the text is framed on the host and uploaded once, cir_index_digests_dev's kernels
+ * leave the digests and the run table in device memory, the run table comes back (32 bytes per
+ * non-empty file) and goes up doubled with the bitmaps, cir_match_repeats_dev's and
+ * cir_match_extents_dev's kernels run on one stream, one synchronise learns the extent count,
+ * and the records and the bitmap come down; the per-block arrays are not made.  A text the
+ * device declines, and every text under CIR_SOURCES_PARSE=host, takes the host parser and its
+ * digests are uploaded instead.  Both paths give identical output, stats [6] and [7] aside.
+ *
+ * CIR_EINVAL: null index, outputs or stats, or more than CIR_REPEATS_MAX_BLOCKS blocks;
+ * CIR_EPARSE / CIR_EHASHSIZE: `index` does not parse; CIR_ENOMEM.  All are decided before any
+ * join; on error the outputs are NULL / 0 and the stats zero.
+ *
+ * stats: [0] blocks wanted, [1] repeats found, [2] their bytes, [3] blocks that took part, [4] of
+ * those present, [5] dropped because the lengths differ, [6] table slots (0 on the host), [7] 1
+ * if joined on the device, [8] extents, [9] blocks left to fetch = [0] - [1]. */
+#define CIR_REPEATS_STATS_FIELDS 10
+int cir_block_repeats(cir_ctx* ctx, const uint8_t* index, size_t len,
+                      const uint64_t* want, const uint64_t* present,
+                      uint64_t** extents_out, size_t* nextents_out, uint64_t** fetch_out,
+                      uint64_t* nblk_out, uint64_t stats[CIR_REPEATS_STATS_FIELDS]);
 
 /* ---- an index's digests as an array ----------------------------------- */
 
