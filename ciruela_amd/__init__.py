@@ -59,6 +59,10 @@ block_repeats                   what is left after that: blocks whose digest ano
                                 counterpart (src/daemon/tracking/progress.rs:129-170)
 Context.match_repeats_dev       the join behind it on the device: per wanted block the
                                 leader of its digest among the image's own blocks
+file_sources,                   link_candidates' rule with the texts parsed and the files
+  Context.index_files_dev,      joined on the device: file records, a fold of each
+  Context.match_files_dev       file's digests, a table keyed by (source, path)
+                                (src/daemon/metadata/hardlink_sources.rs:107-153)
 index_digests,                  what every consumer of an index starts with: its block
   Context.index_digests_dev     digests as one array and a run record per non-empty
                                 file, parsed on the device (the reference parses the
@@ -83,7 +87,7 @@ __all__ = [
     "check_blocks", "BlocksResult", "block_sources", "SourcesResult",
     "block_extents", "ExtentsResult", "Extent",
     "block_repeats", "RepeatsResult",
-    "index_digests", "IndexDigests",
+    "index_digests", "IndexDigests", "file_sources",
 ]
 
 DEFAULT_BLOCK_SIZE = 32768
@@ -376,6 +380,33 @@ class Context:
         _n.check(_n.lib.cir_index_digests_dev(self._h, d_text, length, body_off, body_end,
                                               block_size, d_digests, cap_blocks, d_runs,
                                               cap_runs, d_work, work_bytes, d_res, stream))
+
+    def index_files_dev(self, d_text, length, body_off, body_end, block_size, d_files,
+                        cap_files, d_work, work_bytes, d_res, off_bias=0, block_bias=0,
+                        stream=0):
+        """A device-resident index text to one record of 4 u64 per file entry
+        (cir_index_files_dev): {name_off + off_bias, dir_off + off_bias, size,
+        (first + block_bias) | exe << 63}, size-0 entries included.  d_res: 4
+        u64 {status, file entries, blocks, first declined line}; d_work:
+        cir_index_files_work_bytes(length) bytes; cap_files = length // 8
+        always suffices.  All written by the call, on `stream` alone."""
+        _n.check(_n.lib.cir_index_files_dev(self._h, d_text, length, body_off, body_end,
+                                            block_size, off_bias, block_bias, d_files, cap_files,
+                                            d_work, work_bytes, d_res, stream))
+
+    def match_files_dev(self, need, pool, d_src_first, nsrc, block_size, seed, d_work,
+                        work_bytes, d_cand_src, d_cand_file, d_res, d_pool_verify=0, stream=0):
+        """The join behind file_sources on device-resident records
+        (cir_match_files_dev).  need / pool: (d_text, text_len, d_files,
+        n_files, d_digests, n_blocks); d_src_first: nsrc + 1 u64, the first pool
+        file ordinal of each source.  d_cand_src[i] (u32; 2^32-1: none) and
+        d_cand_file[i] (u64, the ordinal inside that source) per need file;
+        d_res: 4 u64 {status, candidates, their bytes, need files}.  d_work:
+        cir_match_files_work_bytes(n_need_files, n_pool_files) bytes that the
+        call initialises.  All written by the call, on `stream` alone."""
+        _n.check(_n.lib.cir_match_files_dev(self._h, *need, *pool, d_src_first, nsrc, block_size,
+                                            d_pool_verify, seed, d_work, work_bytes, d_cand_src,
+                                            d_cand_file, d_res, stream))
 
     # ---- asynchronous per-block verify (FetchBlock::poll, fetch_blocks.rs:77)
     def verify_submit(self, data, expected, hash_type=None):
@@ -1387,6 +1418,20 @@ def check_blocks(root, index, threads=0, dir_fd=None, context=None):
     return (context or default_context()).check_blocks(root, index, threads, dir_fd)
 
 
+FILE_SOURCES_STATS = ("files", "candidates", "bytes", "pool_files", "sources_used",
+                      "table_slots", "on_device", "why_host")
+
+
+def file_sources(index, sources, context=None):
+    """link_candidates matched on the GPU (cir_file_sources): the same rule and
+    the same pairs.  With a context the texts are parsed and the files joined
+    on its first GPU; whatever the device cannot answer exactly is answered by
+    the host rule (stats["why_host"] says why: a CIR_FILE_WHY_* code).  Without
+    a context the host rule runs (no default context is opened).  Returns
+    ([(file ordinal, source ordinal)], stats dict)."""
+    return _candidates(index, sources, context, True)
+
+
 def link_candidates(index, sources):
     """scan_links (src/daemon/metadata/hardlink_sources.rs:107-153): for every
     file entry of `index`, the first of `sources` (older images' indexes, best
@@ -1394,6 +1439,10 @@ def link_candidates(index, sources):
     Returns [(file ordinal, source ordinal)], file ordinals counting the
     index's file entries from 0.  A source that does not parse or has another
     hash type or block size takes no part.  Host only."""
+    return _candidates(index, sources, None, False)
+
+
+def _candidates(index, sources, context, with_stats):
     if len(index):
         ptr, keep = _buf(index)
     else:
@@ -1407,16 +1456,29 @@ def link_candidates(index, sources):
     s = ctypes.c_void_p()
     n = ctypes.c_size_t()
     skipped = ctypes.c_size_t()
-    _n.check(_n.lib.cir_link_candidates(ptr, len(index), sp, sl, nsrc, ctypes.byref(f),
-                                        ctypes.byref(s), ctypes.byref(n), ctypes.byref(skipped)))
+    stats = (ctypes.c_uint64 * _n.CIR_FILE_SOURCES_STATS_FIELDS)()
+    if with_stats:
+        _n.check(_n.lib.cir_file_sources(context.handle if context is not None else None, ptr,
+                                         len(index), sp, sl, nsrc, ctypes.byref(f),
+                                         ctypes.byref(s), ctypes.byref(n), ctypes.byref(skipped),
+                                         stats))
+    else:
+        _n.check(_n.lib.cir_link_candidates(ptr, len(index), sp, sl, nsrc, ctypes.byref(f),
+                                            ctypes.byref(s), ctypes.byref(n),
+                                            ctypes.byref(skipped)))
     del keep
-    if not n.value:
-        return []
-    files = list((ctypes.c_uint64 * n.value).from_address(f.value))
-    srcs = list((ctypes.c_uint32 * n.value).from_address(s.value))
-    _n.lib.cir_free(f)
-    _n.lib.cir_free(s)
-    return list(zip(files, srcs))
+    pairs = []
+    if n.value:
+        files = list((ctypes.c_uint64 * n.value).from_address(f.value))
+        srcs = list((ctypes.c_uint32 * n.value).from_address(s.value))
+        _n.lib.cir_free(f)
+        _n.lib.cir_free(s)
+        pairs = list(zip(files, srcs))
+    if not with_stats:
+        return pairs
+    st = dict(zip(FILE_SOURCES_STATS, list(stats)))
+    st["skipped"] = skipped.value
+    return pairs, st
 
 
 def get_hash(index):

@@ -61,6 +61,15 @@ CIR_EXTENTS_CAPACITY = 1
 CIR_REPEATS_STATS_FIELDS = 10
 CIR_REPEATS_MAX_BLOCKS = (1 << 30) - 1
 CIR_INDEX_RES_FIELDS = 5
+CIR_FILE_WORDS = 4
+CIR_FILES_RES_FIELDS = 4
+CIR_FILES_OK = 0
+CIR_FILES_COLLISION = 1
+CIR_FILE_SOURCES_STATS_FIELDS = 8
+CIR_FILE_WHY_DECLINED = 1
+CIR_FILE_WHY_COLLISION = 2
+CIR_FILE_WHY_LIMIT = 3
+CIR_FILE_WHY_ENV = 4
 CIR_INDEX_STATS_FIELDS = 4
 CIR_INDEX_OK = 0
 CIR_INDEX_CAPACITY = 1
@@ -205,6 +214,21 @@ _SIGS = {
                                          ctypes.POINTER(ctypes.c_int), c_u64p,
                                          ctypes.POINTER(c_vp), c_u64p, ctypes.POINTER(c_vp),
                                          c_sizep, c_sizep, c_u64p]),
+    "cir_index_files_work_bytes": (ctypes.c_uint64, [ctypes.c_uint64]),
+    "cir_index_files_dev": (ctypes.c_int, [c_vp, c_vp, ctypes.c_uint64, ctypes.c_uint64,
+                                           ctypes.c_uint64, ctypes.c_uint64, ctypes.c_uint64,
+                                           ctypes.c_uint64, c_vp, ctypes.c_uint64, c_vp,
+                                           ctypes.c_uint64, c_vp, c_vp]),
+    "cir_match_files_work_bytes": (ctypes.c_uint64, [ctypes.c_uint64, ctypes.c_uint64]),
+    "cir_match_files_dev": (ctypes.c_int, [c_vp, c_vp, ctypes.c_uint64, c_vp, ctypes.c_uint64,
+                                           c_vp, ctypes.c_uint64, c_vp, ctypes.c_uint64, c_vp,
+                                           ctypes.c_uint64, c_vp, ctypes.c_uint64, c_vp,
+                                           ctypes.c_uint64, ctypes.c_uint64, c_vp,
+                                           ctypes.c_uint64, c_vp, ctypes.c_uint64, c_vp, c_vp,
+                                           c_vp, c_vp]),
+    "cir_file_sources": (ctypes.c_int, [c_vp, c_vp, ctypes.c_size_t, ctypes.POINTER(c_vp),
+                                        c_sizep, ctypes.c_size_t, ctypes.POINTER(c_vp),
+                                        ctypes.POINTER(c_vp), c_sizep, c_sizep, c_u64p]),
     "cir_debug_compress_only_dev": (ctypes.c_int, [ctypes.c_uint64, ctypes.c_uint32, c_vp, c_vp]),
     "cir_debug_relay_blocks": (ctypes.c_uint64, [ctypes.c_uint64, ctypes.c_uint64]),
     "cir_debug_device_identity": (ctypes.c_int, [ctypes.c_int, ctypes.c_char_p, ctypes.c_size_t,

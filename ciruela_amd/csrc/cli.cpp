@@ -19,7 +19,7 @@
 //       commit.rs:51-117) of the image in DIR against INDEX_FILE: silent and
 //       exit 0 when every listed file matches, else exit 1 with one line,
 //       `checksum: <path>` or `read: <path>: <strerror>`
-//   ciruela-index links INDEX SRCDIR=SRCINDEX [SRCDIR=SRCINDEX ...] [--disk-threads N]
+//   ciruela-index links INDEX SRCDIR=SRCINDEX [SRCDIR=SRCINDEX ...] [--disk-threads N] [--host]
 //       the daemon's hardlink step before a download (scan_links, src/daemon/
 //       metadata/hardlink_sources.rs:107-153, then check_and_hardlink, src/
 //       daemon/disk/public.rs:285-346): which files of the new image INDEX
@@ -27,7 +27,15 @@
 //       SRCINDEX (split at the last `=`), best source first.  Prints
 //       `SRCDIR<TAB>PATH` (the path as the index spells it) for every
 //       candidate that passed the re-hash and the mode test, a summary on
-//       stderr, and exits 0 when the check ran.  Nothing is linked.
+//       stderr, and exits 0 when the check ran.  Nothing is linked.  The
+//       candidates come from cir_file_sources on the context the check uses;
+//       --host takes them from cir_link_candidates (the output is the same).
+//   ciruela-index candidates INDEX SRCINDEX [SRCINDEX ...] [--host]
+//       the first half of that step alone (cir_file_sources; no file is
+//       read): one line `FILE# SRC# PATH` per candidate -- the file ordinal in
+//       INDEX, the ordinal of the first SRCINDEX (best first) that lists the
+//       path with equal exe flag, size and digests, the path as the index
+//       spells it.  --host passes no context and opens no device.
 //   ciruela-index blocks DIR INDEX_FILE [--list] [--disk-threads N]
 //       which blocks of INDEX_FILE the partial image in DIR already holds
 //       (cir_check_blocks); --list prints `PATH OFFSET` per missing block
@@ -75,7 +83,8 @@ static void usage() {
           "       ciruela-index hash [--block-size N] FILE...\n"
           "       ciruela-index check DIR INDEX_FILE [--disk-threads N]\n"
           "       ciruela-index links INDEX SRCDIR=SRCINDEX [SRCDIR=SRCINDEX ...]"
-          " [--disk-threads N]\n"
+          " [--disk-threads N] [--host]\n"
+          "       ciruela-index candidates INDEX SRCINDEX [SRCINDEX ...] [--host]\n"
           "       ciruela-index blocks DIR INDEX_FILE [--list] [--disk-threads N]\n"
           "       ciruela-index sources INDEX SRCINDEX [SRCINDEX ...] [--list] [--host]"
           " [--extents]\n"
@@ -254,7 +263,7 @@ int main(int argc, char** argv) {
   uint32_t threads = 0;
   uint64_t bs = CIR_DEFAULT_BLOCK_SIZE;
   std::string index_dir;
-  bool list_blocks = false, host_only = false, extents = false;
+  bool list_blocks = false, host_only = false, extents = false, host_candidates = false;
   std::vector<Job> jobs;
   std::vector<std::string> files;
   for (int i = 2; i < argc; ++i) {
@@ -285,7 +294,9 @@ int main(int argc, char** argv) {
     }
     else if (a == "--index-dir") index_dir = val();
     else if (a == "--list" && (cmd == "blocks" || cmd == "sources")) list_blocks = true;
-    else if (a == "--host" && (cmd == "sources" || cmd == "repeats")) host_only = true;
+    else if (a == "--host" && (cmd == "sources" || cmd == "repeats" || cmd == "candidates"))
+      host_only = true;
+    else if (a == "--host" && cmd == "links") host_candidates = true;
     else if (a == "--extents" && cmd == "sources") extents = true;
     else if (a == "--append" || a == "--append-weak" || a == "--replace") {
       Job j;
@@ -296,7 +307,7 @@ int main(int argc, char** argv) {
       }
       jobs.push_back(j);
     } else if ((cmd == "hash" || cmd == "check" || cmd == "links" || cmd == "blocks" ||
-                cmd == "sources" || cmd == "repeats") &&
+                cmd == "sources" || cmd == "repeats" || cmd == "candidates") &&
                a.size() &&
                a[0] != '-') {
       files.push_back(a);
@@ -327,7 +338,7 @@ int main(int argc, char** argv) {
       if (!read_file(files[i].substr(eq + 1), &link_indexes.back())) return 2;
     }
   }
-  if (cmd == "sources") {
+  if (cmd == "sources" || cmd == "candidates") {
     // the indexes are read (and a missing one reported) before any device is opened
     if (files.size() < 2) {
       usage();
@@ -343,10 +354,13 @@ int main(int argc, char** argv) {
     return 2;
   }
   std::vector<std::string> inputs = cmd == "links" ? link_dirs : files;
-  if (cmd == "sources" || cmd == "repeats") inputs.clear();  // (indexes only: nothing is staged)
+  if (cmd == "sources" || cmd == "repeats" || cmd == "candidates")
+    inputs.clear();  // (indexes only: nothing is staged)
   std::vector<uint8_t> check_index;
   // (read, and a missing one reported, before any device is opened)
-  if ((cmd == "sources" || cmd == "repeats") && !read_file(files[0], &check_index)) return 2;
+  if ((cmd == "sources" || cmd == "repeats" || cmd == "candidates") &&
+      !read_file(files[0], &check_index))
+    return 2;
   if (cmd == "links" && !read_file(files[0], &check_index)) return 2;
   if (cmd == "check" || cmd == "blocks") {
     // the index is read (and a missing one reported) before any device is
@@ -503,8 +517,12 @@ int main(int argc, char** argv) {
     uint64_t* lf = nullptr;
     uint32_t* ls = nullptr;
     size_t nl = 0, skipped = 0;
-    rc = cir_link_candidates(index, check_index.size(), sidx.data(), slen.data(), sidx.size(), &lf,
-                             &ls, &nl, &skipped);
+    uint64_t fst[CIR_FILE_SOURCES_STATS_FIELDS];
+    rc = host_candidates
+             ? cir_link_candidates(index, check_index.size(), sidx.data(), slen.data(), sidx.size(),
+                                   &lf, &ls, &nl, &skipped)
+             : cir_file_sources(ctx, index, check_index.size(), sidx.data(), slen.data(),
+                                sidx.size(), &lf, &ls, &nl, &skipped, fst);
     if (rc) {
       die(rc, files[0].c_str());
       return 2;
@@ -530,6 +548,36 @@ int main(int argc, char** argv) {
             "skipped\n",
             nl, (unsigned long long)st[0], (unsigned long long)st[1], (unsigned long long)st[2],
             skipped);
+    cir_free(lf);
+    cir_free(ls);
+  } else if (cmd == "candidates") {
+    static const uint8_t none = 0;
+    std::vector<const uint8_t*> sidx;
+    std::vector<size_t> slen;
+    for (const std::vector<uint8_t>& v : link_indexes) {
+      sidx.push_back(v.empty() ? &none : v.data());
+      slen.push_back(v.size());
+    }
+    uint64_t* lf = nullptr;
+    uint32_t* ls = nullptr;
+    size_t nl = 0, skipped = 0;
+    uint64_t fst[CIR_FILE_SOURCES_STATS_FIELDS];
+    rc = cir_file_sources(ctx, check_index.empty() ? &none : check_index.data(), check_index.size(),
+                          sidx.data(), slen.data(), sidx.size(), &lf, &ls, &nl, &skipped, fst);
+    if (rc) {
+      die(rc, files[0].c_str());
+      return 2;
+    }
+    const std::vector<std::string> paths = index_file_paths(check_index);
+    for (size_t i = 0; i < nl; ++i)
+      if (lf[i] < paths.size())
+        printf("%llu %u %s\n", (unsigned long long)lf[i], ls[i], paths[lf[i]].c_str());
+    fflush(stdout);
+    fprintf(stderr,
+            "candidates: %llu files, %zu candidates, %llu bytes; %llu source index(es) used, %zu "
+            "skipped; matched on the %s\n",
+            (unsigned long long)fst[0], nl, (unsigned long long)fst[2], (unsigned long long)fst[4],
+            skipped, fst[6] ? "device" : "host");
     cir_free(lf);
     cir_free(ls);
   } else if (cmd == "sources") {

@@ -1,5 +1,5 @@
 // What the whole-call entry points over index texts share (sources.cpp,
-// repeats.cpp): the per-call seed, the call's device memory, the stream drain
+// repeats.cpp, files.cpp): the per-call seed, the call's device memory, the stream drain
 // and the lap clock.
 #pragma once
 #include <stdlib.h>

@@ -285,6 +285,54 @@ hipError_t launch_repeat_join(const uint8_t* digests, uint64_t n, const uint64_t
                               uint64_t seed, uint32_t* match, uint32_t* nmatch, hipStream_t s,
                               const hipEvent_t* tev = nullptr);
 
+// An index's file entries parsed on the device (files.hip;
+// cir_index_files_dev; the rule is files.hpp): the body of a text as
+// launch_index_digests takes it to one record of 4 u64 per file entry {name_off
+// + off_bias, dir_off + off_bias, size, (first + block_bias) | exe << 63}, at
+// most cap_files, all on `s`.  work: files_work_bytes(len) bytes of scratch;
+// res: 4 u64 {status (kIdx*), file entries, blocks, start of the first
+// declined line or UINT64_MAX}, all initialised here.  check_tokens: a last
+// pass reads every hash token's digits and declines a bad one's line (false: a
+// caller that runs launch_index_emit on the same text has that verdict).
+// Unchecked: as launch_index_digests; cap_files < 2^58.
+inline uint64_t files_work_bytes(uint64_t len) { return 32 * (len / kIdxTile + 2); }
+hipError_t launch_index_files(const uint8_t* text, uint64_t len, uint64_t body_off,
+                              uint64_t body_end, uint64_t bs, uint64_t off_bias,
+                              uint64_t block_bias, uint64_t* files, uint64_t cap_files,
+                              uint64_t* work, uint64_t* res, hipStream_t s,
+                              bool check_tokens = true);
+
+// Join of two file lists (files.hip; cir_match_files_dev): per need file the
+// first source, in order, whose first entry at the file's path has the same exe
+// flag, size and digests: cand_src[i] (UINT32_MAX: none) and cand_file[i] (the
+// file ordinal inside that source; UINT64_MAX: none).  A side is an arena of
+// texts, the file records over it and the flat digests their `first` count
+// into (16-B aligned); pool files are ordered by source, src_first (nsrc + 1
+// u64) the first pool ordinal of each.  pool_verify (nullable: pool.digests):
+// the digests the candidates are verified against.  work:
+// match_files_work_bytes(need.nfiles, pool.nfiles) bytes of scratch, zeroed
+// here; res: 4 u64 {status, candidates, their bytes, need files}, all written
+// here; everything on `s`.  Unchecked: bs != 0, pool.nfiles <= kJoinMaxPool,
+// need.nfiles < 2^32, both block counts < 2^32.  tev (nullable, a traced
+// cir_file_sources): 5 events around the memset, the folds, the build, the
+// probe and the verify.
+struct FilesSide {
+  const uint8_t* text;
+  uint64_t text_len;
+  const uint64_t* recs;
+  uint64_t nfiles;
+  const uint8_t* digests;
+  uint64_t nblocks;
+};
+inline uint64_t match_files_work_bytes(uint64_t n_need_files, uint64_t n_pool_files) {
+  return 16 * (n_need_files + n_pool_files) + 4 * join_table_slots(n_pool_files);
+}
+hipError_t launch_match_files(const FilesSide& need, const FilesSide& pool,
+                              const uint64_t* src_first, uint64_t nsrc, uint64_t bs,
+                              const uint8_t* pool_verify, uint64_t seed, uint64_t* work,
+                              uint32_t* cand_src, uint64_t* cand_file, uint64_t* res, hipStream_t s,
+                              const hipEvent_t* tev = nullptr);
+
 // nlanes x `lines` register-only compressions (diagnostic VALU ceiling).
 hipError_t launch_compress_only(uint64_t nlanes, uint32_t lines, uint8_t* out, hipStream_t s);
 

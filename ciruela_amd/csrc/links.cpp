@@ -18,14 +18,14 @@
 #include <vector>
 
 #include "dirsig.hpp"
+#include "links.hpp"
 #include "runtime.hpp"
 
 namespace cir {
-namespace {
 
 int candidates_impl(const uint8_t* index, size_t len, const uint8_t* const* src_index,
                     const size_t* src_len, size_t nsrc, uint64_t** file_out, uint32_t** src_out,
-                    size_t* n_out, size_t* nskipped_out) {
+                    size_t* n_out, size_t* nskipped_out, uint64_t* counts) {
   if (!index || !file_out || !src_out || !n_out || (nsrc && (!src_index || !src_len)))
     return fail(CIR_EINVAL, "null pointer");
   *file_out = nullptr;
@@ -64,7 +64,9 @@ int candidates_impl(const uint8_t* index, size_t len, const uint8_t* const* src_
       if (en.kind == dirsig::EntryKind::kFile) s.files.emplace(en.path, &en);
   std::vector<uint64_t> files;
   std::vector<uint32_t> srcs;
-  uint64_t ordinal = 0;
+  uint64_t ordinal = 0, bytes = 0, pool_files = 0;
+  for (const Source& s : sources)
+    for (const dirsig::Entry& en : s.idx.entries) pool_files += en.kind == dirsig::EntryKind::kFile;
   for (const dirsig::Entry& en : idx.entries) {
     if (en.kind != dirsig::EntryKind::kFile) continue;
     for (const Source& s : sources) {
@@ -74,12 +76,20 @@ int candidates_impl(const uint8_t* index, size_t len, const uint8_t* const* src_
       if (t.exe == en.exe && t.size == en.size && t.hashes == en.hashes) {
         files.push_back(ordinal);
         srcs.push_back(s.ordinal);
+        bytes += en.size;
         break;
       }
     }
     ++ordinal;
   }
   if (nskipped_out) *nskipped_out = skipped;
+  if (counts) {
+    counts[0] = ordinal;
+    counts[1] = files.size();
+    counts[2] = bytes;
+    counts[3] = pool_files;
+    counts[4] = sources.size();
+  }
   if (files.empty()) return CIR_OK;
   uint64_t* f = (uint64_t*)malloc(files.size() * sizeof(uint64_t));
   uint32_t* s = (uint32_t*)malloc(srcs.size() * sizeof(uint32_t));
@@ -96,7 +106,6 @@ int candidates_impl(const uint8_t* index, size_t len, const uint8_t* const* src_
   return CIR_OK;
 }
 
-}  // namespace
 }  // namespace cir
 
 extern "C" int cir_link_candidates(const uint8_t* index, size_t len,
@@ -104,5 +113,5 @@ extern "C" int cir_link_candidates(const uint8_t* index, size_t len,
                                    size_t nsrc, uint64_t** file_out, uint32_t** src_out,
                                    size_t* n_out, size_t* nskipped_out) try {
   return cir::candidates_impl(index, len, src_index, src_len, nsrc, file_out, src_out, n_out,
-                              nskipped_out);
+                              nskipped_out, nullptr);
 } CIR_CATCH_BOUNDARY

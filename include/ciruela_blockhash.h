@@ -50,6 +50,9 @@
  *                              kernels.  Unset: cir_block_extents on the device,
  *                              cir_block_sources on the device from 16,384
  *                              needed blocks on;
+ *       CIR_LINKS_MATCH=host   cir_file_sources with a context answers with the host
+ *                              rule of cir_link_candidates (A/B measurement; read
+ *                              per call);
  *       CIR_DEBUG_SPLIT=k      (tests) every opened GPU appears k times.
  *       CIR_DEBUG_STRIPE_BLOCKS=n  (tests) a scan over several devices deals
  *                              stripes of n blocks (default: one staging
@@ -921,6 +924,135 @@ int cir_index_digests(cir_ctx* ctx, const uint8_t* index, size_t len, int* hash_
                       uint64_t* block_size, uint8_t** digests_out, uint64_t* nblk_out,
                       uint64_t** runs_out, size_t* nruns_out, size_t* nfiles_out,
                       uint64_t stats[CIR_INDEX_STATS_FIELDS]);
+
+/* ---- hardlink candidates matched on the device ------------------------ */
+
+/* Bytes of device scratch cir_index_files_dev needs for a text of len bytes.  Pure.  (Its text
+ * tile is cir_debug_index_tile_bytes.) */
+uint64_t cir_index_files_work_bytes(uint64_t len);
+
+/* The file entries of an index, parsed on the device: the sibling of cir_index_digests_dev over
+ * the same text and frame (d_text, len, body_off, body_end, block_size as there).  One record of
+ * CIR_FILE_WORDS u64 per file entry, size-0 entries included, at the entry's file ordinal (file
+ * entries only, as in cir_link_candidates): {name_off, dir_off, size, first | exe << 63} = the
+ * text offset of the name's first byte, the offset of the '/' that starts the entry's directory
+ * line, the entry's size, and the global block number of its block 0 (for an empty file the
+ * number the next block would get) with the exe flag in bit 63.  off_bias is added to both
+ * offsets as written and block_bias to `first`, so that the records of several texts that sit in
+ * one device arena address that arena and one digest list.  The reference has no counterpart.
+ *
+ * The lines the device takes are cir_index_digests_dev's (ciruela_amd/csrc/idxscan.hpp, the same
+ * parse of every line's head), and the statuses are its CIR_INDEX_*.  d_res (device,
+ * CIR_FILES_RES_FIELDS u64): [0] the status, [1] file entries, [2] blocks, [3] the offset of the
+ * first declined line's start, or UINT64_MAX.  On CIR_INDEX_OK d_files[0 .. 4 x [1]) is written;
+ * on CIR_INDEX_CAPACITY ([1] > cap_files) the counts are exact and no record is written; on
+ * CIR_INDEX_DECLINED the counts mean nothing.  cap_files = len / 8 always suffices (the shortest
+ * file line is "  a f 0\n").  A last pass reads every hash token's digits, so the two calls never
+ * disagree about a text: a bad hex digit declines its line here as it does there.  Nothing is
+ * written past cap_files records, d_work[work_bytes) or d_res[4), and every d_res word is written
+ * by the call.
+ *
+ * Like every *_dev call it allocates nothing, synchronises nothing and runs on `stream` alone
+ * (one memset of d_res and four launches: count, scan, emit, token check; each tile reports the last
+ * directory line it owns, the scan carries a running maximum across the tiles, and an entry takes
+ * the last directory line at or before it; no workgroup waits for another); ctx may be NULL and
+ * is not used.
+ *
+ * CIR_EINVAL, decided before any HIP call: a null d_text (with len > 0), d_files (with cap_files
+ * > 0), d_work or d_res; any of them not 8-byte aligned; body_off > body_end; body_end > len;
+ * block_size == 0; work_bytes < cir_index_files_work_bytes(len); len > 2^36; cap_files > 2^58. */
+#define CIR_FILE_WORDS 4
+#define CIR_FILES_RES_FIELDS 4
+int cir_index_files_dev(cir_ctx* ctx, const uint8_t* d_text, uint64_t len, uint64_t body_off,
+                        uint64_t body_end, uint64_t block_size, uint64_t off_bias,
+                        uint64_t block_bias, uint64_t* d_files, uint64_t cap_files, void* d_work,
+                        uint64_t work_bytes, uint64_t* d_res, void* stream);
+
+/* Bytes of device scratch cir_match_files_dev needs: 16 per file of either side and 4 per table
+ * slot (cir_match_table_slots(n_pool_files)).  Pure; 0 when a count passes the call's limits. */
+uint64_t cir_match_files_work_bytes(uint64_t n_need_files, uint64_t n_pool_files);
+
+/* The join behind cir_file_sources, device-resident: cir_link_candidates' rule over file records.
+ * Each side is a text arena (d_*_text, *_text_len bytes), the file records over it (d_*_files,
+ * CIR_FILE_WORDS u64 each, what cir_index_files_dev wrote with its biases) and the flat digests
+ * the records' `first` count into (d_*_digests, 32 bytes per block, what cir_index_digests_dev
+ * wrote); the two sides may share an arena.  Pool files are ordered by source, then in index
+ * order; d_src_first (device u64 x (nsrc + 1)) holds the first pool file ordinal of each source
+ * and the pool's file count last.  block_size is the indexes' (a file holds ceil(size /
+ * block_size) blocks).
+ *
+ * For need file i the sources 0 .. nsrc-1 in order: a source matches when the first file entry it
+ * lists at the same path has equal exe flag, size and digests, and the first matching source
+ * makes the candidate: d_cand_src[i] (device u32; UINT32_MAX: none) and d_cand_file[i] (device
+ * u64, the file ordinal inside that source; UINT64_MAX: none).  Two paths are equal when their
+ * decoded directories and their decoded names are equal byte by byte (\x41 equals A); they are
+ * compared over the arenas, never copied.  d_res (device, CIR_FILES_RES_FIELDS u64): [0]
+ * CIR_FILES_OK or CIR_FILES_COLLISION, [1] candidates, [2] the sum of their sizes, [3] need files.
+ *
+ * All on `stream` behind one memset of d_work: fold (each file's 128-bit fold is the sum mod 2^64,
+ * per word, of a term mixed under `seed` from a block's position in its file and its digest;
+ * summed inside the wave over the lanes that share a file, one integer atomic add per wave, file
+ * and word, so the result does not depend on arrival order), build (one lane per pool file into a
+ * table of pool ordinals on cir_match_digests_dev's discipline, keyed by source and decoded path:
+ * the slot of (source, path) ends holding the source's first entry), probe (one lane per need
+ * file; equal exe flag, size and fold stop the search) and verify (one lane per need block of a
+ * file with a candidate: its digest must equal the candidate's at the same position, read from
+ * d_pool_verify -- NULL: d_pool_digests; tests pass another array to reach the status).  A
+ * difference is CIR_FILES_COLLISION and the arrays mean nothing; with CIR_FILES_OK the answer is
+ * exactly the host rule's, whatever the seed.  No lane waits for another and every loop is
+ * bounded by an argument; a path walk reads at most 4096 bytes of each token.  Whatever the
+ * records hold, nothing outside the arrays as sized by the arguments is read or written: records
+ * that do not describe the arrays give an unspecified answer, not a fault.  ctx may be NULL and
+ * is not used.
+ *
+ * CIR_EINVAL, decided before any HIP call: a null array with a non-zero count, a null
+ * d_src_first, d_work or d_res; a digest array not 16-byte aligned; records, d_src_first, d_work,
+ * d_cand_file or d_res not 8-byte aligned; d_cand_src not 4-byte aligned; block_size == 0; more
+ * than 2^31 - 1 pool files, 2^32 - 1 need files or 2^32 - 1 blocks on a side; work_bytes <
+ * cir_match_files_work_bytes(n_need_files, n_pool_files). */
+#define CIR_FILES_OK 0
+#define CIR_FILES_COLLISION 1
+int cir_match_files_dev(cir_ctx* ctx, const uint8_t* d_need_text, uint64_t need_text_len,
+                        const uint64_t* d_need_files, uint64_t n_need_files,
+                        const uint8_t* d_need_digests, uint64_t n_need_blocks,
+                        const uint8_t* d_pool_text, uint64_t pool_text_len,
+                        const uint64_t* d_pool_files, uint64_t n_pool_files,
+                        const uint8_t* d_pool_digests, uint64_t n_pool_blocks,
+                        const uint64_t* d_src_first, uint64_t nsrc, uint64_t block_size,
+                        const uint8_t* d_pool_verify, uint64_t seed, void* d_work,
+                        uint64_t work_bytes, uint32_t* d_cand_src, uint64_t* d_cand_file,
+                        uint64_t* d_res, void* stream);
+
+/* cir_link_candidates with a context: the same arguments, outputs, rule and error codes, and
+ * stats.  With ctx == NULL the host rule runs as in cir_link_candidates and no GPU is needed.
+ * With a context the call runs on the context's first device under that device's lock (buffers
+ * are allocated for the call and freed after it, the seed is drawn per call, the current device
+ * is restored): every text is framed on the host (cir_index_frame's rules); a source whose frame
+ * fails or whose hash type or block size differs is skipped and counted without being uploaded;
+ * the other texts go up once into one arena; cir_index_digests_dev's count pass gives every
+ * text's counts (first synchronise), its emit and decode passes and cir_index_files_dev's
+ * kernels fill shared digest and record buffers with the biases set, cir_match_files_dev's
+ * kernels run behind them, and d_cand_src (4 bytes per file) comes down with the verdicts (second
+ * synchronise) and is compacted into file_out / src_out on the host, a loop per file.
+ *
+ * The whole call is answered by the host rule instead -- outputs, error codes and error texts are
+ * then the host's, and this is never an error -- when the device declines any uploaded text, the
+ * status is CIR_FILES_COLLISION, a count passes a device limit (more than 2^31 - 1 pool files,
+ * 2^32 - 1 need files or pool blocks, a text of more than 2^36 bytes), or CIR_LINKS_MATCH=host is
+ * set.  Both paths give identical output, stats [5] to [7] aside.
+ *
+ * stats: [0] file entries of `index`, [1] candidates, [2] their bytes, [3] pool files, [4] sources
+ * used, [5] table slots (0 on the host), [6] 1 if matched on the device, [7] why not: 0, or a
+ * CIR_FILE_WHY_*. */
+#define CIR_FILE_SOURCES_STATS_FIELDS 8
+#define CIR_FILE_WHY_DECLINED 1  /* the device declined a text */
+#define CIR_FILE_WHY_COLLISION 2 /* two folds collided */
+#define CIR_FILE_WHY_LIMIT 3     /* a count passes a device limit */
+#define CIR_FILE_WHY_ENV 4       /* CIR_LINKS_MATCH=host */
+int cir_file_sources(cir_ctx* ctx, const uint8_t* index, size_t len,
+                     const uint8_t* const* src_index, const size_t* src_len, size_t nsrc,
+                     uint64_t** file_out, uint32_t** src_out, size_t* n_out,
+                     size_t* nskipped_out, uint64_t stats[CIR_FILE_SOURCES_STATS_FIELDS]);
 
 /* ---- index (DIRSIGNATURE.v1) ----------------------------------------- */
 
