@@ -1,15 +1,20 @@
 // What the whole-call entry points over index texts share (sources.cpp,
-// repeats.cpp, files.cpp): the per-call seed, the call's device memory, the stream drain
-// and the lap clock.
+// repeats.cpp, files.cpp, idxscan.cpp): the per-call seed and lap clock, the
+// call's hold on the context's first device (DeviceCall), the trace events,
+// the size test, the two device parses of index texts (TextSet: k framed
+// texts in two passes; parse_one_text: one text in one shot) and the extent
+// tail on the device.  The bodies are devcall.cpp.
 #pragma once
 #include <stdlib.h>
 #include <string.h>
 #include <sys/random.h>
 
 #include <chrono>
+#include <mutex>
 #include <random>
 #include <vector>
 
+#include "idxscan.hpp"
 #include "runtime.hpp"
 
 namespace cir {
@@ -33,14 +38,35 @@ inline bool parse_on_host() {
   return v && strcmp(v, "host") == 0;
 }
 
+// May an index text of len bytes be parsed on the device?  (The kernels'
+// limit, and u32 block ordinals.)
+inline bool device_takes(size_t len) {
+  return len <= dev::kIdxMaxLen && len / idxscan::kTokenBytes <= 0xFFFFFFFFull;
+}
+
+// N events for a traced call's kernel laps; none exists until create().
+template <int N>
+struct TraceEvents {
+  hipEvent_t ev[N] = {};
+  ~TraceEvents() {
+    for (hipEvent_t e : ev)
+      if (e) (void)hipEventDestroy(e);
+  }
+  int create() {
+    for (hipEvent_t& e : ev) CIR_HIP(hipEventCreate(&e));
+    return CIR_OK;
+  }
+  float lap(int i) const {  // ev[i] to ev[i + 1] in ms, 0 when it cannot be read
+    float f = 0;
+    return hipEventElapsedTime(&f, ev[i], ev[i + 1]) == hipSuccess ? f : 0;
+  }
+};
+
 struct DevSet {
   std::vector<void*> p;
-  hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
   ~DevSet() {
     for (void* q : p)
       if (q) (void)hipFree(q);
-    for (hipEvent_t e : ev)
-      if (e) (void)hipEventDestroy(e);
   }
   int alloc(void** out, size_t bytes) {
     void* q = nullptr;
@@ -54,12 +80,91 @@ struct DevSet {
   }
 };
 
-// Waits for the stream on scope exit: declared behind the host buffers that
-// asynchronous copies write, so none is destroyed with a copy in flight on an
-// error return.
+// Waits for the stream on scope exit, so that no host buffer is destroyed and
+// no device buffer freed with a copy in flight on an error return.
 struct StreamDrain {
   hipStream_t s;
   ~StreamDrain() { (void)hipStreamSynchronize(s); }
 };
+
+// A call's hold on the context's first device (the caller has checked that
+// there is one, where it checks).  The members' order is the call's epilogue
+// in reverse: drain the stream, free the call's device memory, restore the
+// caller's device, unlock.  Host buffers that asynchronous copies read or
+// write are declared before it, so they outlive the drain.
+struct DeviceCall {
+  Device& d;
+  std::unique_lock<std::mutex> lk;
+  DeviceGuard guard;
+  hipStream_t s;
+  DevSet b;
+  StreamDrain drain;
+  explicit DeviceCall(cir_ctx* ctx) : d(*ctx->devs[0]), lk(d.mu), s(d.compute), drain{s} {}
+  int begin() {  // first, and once
+    CIR_HIP(hipSetDevice(d.id));
+    return CIR_OK;
+  }
+  // Around the host parse of a text the device declined: the stream is idle
+  // then and the buffers are this call's own.
+  void unlock() { lk.unlock(); }
+  void lock() { lk.lock(); }
+  template <class T>
+  int alloc(T** out, size_t bytes) {
+    return b.alloc((void**)out, bytes);
+  }
+};
+
+// The two-pass device parse of k framed texts that share a block size, into
+// digest buffers of exactly the counted size.  It owns the host memory its
+// copies write, so it is declared before the DeviceCall it works on.
+struct TextSet {
+  struct Item {
+    const uint8_t* p;
+    size_t len, body_off, body_end;
+    uint64_t text_off, work_off, runs_off;  // bytes / bytes / records in the buffers
+    uint64_t cnt[CIR_INDEX_RES_FIELDS];     // the count pass's result words
+    std::vector<idxscan::Run> runs;         // after finish(c, true)
+  };
+  std::vector<Item> item;
+  uint64_t text_bytes = 0, work_bytes = 0, run_recs = 0;
+  uint8_t* d_text = nullptr;
+  uint8_t* d_work = nullptr;
+  uint64_t* d_res = nullptr;
+  uint64_t* d_runs = nullptr;
+  std::vector<uint64_t> res;                  // the result words as last downloaded
+  Clock::time_point t_bufs, t_up, t_counted;  // buffers there / texts up / counts in
+
+  size_t add(const uint8_t* p, size_t len, size_t body_off, size_t body_end);
+  // Allocates the texts' buffers (the text buffer with text_slack bytes to
+  // spare), uploads, runs the count pass, downloads item[i].cnt, synchronises.
+  // An empty set allocates and copies nothing.
+  int count(DeviceCall& c, uint64_t bs, size_t text_slack, bool trace);
+  bool counted_ok(size_t i) const { return item[i].cnt[0] == CIR_INDEX_OK; }
+  // Queues text i's emit pass: max_blocks digests to d_digests.
+  int emit(DeviceCall& c, size_t i, uint8_t* d_digests, uint64_t max_blocks);
+  // Queues the download of the verdicts, with the run table of every text the
+  // count pass took if with_runs, and synchronises.
+  int finish(DeviceCall& c, bool with_runs);
+  uint64_t status(size_t i) const { return res[CIR_INDEX_RES_FIELDS * i]; }
+
+ private:
+  uint64_t bs_ = 0;
+};
+
+// The one-shot device parse of one framed text: upload, launch_index_digests
+// into capacity-sized buffers of c, res downloaded, one synchronise.
+int parse_one_text(DeviceCall& c, const uint8_t* text, size_t len, uint64_t body_off,
+                   uint64_t body_end, uint64_t bs, uint64_t res[CIR_INDEX_RES_FIELDS],
+                   uint8_t** d_digests, uint64_t** d_runs);
+
+// The extent tail on the device, behind launch_extent_map(a, ..., d_fetch, ~0,
+// d_work, d_xres) and the synchronise that learnt `count`, its x_res[5]: the
+// records are allocated exactly, emitted and downloaded with the fetch
+// bitmap.  *rec (null when count is 0) and *fetch are malloc'd and the
+// caller's; on failure the stream is drained before they are freed.
+// lap_emit: synchronise behind the emit kernels, for *t_emit (a traced call).
+int device_extent_tail(DeviceCall& c, const dev::ExtentArgs& a, uint64_t count, uint64_t* d_work,
+                       uint64_t* d_xres, const uint64_t* d_fetch, bool lap_emit, uint64_t** rec,
+                       uint64_t** fetch, Clock::time_point* t_emit);
 
 }  // namespace cir

@@ -9,7 +9,10 @@
 // digests already are: the records, the path hash and the fold are files.hpp,
 // the kernels files.hip and idxscan.hip.  Whatever the device cannot answer
 // exactly -- a text it declines, a collided fold, a count past a limit -- is
-// answered by the host rule, unchanged.
+// answered by the host rule, unchanged.  The hold on the device and the
+// two-pass parse of the texts are devcall.hpp's (DeviceCall, TextSet); the
+// file records' scratch and results, and the policy -- any text declined sends
+// the whole call to the host rule, with a reason -- are here.
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -111,19 +114,12 @@ struct Outs {
   uint64_t* stats;
 };
 
-// One text of the call on the device.
+// One text of the call on the device, beside its TextSet item.
 struct Text {
-  const uint8_t* p = nullptr;
-  size_t len = 0;
-  size_t body_off = 0, body_end = 0;
   uint32_t ordinal = 0;  // the source's, as the caller counts
-  uint64_t text_off = 0, iwork_off = 0, fwork_off = 0, runs_off = 0;
+  uint64_t fwork_off = 0;
   uint64_t nfiles = 0, nblk = 0;
 };
-
-bool device_takes(size_t len) {
-  return len <= dev::kIdxMaxLen && len / idxscan::kTokenBytes <= 0xFFFFFFFFull;
-}
 
 // With a context: on its first device, under that device's lock.  Returns a
 // CIR_* code, or kHostFlow with *why set and nothing reported.
@@ -135,84 +131,51 @@ int file_sources_dev(cir_ctx* ctx, const uint8_t* index, size_t len,
   const auto t0 = Clock::now();
   dirsig::Header h;
   std::string err;
-  std::vector<Text> tx(1);  // the new index, then the sources that take part
-  tx[0].p = index;
-  tx[0].len = len;
+  // host memory that asynchronous copies read or write: declared before the call
+  TextSet ts;  // the new index, then the sources that take part
+  std::vector<Text> tx(1);  // (tx[k] goes with ts.item[k])
+  size_t body_off = 0, body_end = 0;
   *why = kWhyDeclined;  // (a frame that does not parse is the host parser's to report)
-  if (!dirsig::frame(index, len, &h, &tx[0].body_off, &tx[0].body_end, &err)) return kHostFlow;
+  if (!dirsig::frame(index, len, &h, &body_off, &body_end, &err)) return kHostFlow;
+  ts.add(index, len, body_off, body_end);
   bool fits = device_takes(len);
+  uint64_t fwork_bytes = dev::files_work_bytes(len);
   for (size_t j = 0; j < nsrc; ++j) {
     Text t;
     dirsig::Header sh;
     std::string serr;
-    if (!src_index[j] || !dirsig::frame(src_index[j], src_len[j], &sh, &t.body_off, &t.body_end, &serr) ||
+    if (!src_index[j] || !dirsig::frame(src_index[j], src_len[j], &sh, &body_off, &body_end, &serr) ||
         sh.hash != h.hash || sh.block_size != h.block_size)
       continue;  // skipped, and not uploaded
-    t.p = src_index[j];
-    t.len = src_len[j];
+    ts.add(src_index[j], src_len[j], body_off, body_end);
     t.ordinal = (uint32_t)j;
-    fits = fits && device_takes(t.len);
+    t.fwork_off = fwork_bytes;
+    fwork_bytes += dev::files_work_bytes(src_len[j]);
+    fits = fits && device_takes(src_len[j]);
     tx.push_back(t);
   }
   *why = kWhyLimit;
   if (!fits) return kHostFlow;
-  const uint64_t bs = h.block_size;
+  const uint64_t bs = h.block_size, text_bytes = ts.text_bytes;
   const size_t nt = tx.size(), used = nt - 1;
-  uint64_t text_bytes = 0, iwork_bytes = 0, fwork_bytes = 0, run_recs = 0;
-  for (Text& t : tx) {
-    t.text_off = text_bytes;
-    t.iwork_off = iwork_bytes;
-    t.fwork_off = fwork_bytes;
-    t.runs_off = run_recs;
-    text_bytes += (t.len + 15) & ~(uint64_t)15;
-    iwork_bytes += dev::idx_work_bytes(t.len);
-    fwork_bytes += dev::files_work_bytes(t.len);
-    run_recs += t.len / idxscan::kMinRunLine;
-  }
-  // host memory that asynchronous copies read or write: declared before the drain
-  std::vector<uint64_t> i_res(CIR_INDEX_RES_FIELDS * nt), f_res(files::kResFields * nt);
+  std::vector<uint64_t> f_res(files::kResFields * nt);
   std::vector<uint64_t> src_first(used + 1);
   std::vector<uint32_t> cand;
   uint64_t m_res[files::kResFields] = {0, 0, 0, 0};
+  TraceEvents<5> mev;
 
-  Device& d = *ctx->devs[0];
-  std::unique_lock<std::mutex> lk(d.mu);
-  DeviceGuard guard;
-  CIR_HIP(hipSetDevice(d.id));
-  hipStream_t s = d.compute;
-  DevSet b;
-  StreamDrain drain{s};
-  uint8_t* d_text = nullptr;
-  uint8_t* d_iwork = nullptr;
+  DeviceCall c(ctx);
+  hipStream_t s = c.s;
   uint8_t* d_fwork = nullptr;
-  uint64_t* d_ires = nullptr;
   uint64_t* d_fres = nullptr;
-  uint64_t* d_runs = nullptr;
   int rc;
-  if ((rc = b.alloc((void**)&d_text, text_bytes + 16)) || (rc = b.alloc((void**)&d_iwork, iwork_bytes)) ||
-      (rc = b.alloc((void**)&d_fwork, fwork_bytes)) ||
-      (rc = b.alloc((void**)&d_ires, 8 * i_res.size())) ||
-      (rc = b.alloc((void**)&d_fres, 8 * f_res.size())) ||
-      (rc = b.alloc((void**)&d_runs, 32 * run_recs)))
-    return rc;
-  const auto t1 = Clock::now();
-  for (const Text& t : tx)
-    CIR_HIP(hipMemcpyAsync(d_text + t.text_off, t.p, t.len, hipMemcpyHostToDevice, s));
-  if (trace) CIR_HIP(hipStreamSynchronize(s));
-  const auto t2 = Clock::now();
-  for (size_t k = 0; k < nt; ++k) {
-    const Text& t = tx[k];
-    CIR_HIP(dev::launch_index_count(d_text + t.text_off, t.len, t.body_off, t.body_end, bs,
-                                    t.len / idxscan::kTokenBytes, t.len / idxscan::kMinRunLine,
-                                    (uint64_t*)(d_iwork + t.iwork_off),
-                                    d_ires + CIR_INDEX_RES_FIELDS * k, s));
-  }
-  CIR_HIP(hipMemcpyAsync(i_res.data(), d_ires, 8 * i_res.size(), hipMemcpyDeviceToHost, s));
-  CIR_HIP(hipStreamSynchronize(s));
-  const auto t3 = Clock::now();
+  // (the text buffer with 16 bytes to spare, as cir_index_files_dev's callers give it)
+  if ((rc = c.begin()) || (rc = ts.count(c, bs, 16, trace))) return rc;
+  const auto t1 = ts.t_bufs, t2 = ts.t_up, t3 = ts.t_counted;
+  uint8_t* const d_text = ts.d_text;
   uint64_t pool_files = 0, pool_blocks = 0;
   for (size_t k = 0; k < nt; ++k) {
-    const uint64_t* r = i_res.data() + CIR_INDEX_RES_FIELDS * k;
+    const uint64_t* r = ts.item[k].cnt;
     if (r[0] != CIR_INDEX_OK) {
       *why = kWhyDeclined;
       return kHostFlow;
@@ -230,7 +193,10 @@ int file_sources_dev(cir_ctx* ctx, const uint8_t* index, size_t len,
   if (pool_files > files::kMaxPoolFiles || need_files > files::kMaxNeedFiles ||
       pool_blocks > 0xFFFFFFFFull)
     return kHostFlow;  // (*why is kWhyLimit)
-  // the join's buffers; the digests and the records are written straight into them
+  // the join's buffers; the digests and the records are written straight into them.
+  // The record kernels' small scratch and results are allocated here and not
+  // in front of the texts: with them first, case (c) of DESIGN 4.5h was 0.15 to
+  // 0.3 ms slower (profiles/index_calls/ab.json, alloc_order).
   uint8_t* d_ndig = nullptr;
   uint8_t* d_pdig = nullptr;
   uint64_t* d_nrec = nullptr;
@@ -240,36 +206,26 @@ int file_sources_dev(cir_ctx* ctx, const uint8_t* index, size_t len,
   uint32_t* d_csrc = nullptr;
   uint64_t* d_cfile = nullptr;
   uint64_t* d_mres = nullptr;
-  if ((rc = b.alloc((void**)&d_ndig, 32 * need_blocks + 32)) ||
-      (rc = b.alloc((void**)&d_pdig, 32 * pool_blocks + 32)) ||
-      (rc = b.alloc((void**)&d_nrec, 32 * need_files)) || (rc = b.alloc((void**)&d_prec, 32 * pool_files)) ||
-      (rc = b.alloc((void**)&d_first, 8 * (used + 1))) ||
-      (rc = b.alloc((void**)&d_mwork, dev::match_files_work_bytes(need_files, pool_files))) ||
-      (rc = b.alloc((void**)&d_csrc, 4 * need_files)) || (rc = b.alloc((void**)&d_cfile, 8 * need_files)) ||
-      (rc = b.alloc((void**)&d_mres, sizeof m_res)))
+  if ((rc = c.alloc(&d_fwork, fwork_bytes)) || (rc = c.alloc(&d_fres, 8 * f_res.size())) ||
+      (rc = c.alloc(&d_ndig, 32 * need_blocks + 32)) ||
+      (rc = c.alloc(&d_pdig, 32 * pool_blocks + 32)) ||
+      (rc = c.alloc(&d_nrec, 32 * need_files)) || (rc = c.alloc(&d_prec, 32 * pool_files)) ||
+      (rc = c.alloc(&d_first, 8 * (used + 1))) ||
+      (rc = c.alloc(&d_mwork, dev::match_files_work_bytes(need_files, pool_files))) ||
+      (rc = c.alloc(&d_csrc, 4 * need_files)) || (rc = c.alloc(&d_cfile, 8 * need_files)) ||
+      (rc = c.alloc(&d_mres, sizeof m_res)))
     return rc;
-  hipEvent_t mev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
-  struct Events {
-    hipEvent_t* ev;
-    ~Events() {
-      for (int i = 0; i < 5; ++i)
-        if (ev[i]) (void)hipEventDestroy(ev[i]);
-    }
-  } mev_guard{mev};
-  if (trace)
-    for (hipEvent_t& e : mev) CIR_HIP(hipEventCreate(&e));
+  if (trace && (rc = mev.create())) return rc;
   CIR_HIP(hipMemcpyAsync(d_first, src_first.data(), 8 * (used + 1), hipMemcpyHostToDevice, s));
   uint64_t file_at = 0, block_at = 0;  // pool ordinals of the next source's first file and block
   for (size_t k = 0; k < nt; ++k) {
     const Text& t = tx[k];
+    const TextSet::Item& it = ts.item[k];
     uint8_t* dig = k ? d_pdig + 32 * block_at : d_ndig;
     uint64_t* rec = k ? d_prec + files::kFileWords * file_at : d_nrec;
-    CIR_HIP(dev::launch_index_emit(d_text + t.text_off, t.len, t.body_off, t.body_end, bs, dig,
-                                   t.nblk, d_runs + 4 * t.runs_off, t.len / idxscan::kMinRunLine,
-                                   (uint64_t*)(d_iwork + t.iwork_off),
-                                   d_ires + CIR_INDEX_RES_FIELDS * k, s));
-    CIR_HIP(dev::launch_index_files(d_text + t.text_off, t.len, t.body_off, t.body_end, bs,
-                                    t.text_off, k ? block_at : 0, rec, t.nfiles,
+    if ((rc = ts.emit(c, k, dig, t.nblk))) return rc;
+    CIR_HIP(dev::launch_index_files(d_text + it.text_off, it.len, it.body_off, it.body_end, bs,
+                                    it.text_off, k ? block_at : 0, rec, t.nfiles,
                                     (uint64_t*)(d_fwork + t.fwork_off),
                                     d_fres + files::kResFields * k, s, false));
     if (k) {
@@ -282,19 +238,18 @@ int file_sources_dev(cir_ctx* ctx, const uint8_t* index, size_t len,
   const dev::FilesSide need{d_text, text_bytes, d_nrec, need_files, d_ndig, need_blocks};
   const dev::FilesSide pool{d_text, text_bytes, d_prec, pool_files, d_pdig, pool_blocks};
   CIR_HIP(dev::launch_match_files(need, pool, d_first, used, bs, nullptr, draw_seed(), d_mwork,
-                                  d_csrc, d_cfile, d_mres, s, trace ? mev : nullptr));
+                                  d_csrc, d_cfile, d_mres, s, trace ? mev.ev : nullptr));
   cand.resize(need_files);
-  CIR_HIP(hipMemcpyAsync(i_res.data(), d_ires, 8 * i_res.size(), hipMemcpyDeviceToHost, s));
   CIR_HIP(hipMemcpyAsync(f_res.data(), d_fres, 8 * f_res.size(), hipMemcpyDeviceToHost, s));
   CIR_HIP(hipMemcpyAsync(m_res, d_mres, sizeof m_res, hipMemcpyDeviceToHost, s));
   if (need_files)
     CIR_HIP(hipMemcpyAsync(cand.data(), d_csrc, 4 * need_files, hipMemcpyDeviceToHost, s));
-  CIR_HIP(hipStreamSynchronize(s));
+  if ((rc = ts.finish(c, false))) return rc;  // (the run tables stay on the device)
   const auto t5 = Clock::now();
   // every verdict is in: a bad token shows only after the decode pass
   for (size_t k = 0; k < nt; ++k) {
     const uint64_t* fr = f_res.data() + files::kResFields * k;
-    if (i_res[CIR_INDEX_RES_FIELDS * k] != CIR_INDEX_OK || fr[0] != CIR_INDEX_OK ||
+    if (ts.status(k) != CIR_INDEX_OK || fr[0] != CIR_INDEX_OK ||
         fr[1] != tx[k].nfiles || fr[2] != tx[k].nblk) {
       *why = kWhyDeclined;
       return kHostFlow;
@@ -336,8 +291,7 @@ int file_sources_dev(cir_ctx* ctx, const uint8_t* index, size_t len,
   o.stats[6] = 1;
   o.stats[7] = kWhyNone;
   if (trace) {
-    float lap[4] = {0, 0, 0, 0};
-    for (int i = 0; i < 4; ++i) (void)hipEventElapsedTime(&lap[i], mev[i], mev[i + 1]);
+    const float lap[4] = {mev.lap(0), mev.lap(1), mev.lap(2), mev.lap(3)};
     fprintf(stderr,
             "cir file_sources: %llu files (%llu blocks) against %llu pool files (%llu blocks) of %zu "
             "source(s), device; frame and buffers %.2f ms, text upload %.2f ms (%llu bytes), count "

@@ -7,13 +7,16 @@
 // src/blocks.rs:150-183; scan_links, src/daemon/metadata/hardlink_sources.rs:
 // 107-153).  Here the text is parsed where the digests are used: the kernels
 // are idxscan.hip, the rule which lines they take is idxscan.hpp, and a text
-// they decline goes through dirsig::parse as before.
+// they decline goes through dirsig::parse as before.  cir_index_digests' hold
+// on the device and its one-shot parse are devcall.hpp's (DeviceCall,
+// parse_one_text).
 #include <stdlib.h>
 #include <string.h>
 
 #include <string>
 #include <vector>
 
+#include "devcall.hpp"
 #include "dirsig.hpp"
 #include "idxscan.hpp"
 #include "runtime.hpp"
@@ -63,50 +66,26 @@ struct Arrays {
   }
 };
 
-// Device memory of one call, freed on every return path.
-struct DevBufs {
-  void* p[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
-  ~DevBufs() {
-    for (void* q : p)
-      if (q) (void)hipFree(q);
-  }
-};
-
-// Upload, the four kernels on ctx's first device, download.  *status = d_res[0];
-// on CIR_INDEX_OK the arrays are filled (malloc'd, null when empty).
+// parse_one_text on ctx's first device, download.  *status = res[0]; on
+// CIR_INDEX_OK the arrays are filled (malloc'd, null when empty).  out and res
+// are the caller's, declared before the call: they outlive its drain.
 int device_parse(cir_ctx* ctx, const uint8_t* index, size_t len, uint64_t body_off,
                  uint64_t body_end, uint64_t bs, Arrays* out, uint64_t res[CIR_INDEX_RES_FIELDS]) {
-  Device& d = *ctx->devs[0];
-  std::lock_guard<std::mutex> lk(d.mu);
-  DeviceGuard guard;
-  CIR_HIP(hipSetDevice(d.id));
-  const uint64_t cap_blocks = len / idxscan::kTokenBytes, cap_runs = len / idxscan::kMinRunLine;
-  const uint64_t work_bytes = dev::idx_work_bytes(len);
-  const size_t bytes[5] = {(size_t)len + 16, (size_t)(32 * cap_blocks + 32),
-                           (size_t)(32 * cap_runs + 32), (size_t)work_bytes,
-                           CIR_INDEX_RES_FIELDS * sizeof(uint64_t)};
-  DevBufs b;
-  for (int i = 0; i < 5; ++i)
-    if (hipMalloc(&b.p[i], bytes[i]) != hipSuccess) {
-      (void)hipGetLastError();
-      return fail(CIR_ENOMEM, "hipMalloc of the index parse's buffers");
-    }
-  hipStream_t s = d.compute;
-  CIR_HIP(hipMemcpyAsync(b.p[0], index, len, hipMemcpyHostToDevice, s));
-  CIR_HIP(dev::launch_index_digests((const uint8_t*)b.p[0], len, body_off, body_end, bs,
-                                    (uint8_t*)b.p[1], cap_blocks, (uint64_t*)b.p[2], cap_runs,
-                                    (uint64_t*)b.p[3], (uint64_t*)b.p[4], s));
-  CIR_HIP(hipMemcpyAsync(res, b.p[4], CIR_INDEX_RES_FIELDS * sizeof(uint64_t),
-                         hipMemcpyDeviceToHost, s));
-  CIR_HIP(hipStreamSynchronize(s));
+  DeviceCall c(ctx);
+  uint8_t* d_dig = nullptr;
+  uint64_t* d_runs = nullptr;
+  int rc;
+  if ((rc = c.begin()) ||
+      (rc = parse_one_text(c, index, len, body_off, body_end, bs, res, &d_dig, &d_runs)))
+    return rc;
   if (res[0] != CIR_INDEX_OK) return CIR_OK;
   if (res[3]) {
     out->digests = (uint8_t*)malloc(32 * res[3]);
     out->runs = (uint64_t*)malloc(32 * res[2]);
     if (!out->digests || !out->runs) return fail(CIR_ENOMEM, "malloc");
-    CIR_HIP(hipMemcpyAsync(out->digests, b.p[1], 32 * res[3], hipMemcpyDeviceToHost, s));
-    CIR_HIP(hipMemcpyAsync(out->runs, b.p[2], 32 * res[2], hipMemcpyDeviceToHost, s));
-    CIR_HIP(hipStreamSynchronize(s));
+    CIR_HIP(hipMemcpyAsync(out->digests, d_dig, 32 * res[3], hipMemcpyDeviceToHost, c.s));
+    CIR_HIP(hipMemcpyAsync(out->runs, d_runs, 32 * res[2], hipMemcpyDeviceToHost, c.s));
+    CIR_HIP(hipStreamSynchronize(c.s));
   }
   return CIR_OK;
 }
@@ -133,8 +112,7 @@ int index_digests_impl(cir_ctx* ctx, const uint8_t* index, size_t len, int* hash
     size_t body_off = 0, body_end = 0;
     std::string err;
     // (a frame that does not parse is the host parser's to report)
-    if (len <= dev::kIdxMaxLen && len / idxscan::kTokenBytes <= 0xFFFFFFFFull &&
-        dirsig::frame(index, len, &h, &body_off, &body_end, &err)) {
+    if (device_takes(len) && dirsig::frame(index, len, &h, &body_off, &body_end, &err)) {
       Arrays a;
       uint64_t res[CIR_INDEX_RES_FIELDS];
       const int rc = device_parse(ctx, index, len, body_off, body_end, h.block_size, &a, res);

@@ -14,7 +14,9 @@
 // are repeats.hip.  The mapping and the merge are cir_block_extents' own
 // (extents.hpp, sources.hpp, extents.hip) over the need run table twice, and
 // with a context the text is parsed by cir_index_digests_dev's kernels
-// (idxscan.hip).
+// (idxscan.hip) through devcall.hpp's parse_one_text, on its DeviceCall, and
+// the extents come down through its device_extent_tail; with ctx = NULL they
+// are sources::extents_owned's.
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -79,7 +81,7 @@ int too_many_blocks() { return fail(CIR_EINVAL, "more than 2^30-1 blocks in the 
 // extents_of over the doubled run table.  need.n > 0.
 int answer_on_host(const Outs& o, const sources::BlockList& need, const uint8_t* digests,
                    uint64_t bs, const uint64_t* want, const uint64_t* present, bool trace) {
-  const uint64_t n = need.n, nwords = (n + 63) / 64;
+  const uint64_t n = need.n;
   const auto t0 = Clock::now();
   std::vector<uint32_t> match(n), src(n);
   std::vector<uint64_t> file(n), block(n);
@@ -88,28 +90,10 @@ int answer_on_host(const Outs& o, const sources::BlockList& need, const uint8_t*
   const sources::BlockList pool = repeats::doubled(need);
   const sources::MapStats ms = sources::map_matches(need, pool, bs, want, match.data(), src.data(),
                                                     file.data(), block.data());
-  std::vector<sources::Extent> ex;
-  uint64_t* fetch = (uint64_t*)malloc(nwords * sizeof(uint64_t));
-  if (!fetch) return fail(CIR_ENOMEM, "malloc");
   uint64_t left = 0;
-  try {
-    left = sources::extents_of(need, bs, want, src.data(), file.data(), block.data(), &ex, fetch);
-  } catch (...) {
-    free(fetch);
-    throw;
-  }
-  uint64_t* rec = nullptr;
-  if (!ex.empty()) {
-    rec = (uint64_t*)malloc(ex.size() * sizeof(sources::Extent));
-    if (!rec) {
-      free(fetch);
-      return fail(CIR_ENOMEM, "malloc");
-    }
-    memcpy(rec, ex.data(), ex.size() * sizeof(sources::Extent));
-  }
-  *o.extents_out = rec;
-  *o.nextents_out = ex.size();
-  *o.fetch_out = fetch;
+  if (!sources::extents_owned(need, bs, want, src.data(), file.data(), block.data(), o.extents_out,
+                              o.nextents_out, o.fetch_out, &left))
+    return fail(CIR_ENOMEM, "malloc");
   *o.nblk_out = n;
   o.stats[0] = ms.wanted;
   o.stats[1] = ms.found;
@@ -117,14 +101,14 @@ int answer_on_host(const Outs& o, const sources::BlockList& need, const uint8_t*
   o.stats[3] = c.wanted + c.present;
   o.stats[4] = c.present;
   o.stats[5] = ms.dropped;
-  o.stats[8] = ex.size();
+  o.stats[8] = *o.nextents_out;
   o.stats[9] = left;
   if (trace)
     fprintf(stderr,
             "cir block_repeats: %llu blocks, %llu take part, host; join %.2f ms, map and merge "
             "%.2f ms; %zu extents\n",
             (unsigned long long)n, (unsigned long long)o.stats[3], ms_between(t0, t1),
-            ms_between(t1, Clock::now()), ex.size());
+            ms_between(t1, Clock::now()), *o.nextents_out);
   return CIR_OK;
 }
 
@@ -155,7 +139,7 @@ int host_parse(const uint8_t* index, size_t len, sources::BlockList* need,
 int repeats_on_device(cir_ctx* ctx, const uint8_t* index, size_t len, bool framed,
                       const dirsig::Header& h, size_t body_off, size_t body_end,
                       const uint64_t* want, const uint64_t* present, const Outs& o, bool trace) {
-  // host memory that asynchronous copies read or write: declared before the drain
+  // host memory that asynchronous copies read or write: declared before the call
   sources::BlockList need;
   std::vector<uint8_t> h_digests;
   std::vector<uint64_t> h_runs, tabs;
@@ -168,33 +152,17 @@ int repeats_on_device(cir_ctx* ctx, const uint8_t* index, size_t len, bool frame
     if (rc) return rc;  // (before the context is looked at)
   }
   if (ctx->devs.empty()) return fail(CIR_EINVAL, "context without a device");
-  Device& d = *ctx->devs[0];
-  std::unique_lock<std::mutex> lk(d.mu);
-  DeviceGuard guard;
-  CIR_HIP(hipSetDevice(d.id));
-  hipStream_t s = d.compute;
-  DevSet b;
-  StreamDrain drain{s};
+  TraceEvents<3> jev, xev;
+  DeviceCall c(ctx);
+  hipStream_t s = c.s;
   uint8_t* d_dig = nullptr;
   uint64_t* d_runs = nullptr;
   bool dev_parsed = false;
   int rc;
+  if ((rc = c.begin())) return rc;
   if (framed) {
-    const uint64_t cap_blocks = len / idxscan::kTokenBytes, cap_runs = len / idxscan::kMinRunLine;
-    uint8_t* d_text = nullptr;
-    uint64_t* d_iwork = nullptr;
-    uint64_t* d_ires = nullptr;
-    if ((rc = b.alloc((void**)&d_text, len + 16)) ||
-        (rc = b.alloc((void**)&d_dig, 32 * cap_blocks + 32)) ||
-        (rc = b.alloc((void**)&d_runs, 32 * cap_runs + 32)) ||
-        (rc = b.alloc((void**)&d_iwork, dev::idx_work_bytes(len))) ||
-        (rc = b.alloc((void**)&d_ires, sizeof i_res)))
+    if ((rc = parse_one_text(c, index, len, body_off, body_end, bs, i_res, &d_dig, &d_runs)))
       return rc;
-    CIR_HIP(hipMemcpyAsync(d_text, index, len, hipMemcpyHostToDevice, s));
-    CIR_HIP(dev::launch_index_digests(d_text, len, body_off, body_end, bs, d_dig, cap_blocks,
-                                      d_runs, cap_runs, d_iwork, d_ires, s));
-    CIR_HIP(hipMemcpyAsync(i_res, d_ires, sizeof i_res, hipMemcpyDeviceToHost, s));
-    CIR_HIP(hipStreamSynchronize(s));
     if (i_res[0] == CIR_INDEX_OK) {
       dev_parsed = true;
       if (i_res[3] > repeats::kMaxBlocks) return too_many_blocks();
@@ -207,10 +175,10 @@ int repeats_on_device(cir_ctx* ctx, const uint8_t* index, size_t len, bool frame
         need.runs.push_back(
             sources::FileRun{h_runs[4 * r], h_runs[4 * r + 1], h_runs[4 * r + 2], 0});
       need.n = i_res[3];
-    } else {  // (the stream is idle and the buffers are this call's own)
-      lk.unlock();
+    } else {
+      c.unlock();
       rc = host_parse(index, len, &need, &h_digests, &bs);
-      lk.lock();
+      c.lock();
       if (rc) return rc;
     }
   }
@@ -221,21 +189,14 @@ int repeats_on_device(cir_ctx* ctx, const uint8_t* index, size_t len, bool frame
     return CIR_OK;
   }
   if (!dev_parsed) {
-    if ((rc = b.alloc((void**)&d_dig, 32 * n))) return rc;
+    if ((rc = c.alloc(&d_dig, 32 * n))) return rc;
     CIR_HIP(hipMemcpyAsync(d_dig, h_digests.data(), 32 * n, hipMemcpyHostToDevice, s));
   }
   // the need run table twice: its first copy is the need table as well
   const size_t nr = need.runs.size();
   const sources::BlockList pool = repeats::doubled(need);
   tabs.resize(8 * nr);
-  for (size_t i = 0; i < 2 * nr; ++i) {
-    const sources::FileRun& r = pool.runs[i];
-    uint64_t* t = tabs.data() + 4 * i;
-    t[0] = r.first;
-    t[1] = r.size;
-    t[2] = r.file;
-    t[3] = r.src;
-  }
+  sources::pack_runs(pool, tabs.data());
   const uint64_t slots = dev::join_table_slots(n);
   uint64_t* d_tabs = nullptr;
   uint64_t* d_want = nullptr;
@@ -245,84 +206,49 @@ int repeats_on_device(cir_ctx* ctx, const uint8_t* index, size_t len, bool frame
   uint64_t* d_work = nullptr;
   uint64_t* d_xres = nullptr;
   uint64_t* d_fetch = nullptr;
-  if ((rc = b.alloc((void**)&d_tabs, 64 * nr)) ||
-      (want && (rc = b.alloc((void**)&d_want, 8 * nwords))) ||
-      (present && (rc = b.alloc((void**)&d_present, 8 * nwords))) ||
-      (rc = b.alloc((void**)&d_table, slots * sizeof(uint32_t))) ||
-      (rc = b.alloc((void**)&d_match, (n + 4) * sizeof(uint32_t))) ||
-      (rc = b.alloc((void**)&d_work, dev::ext_work_bytes(n))) ||
-      (rc = b.alloc((void**)&d_xres, sizeof x_res)) || (rc = b.alloc((void**)&d_fetch, 8 * nwords)))
+  if ((rc = c.alloc(&d_tabs, 64 * nr)) ||
+      (want && (rc = c.alloc(&d_want, 8 * nwords))) ||
+      (present && (rc = c.alloc(&d_present, 8 * nwords))) ||
+      (rc = c.alloc(&d_table, slots * sizeof(uint32_t))) ||
+      (rc = c.alloc(&d_match, (n + 4) * sizeof(uint32_t))) ||
+      (rc = c.alloc(&d_work, dev::ext_work_bytes(n))) ||
+      (rc = c.alloc(&d_xres, sizeof x_res)) || (rc = c.alloc(&d_fetch, 8 * nwords)))
     return rc;
-  hipEvent_t xev[3] = {nullptr, nullptr, nullptr};
-  struct Events {
-    hipEvent_t* ev;
-    ~Events() {
-      for (int i = 0; i < 3; ++i)
-        if (ev[i]) (void)hipEventDestroy(ev[i]);
-    }
-  } xev_guard{xev};
-  if (trace) {
-    for (hipEvent_t& e : b.ev) CIR_HIP(hipEventCreate(&e));
-    for (hipEvent_t& e : xev) CIR_HIP(hipEventCreate(&e));
-  }
+  if (trace && ((rc = jev.create()) || (rc = xev.create()))) return rc;
   CIR_HIP(hipMemcpyAsync(d_tabs, tabs.data(), 64 * nr, hipMemcpyHostToDevice, s));
   if (want) CIR_HIP(hipMemcpyAsync(d_want, want, 8 * nwords, hipMemcpyHostToDevice, s));
   if (present) CIR_HIP(hipMemcpyAsync(d_present, present, 8 * nwords, hipMemcpyHostToDevice, s));
   if (trace) CIR_HIP(hipStreamSynchronize(s));
   const auto t2 = Clock::now();
   CIR_HIP(dev::launch_repeat_join(d_dig, n, d_want, d_present, d_table, slots, draw_seed(), d_match,
-                                  d_match + n, s, trace ? b.ev : nullptr));
+                                  d_match + n, s, trace ? jev.ev : nullptr));
   const dev::ExtentArgs args{d_match, n, d_tabs, nr, d_tabs, 2 * nr, 2 * n, bs, d_want};
   // (no cap: the count decides the allocation, not the other way round)
   CIR_HIP(dev::launch_extent_map(args, nullptr, nullptr, nullptr, d_fetch, ~0ull, d_work, d_xres, s,
-                                 trace ? xev : nullptr));
+                                 trace ? xev.ev : nullptr));
   CIR_HIP(hipMemcpyAsync(x_res, d_xres, sizeof x_res, hipMemcpyDeviceToHost, s));
   CIR_HIP(hipStreamSynchronize(s));
   const auto t3 = Clock::now();
   const uint64_t count = x_res[5];
-  uint64_t* fetch = (uint64_t*)malloc(nwords * sizeof(uint64_t));
-  uint64_t* rec = count ? (uint64_t*)malloc(count * sizeof(sources::Extent)) : nullptr;
-  auto drop = [&](int code) {
-    (void)hipStreamSynchronize(s);  // (no copy is in flight into what is freed)
-    free(fetch);
-    free(rec);
-    return code;
-  };
-  if (!fetch || (count && !rec)) return drop(fail(CIR_ENOMEM, "malloc"));
-  hipError_t e = hipSuccess;
-  if (count) {
-    uint64_t* d_ext = nullptr;
-    if ((rc = b.alloc((void**)&d_ext, count * sizeof(sources::Extent)))) return drop(rc);
-    if ((e = dev::launch_extent_emit(args, d_ext, count, count, d_work, d_xres, s)) != hipSuccess)
-      return drop(hip_fail(e, "launch_extent_emit"));
-    if ((e = hipMemcpyAsync(rec, d_ext, count * sizeof(sources::Extent), hipMemcpyDeviceToHost,
-                            s)) != hipSuccess)
-      return drop(hip_fail(e, "download of the extents"));
-  }
-  if ((e = hipMemcpyAsync(fetch, d_fetch, 8 * nwords, hipMemcpyDeviceToHost, s)) != hipSuccess ||
-      (e = hipStreamSynchronize(s)) != hipSuccess)
-    return drop(hip_fail(e, "download of the fetch bitmap"));
-  const repeats::Counts c = repeats::count_classes(want, present, n);
-  *o.extents_out = rec;
+  auto t_emit = t3;
+  if ((rc = device_extent_tail(c, args, count, d_work, d_xres, d_fetch, false, o.extents_out,
+                               o.fetch_out, &t_emit)))
+    return rc;
+  const repeats::Counts cc = repeats::count_classes(want, present, n);
   *o.nextents_out = count;
-  *o.fetch_out = fetch;
   *o.nblk_out = n;
   o.stats[0] = x_res[1];
   o.stats[1] = x_res[2];
   o.stats[2] = x_res[3];
-  o.stats[3] = c.wanted + c.present;
-  o.stats[4] = c.present;
+  o.stats[3] = cc.wanted + cc.present;
+  o.stats[4] = cc.present;
   o.stats[5] = x_res[4];
   o.stats[6] = slots;
   o.stats[7] = 1;
   o.stats[8] = count;
   o.stats[9] = x_res[1] - x_res[2];
   if (trace) {
-    float build = 0, probe = 0, map = 0, scan = 0;
-    (void)hipEventElapsedTime(&build, b.ev[0], b.ev[1]);
-    (void)hipEventElapsedTime(&probe, b.ev[1], b.ev[2]);
-    (void)hipEventElapsedTime(&map, xev[0], xev[1]);
-    (void)hipEventElapsedTime(&scan, xev[1], xev[2]);
+    const float build = jev.lap(0), probe = jev.lap(1), map = xev.lap(0), scan = xev.lap(1);
     fprintf(stderr,
             "cir block_repeats: %llu blocks, %llu take part, device (text parsed on the %s); parse "
             "%.2f ms, tables upload %.2f ms (%zu runs twice), build kernel %.3f ms, probe kernel "
@@ -346,8 +272,7 @@ int block_repeats_impl(cir_ctx* ctx, const uint8_t* index, size_t len, const uin
     size_t body_off = 0, body_end = 0;
     std::string err;
     // (a frame that does not parse is the host parser's to report)
-    const bool framed = !parse_on_host() && len <= dev::kIdxMaxLen &&
-                        len / idxscan::kTokenBytes <= 0xFFFFFFFFull &&
+    const bool framed = !parse_on_host() && device_takes(len) &&
                         dirsig::frame(index, len, &h, &body_off, &body_end, &err);
     const int rc = repeats_on_device(ctx, index, len, framed, h, body_off, body_end, want, present,
                                      o, trace);

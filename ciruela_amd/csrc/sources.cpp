@@ -20,6 +20,13 @@
 // bitmap of what is left to fetch; cir_match_extents_dev is the mapping and
 // the merge behind it on the device (extents.hip, the rule extents.hpp), and
 // maps cir_block_sources' matches there too.  One flow serves both calls.
+//
+// The hold on the device, the two-pass parse of the texts (TextSet) and the
+// extent tail on the device are devcall.hpp's, shared with repeats.cpp,
+// files.cpp and idxscan.cpp; the extent tail on the host and the run tables'
+// packing are sources.hpp's.  What is here is the policy: a text the device
+// declines goes to the host parser alone, and a bad token found by the decode
+// pass means one more attempt with that text on the host.
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -94,63 +101,45 @@ int match_extents_dev_impl(const uint32_t* d_match, uint64_t n_need, const uint6
   return CIR_OK;
 }
 
-// Device memory of one call, freed on every return path.
-struct DevBufs {
-  void* p[4] = {nullptr, nullptr, nullptr, nullptr};
-  hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
-  ~DevBufs() {
-    for (void* q : p)
-      if (q) (void)hipFree(q);
-    for (hipEvent_t e : ev)
-      if (e) (void)hipEventDestroy(e);
-  }
-};
-
 struct Laps {
   double upload = 0, build = 0, probe = 0, download = 0;
 };
 
 // The join on ctx's first device: buffers for the call, one upload of each
-// list, launch_join on the device's compute stream, one download.
+// list, launch_join on the device's compute stream, one download.  need, pool
+// and match are the caller's and outlive the call's drain.
 int device_join(cir_ctx* ctx, const std::vector<uint8_t>& need, uint64_t n_need,
                 const std::vector<uint8_t>& pool, uint64_t n_pool, uint64_t slots,
                 uint32_t* match, bool trace, Laps* laps) {
-  Device& d = *ctx->devs[0];
-  std::lock_guard<std::mutex> lk(d.mu);
-  DeviceGuard guard;
-  CIR_HIP(hipSetDevice(d.id));
-  DevBufs b;
-  const size_t bytes[4] = {std::max<size_t>(32 * n_need, 32), std::max<size_t>(32 * n_pool, 32),
-                           (size_t)slots * sizeof(uint32_t), (n_need + 4) * sizeof(uint32_t)};
-  for (int i = 0; i < 4; ++i)
-    if (hipMalloc(&b.p[i], bytes[i]) != hipSuccess) {
-      (void)hipGetLastError();
-      return fail(CIR_ENOMEM, "hipMalloc of the join's buffers");
-    }
-  if (trace)
-    for (hipEvent_t& e : b.ev) CIR_HIP(hipEventCreate(&e));
-  uint8_t* d_need = (uint8_t*)b.p[0];
-  uint8_t* d_pool = (uint8_t*)b.p[1];
-  uint32_t* d_table = (uint32_t*)b.p[2];
-  uint32_t* d_match = (uint32_t*)b.p[3];
-  hipStream_t s = d.compute;
+  TraceEvents<3> jev;
+  DeviceCall c(ctx);
+  int rc;
+  if ((rc = c.begin())) return rc;
+  uint8_t* d_need = nullptr;
+  uint8_t* d_pool = nullptr;
+  uint32_t* d_table = nullptr;
+  uint32_t* d_match = nullptr;
+  if ((rc = c.alloc(&d_need, std::max<size_t>(32 * n_need, 32))) ||
+      (rc = c.alloc(&d_pool, std::max<size_t>(32 * n_pool, 32))) ||
+      (rc = c.alloc(&d_table, slots * sizeof(uint32_t))) ||
+      (rc = c.alloc(&d_match, (n_need + 4) * sizeof(uint32_t))))
+    return rc;
+  if (trace && (rc = jev.create())) return rc;
+  hipStream_t s = c.s;
   const auto t0 = Clock::now();
   CIR_HIP(hipMemcpyAsync(d_need, need.data(), 32 * n_need, hipMemcpyHostToDevice, s));
   if (n_pool) CIR_HIP(hipMemcpyAsync(d_pool, pool.data(), 32 * n_pool, hipMemcpyHostToDevice, s));
   if (trace) CIR_HIP(hipStreamSynchronize(s));
   const auto t1 = Clock::now();
   CIR_HIP(dev::launch_join(d_need, n_need, d_pool, n_pool, d_table, slots, draw_seed(), d_match,
-                           d_match + n_need, s, trace ? b.ev : nullptr));
+                           d_match + n_need, s, trace ? jev.ev : nullptr));
   if (trace) CIR_HIP(hipStreamSynchronize(s));
   const auto t2 = Clock::now();
   CIR_HIP(hipMemcpyAsync(match, d_match, n_need * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
   CIR_HIP(hipStreamSynchronize(s));
   if (trace) {
-    float f = 0;
-    CIR_HIP(hipEventElapsedTime(&f, b.ev[0], b.ev[1]));
-    laps->build = f;
-    CIR_HIP(hipEventElapsedTime(&f, b.ev[1], b.ev[2]));
-    laps->probe = f;
+    laps->build = jev.lap(0);
+    laps->probe = jev.lap(1);
     laps->upload = ms_between(t0, t1);
     laps->download = ms_between(t2, Clock::now());
   }
@@ -214,15 +203,13 @@ int answer_on_host(const Answer& a, const sources::BlockList& need,
   uint32_t* so = (uint32_t*)malloc(n * sizeof(uint32_t));
   uint64_t* fo = (uint64_t*)malloc(n * sizeof(uint64_t));
   uint64_t* bo = (uint64_t*)malloc(n * sizeof(uint64_t));
-  uint64_t* fetch = a.extents ? (uint64_t*)malloc((n + 63) / 64 * sizeof(uint64_t)) : nullptr;
   auto drop = [&](int rc) {
     free(so);
     free(fo);
     free(bo);
-    free(fetch);
     return rc;
   };
-  if (!so || !fo || !bo || (a.extents && !fetch)) return drop(fail(CIR_ENOMEM, "malloc"));
+  if (!so || !fo || !bo) return drop(fail(CIR_ENOMEM, "malloc"));
   const sources::MapStats ms = sources::map_matches(need, pool, bs, want, match, so, fo, bo);
   a.stats[0] = ms.wanted;
   a.stats[1] = ms.found;
@@ -235,22 +222,12 @@ int answer_on_host(const Answer& a, const sources::BlockList& need,
     *a.src_block_out = bo;
     return CIR_OK;
   }
-  std::vector<sources::Extent> ex;
-  a.stats[9] = sources::extents_of(need, bs, want, so, fo, bo, &ex, fetch);
-  a.stats[8] = ex.size();
-  uint64_t* rec = nullptr;
-  if (!ex.empty()) {
-    rec = (uint64_t*)malloc(ex.size() * sizeof(sources::Extent));
-    if (!rec) {
-      *a.nblk_out = 0;
-      return drop(fail(CIR_ENOMEM, "malloc"));
-    }
-    memcpy(rec, ex.data(), ex.size() * sizeof(sources::Extent));
+  if (!sources::extents_owned(need, bs, want, so, fo, bo, a.extents_out, a.nextents_out,
+                              a.fetch_out, &a.stats[9])) {
+    *a.nblk_out = 0;
+    return drop(fail(CIR_ENOMEM, "malloc"));
   }
-  *a.extents_out = rec;
-  *a.nextents_out = ex.size();
-  *a.fetch_out = fetch;
-  fetch = nullptr;
+  a.stats[8] = *a.nextents_out;
   return drop(CIR_OK);
 }
 
@@ -265,13 +242,11 @@ struct Text {
   bool dev = false;        // its body is parsed on the device in this attempt
   bool usable = false;
   uint64_t nblk = 0;
-  uint64_t text_off = 0, work_off = 0, runs_off = 0;  // bytes / bytes / records in the buffers
-  uint64_t res[CIR_INDEX_RES_FIELDS] = {0, 0, 0, 0, 0};
+  size_t slot = 0;       // device path: its place in this attempt's TextSet
   dirsig::Index parsed;  // on the host path
   std::string err;
   bool host_done = false, host_ok = false;  // dirsig::parse ran / took it
   std::vector<uint8_t> digests;       // host path: its digests, until they are uploaded
-  std::vector<idxscan::Run> runs;     // device path: its run table
 };
 
 // What an attempt returns besides a CIR_* code (none of those is positive).
@@ -293,23 +268,17 @@ struct DevLaps {
 //                       extent count, the records are allocated exactly,
 //                       emitted and downloaded with the fetch bitmap; the
 //                       per-block arrays are never made.
-// need.n > 0.  b: the call's device memory.
+// need.n > 0.  x_res, like *tabs, is the caller's and outlives c's drain.
 int answer_on_device(const Answer& a, const sources::BlockList& need,
                      const sources::BlockList& pool, uint64_t n_pool, uint64_t bs,
-                     const uint64_t* want, const uint32_t* d_match, DevSet* b,
-                     std::vector<uint64_t>* tabs, uint64_t* x_res, hipStream_t s, bool trace,
-                     DevLaps* laps) {
+                     const uint64_t* want, const uint32_t* d_match, DeviceCall& c,
+                     std::vector<uint64_t>* tabs, uint64_t* x_res, bool trace, DevLaps* laps) {
+  hipStream_t s = c.s;
   const uint64_t n = need.n, nwords = (n + 63) / 64;
   const size_t nr = need.runs.size(), pr = pool.runs.size();
   tabs->resize(4 * (nr + pr));
-  for (size_t i = 0; i < nr + pr; ++i) {
-    const sources::FileRun& r = i < nr ? need.runs[i] : pool.runs[i - nr];
-    uint64_t* o = tabs->data() + 4 * i;
-    o[0] = r.first;
-    o[1] = r.size;
-    o[2] = r.file;
-    o[3] = r.src;
-  }
+  sources::pack_runs(need, tabs->data());
+  sources::pack_runs(pool, tabs->data() + 4 * nr);
   uint64_t* d_tabs = nullptr;
   uint64_t* d_want = nullptr;
   uint64_t* d_work = nullptr;
@@ -319,15 +288,15 @@ int answer_on_device(const Answer& a, const sources::BlockList& need,
   uint64_t* d_bo = nullptr;
   uint64_t* d_fetch = nullptr;
   int rc;
-  if ((rc = b->alloc((void**)&d_tabs, 32 * (nr + pr))) ||
-      (want && (rc = b->alloc((void**)&d_want, 8 * nwords))) ||
-      (rc = b->alloc((void**)&d_work, dev::ext_work_bytes(n))) ||
-      (rc = b->alloc((void**)&d_xres, sizeof(uint64_t) * extents::kResFields)))
+  if ((rc = c.alloc(&d_tabs, 32 * (nr + pr))) ||
+      (want && (rc = c.alloc(&d_want, 8 * nwords))) ||
+      (rc = c.alloc(&d_work, dev::ext_work_bytes(n))) ||
+      (rc = c.alloc(&d_xres, sizeof(uint64_t) * extents::kResFields)))
     return rc;
   if (a.extents) {
-    if ((rc = b->alloc((void**)&d_fetch, 8 * nwords))) return rc;
-  } else if ((rc = b->alloc((void**)&d_so, 4 * n)) || (rc = b->alloc((void**)&d_fo, 8 * n)) ||
-             (rc = b->alloc((void**)&d_bo, 8 * n))) {
+    if ((rc = c.alloc(&d_fetch, 8 * nwords))) return rc;
+  } else if ((rc = c.alloc(&d_so, 4 * n)) || (rc = c.alloc(&d_fo, 8 * n)) ||
+             (rc = c.alloc(&d_bo, 8 * n))) {
     return rc;
   }
   const auto t0 = Clock::now();
@@ -337,15 +306,8 @@ int answer_on_device(const Answer& a, const sources::BlockList& need,
   const auto t1 = Clock::now();
   const dev::ExtentArgs args{d_match, n, d_tabs, nr, d_tabs + 4 * nr, pr, n_pool, bs, d_want};
   // (no cap: the count decides the allocation, not the other way round)
-  struct Events {
-    hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
-    ~Events() {
-      for (hipEvent_t e : ev)
-        if (e) (void)hipEventDestroy(e);
-    }
-  } tev;
-  if (trace)
-    for (hipEvent_t& e : tev.ev) CIR_HIP(hipEventCreate(&e));
+  TraceEvents<3> tev;
+  if (trace && (rc = tev.create())) return rc;
   CIR_HIP(dev::launch_extent_map(args, d_so, d_fo, d_bo, d_fetch, ~0ull, d_work, d_xres, s,
                                  trace ? tev.ev : nullptr));
   if (trace) CIR_HIP(hipStreamSynchronize(s));
@@ -353,15 +315,11 @@ int answer_on_device(const Answer& a, const sources::BlockList& need,
   uint32_t* so = nullptr;
   uint64_t* fo = nullptr;
   uint64_t* bo = nullptr;
-  uint64_t* rec = nullptr;
-  uint64_t* fetch = nullptr;
   auto drop = [&](int code) {
     (void)hipStreamSynchronize(s);  // (no copy is in flight into what is freed)
     free(so);
     free(fo);
     free(bo);
-    free(rec);
-    free(fetch);
     return code;
   };
   hipError_t e = hipSuccess;
@@ -383,26 +341,10 @@ int answer_on_device(const Answer& a, const sources::BlockList& need,
   auto t4 = t3;
   if (a.extents) {
     const uint64_t count = x_res[5];
-    fetch = (uint64_t*)malloc(nwords * sizeof(uint64_t));
-    if (count) rec = (uint64_t*)malloc(count * sizeof(sources::Extent));
-    if (!fetch || (count && !rec)) return drop(fail(CIR_ENOMEM, "malloc"));
-    uint64_t* d_ext = nullptr;
-    if (count) {
-      if ((rc = b->alloc((void**)&d_ext, count * sizeof(sources::Extent)))) return drop(rc);
-      if ((e = dev::launch_extent_emit(args, d_ext, count, count, d_work, d_xres, s)) != hipSuccess)
-        return drop(hip_fail(e, "launch_extent_emit"));
-      if (trace && (e = hipStreamSynchronize(s)) != hipSuccess) return drop(hip_fail(e, "emit"));
-      t4 = Clock::now();
-      if ((e = hipMemcpyAsync(rec, d_ext, count * sizeof(sources::Extent), hipMemcpyDeviceToHost,
-                              s)) != hipSuccess)
-        return drop(hip_fail(e, "download of the extents"));
-    }
-    if ((e = hipMemcpyAsync(fetch, d_fetch, 8 * nwords, hipMemcpyDeviceToHost, s)) != hipSuccess ||
-        (e = hipStreamSynchronize(s)) != hipSuccess)
-      return drop(hip_fail(e, "download of the fetch bitmap"));
-    *a.extents_out = rec;
+    if ((rc = device_extent_tail(c, args, count, d_work, d_xres, d_fetch, trace, a.extents_out,
+                                 a.fetch_out, &t4)))
+      return rc;
     *a.nextents_out = count;
-    *a.fetch_out = fetch;
     a.stats[8] = count;
     a.stats[9] = x_res[1] - x_res[2];
   } else {
@@ -417,9 +359,8 @@ int answer_on_device(const Answer& a, const sources::BlockList& need,
   *a.nblk_out = n;
   if (trace) {
     laps->tables_upload = ms_between(t0, t1);
-    float f = 0;
-    if (hipEventElapsedTime(&f, tev.ev[0], tev.ev[1]) == hipSuccess) laps->map = f;
-    if (hipEventElapsedTime(&f, tev.ev[1], tev.ev[2]) == hipSuccess) laps->scan = f;
+    laps->map = tev.lap(0);
+    laps->scan = tev.lap(1);
     laps->emit = ms_between(t3, t4);
     laps->download = ms_between(t2, t3) + ms_between(t4, Clock::now());
     fprintf(stderr,
@@ -460,8 +401,7 @@ int sources_dev_attempt(cir_ctx* ctx, std::vector<Text>& tx, size_t nsrc,
   };
   auto want_dev = [&](size_t k) {
     const Text& t = tx[k];
-    return t.framed && !force_host[k] && t.len <= dev::kIdxMaxLen &&
-           t.len / idxscan::kTokenBytes <= 0xFFFFFFFFull;
+    return t.framed && !force_host[k] && device_takes(t.len);
   };
   // the new index first: its header decides which sources take part
   nw.dev = want_dev(nsrc);
@@ -489,74 +429,34 @@ int sources_dev_attempt(cir_ctx* ctx, std::vector<Text>& tx, size_t nsrc,
   fan_out(on_host.size(), [&](size_t i) { host_parse(tx[on_host[i]]); });
   const double host_first_ms = ms_between(th0, Clock::now());
 
-  Device& d = *ctx->devs[0];
-  std::unique_lock<std::mutex> lk(d.mu);
-  DeviceGuard guard;
-  CIR_HIP(hipSetDevice(d.id));
-  hipStream_t s = d.compute;
-  DevSet b;
-  // the texts, their scratch, result words and run tables
-  uint64_t text_bytes = 0, work_bytes = 0, run_recs = 0;
-  for (size_t k : on_dev) {
-    Text& t = tx[k];
-    t.text_off = text_bytes;
-    t.work_off = work_bytes;
-    t.runs_off = run_recs;
-    text_bytes += (t.len + 15) & ~(uint64_t)15;
-    work_bytes += dev::idx_work_bytes(t.len);
-    run_recs += t.len / idxscan::kMinRunLine;
-  }
-  uint8_t* d_text = nullptr;
-  uint8_t* d_work = nullptr;
-  uint64_t* d_res = nullptr;
-  uint64_t* d_runs = nullptr;
-  std::vector<uint64_t> h_res(CIR_INDEX_RES_FIELDS * on_dev.size() + 1);
+  // host memory that asynchronous copies read or write: declared before the call
+  TextSet ts;  // the texts, their scratch, result words and run tables
+  for (size_t k : on_dev) tx[k].slot = ts.add(tx[k].p, tx[k].len, tx[k].body_off, tx[k].body_end);
   std::vector<uint64_t> tabs;  // the combined run tables, uploaded for the device map
   uint64_t x_res[extents::kResFields] = {0, 0, 0, 0, 0, 0};
-  StreamDrain drain{s};
-  if (!on_dev.empty()) {
-    int rc;
-    if ((rc = b.alloc((void**)&d_text, text_bytes)) || (rc = b.alloc((void**)&d_work, work_bytes)) ||
-        (rc = b.alloc((void**)&d_res, sizeof(uint64_t) * CIR_INDEX_RES_FIELDS * on_dev.size())) ||
-        (rc = b.alloc((void**)&d_runs, 32 * run_recs)))
-      return rc;
-  }
-  const auto t1 = Clock::now();
-  for (size_t k : on_dev)
-    CIR_HIP(hipMemcpyAsync(d_text + tx[k].text_off, tx[k].p, tx[k].len, hipMemcpyHostToDevice, s));
-  if (trace) CIR_HIP(hipStreamSynchronize(s));
-  const auto t2 = Clock::now();
-  for (size_t i = 0; i < on_dev.size(); ++i) {
-    const Text& t = tx[on_dev[i]];
-    CIR_HIP(dev::launch_index_count(d_text + t.text_off, t.len, t.body_off, t.body_end, bs,
-                                    t.len / idxscan::kTokenBytes, t.len / idxscan::kMinRunLine,
-                                    (uint64_t*)(d_work + t.work_off),
-                                    d_res + CIR_INDEX_RES_FIELDS * i, s));
-  }
-  if (!on_dev.empty())
-    CIR_HIP(hipMemcpyAsync(h_res.data(), d_res,
-                           sizeof(uint64_t) * CIR_INDEX_RES_FIELDS * on_dev.size(),
-                           hipMemcpyDeviceToHost, s));
-  CIR_HIP(hipStreamSynchronize(s));
-  const auto t5 = Clock::now();
+  TraceEvents<3> jev;
+  DeviceCall c(ctx);
+  hipStream_t s = c.s;
+  int rc;
+  if ((rc = c.begin()) || (rc = ts.count(c, bs, 0, trace))) return rc;
+  const auto t1 = ts.t_bufs, t2 = ts.t_up, t5 = ts.t_counted;
   // what the count pass declined takes the host parser, that text alone
   std::vector<size_t> declined;
-  for (size_t i = 0; i < on_dev.size(); ++i) {
-    Text& t = tx[on_dev[i]];
-    memcpy(t.res, h_res.data() + CIR_INDEX_RES_FIELDS * i, sizeof t.res);
-    if (t.res[0] != CIR_INDEX_OK) {
+  for (size_t k : on_dev) {
+    Text& t = tx[k];
+    if (!ts.counted_ok(t.slot)) {
       t.dev = false;
-      force_host[on_dev[i]] = 1;
-      declined.push_back(on_dev[i]);
+      force_host[k] = 1;
+      declined.push_back(k);
     } else {
       t.usable = true;
-      t.nblk = t.res[3];
+      t.nblk = ts.item[t.slot].cnt[3];
     }
   }
-  if (!declined.empty()) {  // (the stream is idle and the buffers are this call's own)
-    lk.unlock();
+  if (!declined.empty()) {
+    c.unlock();
     fan_out(declined.size(), [&](size_t i) { host_parse(tx[declined[i]]); });
-    lk.lock();
+    c.lock();
   }
   if (!nw.dev) {
     if (!nw.host_ok) return parse_fail(nw.parsed.bad_hash_size, nw.err);
@@ -588,15 +488,10 @@ int sources_dev_attempt(cir_ctx* ctx, std::vector<Text>& tx, size_t nsrc,
   uint8_t* d_pool = nullptr;
   uint32_t* d_table = nullptr;
   uint32_t* d_match = nullptr;
-  {
-    int rc;
-    if ((rc = b.alloc((void**)&d_need, 32 * n_need)) || (rc = b.alloc((void**)&d_pool, 32 * n_pool)) ||
-        (rc = b.alloc((void**)&d_table, slots * sizeof(uint32_t))) ||
-        (rc = b.alloc((void**)&d_match, (n_need + 4) * sizeof(uint32_t))))
-      return rc;
-  }
-  if (trace)
-    for (hipEvent_t& e : b.ev) CIR_HIP(hipEventCreate(&e));
+  if ((rc = c.alloc(&d_need, 32 * n_need)) || (rc = c.alloc(&d_pool, 32 * n_pool)) ||
+      (rc = c.alloc(&d_table, slots * sizeof(uint32_t))) ||
+      (rc = c.alloc(&d_match, (n_need + 4) * sizeof(uint32_t))) || (trace && (rc = jev.create())))
+    return rc;
   uint64_t at = 0;  // pool ordinal of the next source's block 0
   double upload_ms = 0;
   for (size_t k = 0; k <= nsrc; ++k) {
@@ -605,12 +500,7 @@ int sources_dev_attempt(cir_ctx* ctx, std::vector<Text>& tx, size_t nsrc,
     if (!t.usable) continue;
     uint8_t* dst = j == nsrc ? d_need : d_pool + 32 * at;
     if (t.dev) {
-      const size_t i = std::find(on_dev.begin(), on_dev.end(), j) - on_dev.begin();
-      CIR_HIP(dev::launch_index_emit(d_text + t.text_off, t.len, t.body_off, t.body_end, bs, dst,
-                                     t.nblk, d_runs + 4 * t.runs_off,
-                                     t.len / idxscan::kMinRunLine,
-                                     (uint64_t*)(d_work + t.work_off),
-                                     d_res + CIR_INDEX_RES_FIELDS * i, s));
+      if ((rc = ts.emit(c, t.slot, dst, t.nblk))) return rc;
     } else if (t.nblk) {
       const auto u0 = Clock::now();
       t.digests.resize(32 * t.nblk);
@@ -623,24 +513,12 @@ int sources_dev_attempt(cir_ctx* ctx, std::vector<Text>& tx, size_t nsrc,
   if (trace) CIR_HIP(hipStreamSynchronize(s));
   const auto t7 = Clock::now();
   // the verdicts again (a bad token shows only now) and the run tables
-  if (!on_dev.empty())
-    CIR_HIP(hipMemcpyAsync(h_res.data(), d_res,
-                           sizeof(uint64_t) * CIR_INDEX_RES_FIELDS * on_dev.size(),
-                           hipMemcpyDeviceToHost, s));
-  for (size_t k : on_dev) {
-    Text& t = tx[k];
-    if (!t.dev) continue;
-    t.runs.resize(t.res[2]);
-    if (t.res[2])
-      CIR_HIP(hipMemcpyAsync(t.runs.data(), d_runs + 4 * t.runs_off, 32 * t.res[2],
-                             hipMemcpyDeviceToHost, s));
-  }
-  CIR_HIP(hipStreamSynchronize(s));
+  if ((rc = ts.finish(c, true))) return rc;
   const auto t8 = Clock::now();
   bool again = false;
-  for (size_t i = 0; i < on_dev.size(); ++i)
-    if (tx[on_dev[i]].dev && h_res[CIR_INDEX_RES_FIELDS * i] != CIR_INDEX_OK) {
-      force_host[on_dev[i]] = 1;
+  for (size_t k : on_dev)
+    if (tx[k].dev && ts.status(tx[k].slot) != CIR_INDEX_OK) {
+      force_host[k] = 1;
       again = true;
     }
   if (again) return kRetry;
@@ -658,7 +536,7 @@ int sources_dev_attempt(cir_ctx* ctx, std::vector<Text>& tx, size_t nsrc,
     sources::BlockList* list = j == nsrc ? &need : &pool;
     const uint32_t src = j == nsrc ? 0 : (uint32_t)j;
     if (t.dev) {
-      for (const idxscan::Run& r : t.runs)
+      for (const idxscan::Run& r : ts.item[t.slot].runs)
         list->runs.push_back(sources::FileRun{list->n + r.first, r.size, r.file, src});
       list->n += t.nblk;
     } else {
@@ -669,7 +547,7 @@ int sources_dev_attempt(cir_ctx* ctx, std::vector<Text>& tx, size_t nsrc,
   }
   stats[6] = slots;
   hipError_t e = dev::launch_join(d_need, n_need, d_pool, n_pool, d_table, slots, draw_seed(),
-                                  d_match, d_match + n_need, s, trace ? b.ev : nullptr);
+                                  d_match, d_match + n_need, s, trace ? jev.ev : nullptr);
   if (e != hipSuccess) return hip_fail(e, "launch_join");
   if (trace) CIR_HIP(hipStreamSynchronize(s));
   const auto t9 = Clock::now();
@@ -681,18 +559,16 @@ int sources_dev_attempt(cir_ctx* ctx, std::vector<Text>& tx, size_t nsrc,
                            s));
     CIR_HIP(hipStreamSynchronize(s));
     t10 = Clock::now();
-    const int rc = answer_on_host(ans, need, pool, bs, want, match.data());
-    if (rc) return rc;
+    if ((rc = answer_on_host(ans, need, pool, bs, want, match.data()))) return rc;
   } else {
-    const int rc = answer_on_device(ans, need, pool, n_pool, bs, want, d_match, &b, &tabs, x_res, s,
-                                    trace, laps);
-    if (rc) return rc;
+    if ((rc = answer_on_device(ans, need, pool, n_pool, bs, want, d_match, c, &tabs, x_res, trace,
+                               laps)))
+      return rc;
     t10 = Clock::now();
   }
   if (trace) {
-    float f = 0;
-    if (hipEventElapsedTime(&f, b.ev[0], b.ev[1]) == hipSuccess) laps->build = f;
-    if (hipEventElapsedTime(&f, b.ev[1], b.ev[2]) == hipSuccess) laps->probe = f;
+    laps->build = jev.lap(0);
+    laps->probe = jev.lap(1);
     laps->frame += ms_between(t0, t1);  // (with the host's share and the buffers' hipMalloc)
     laps->text_upload += ms_between(t1, t2);
     laps->count += ms_between(t2, t5);

@@ -1,9 +1,11 @@
 // cir_block_sources' host side, header-only and free of HIP: the need list and
 // the pool of two or more parsed indexes, the host join and the mapping of a
 // pool ordinal back to (source, file, block), and the merge of those into
-// extents (cir_block_extents; the continuation rule is extents.hpp).  Compiled
-// alone by tools/sources_fuzz.cpp and tools/extents_fuzz.cpp (with dirsig.cpp)
-// under the sanitizers.
+// extents (cir_block_extents; the continuation rule is extents.hpp), handed
+// over as malloc'd arrays by extents_owned (the host tail of cir_block_extents
+// and cir_block_repeats), and pack_runs, the run tables as the kernels read
+// them.  Compiled alone by tools/sources_fuzz.cpp, tools/extents_fuzz.cpp and
+// tools/repeats_fuzz.cpp (with dirsig.cpp) under the sanitizers.
 //
 // The rule (include/ciruela_blockhash.h, cir_block_sources): the need list is
 // the new index's file entries in index order, blocks ascending; the pool is
@@ -15,6 +17,7 @@
 // whose two blocks differ in length is dropped and no second one looked for.
 #pragma once
 #include <stdint.h>
+#include <stdlib.h>
 #include <string.h>
 
 #include <algorithm>
@@ -232,6 +235,51 @@ inline uint64_t extents_of(const BlockList& need, uint64_t bs, const uint64_t* w
     }
   }
   return left;
+}
+
+// extents_of with its results handed over: *fetch (ceil(need.n / 64) words)
+// and *rec (*count records; null when there is none) are malloc'd and the
+// caller's, *left is extents_of's count.  False when memory ran out, with
+// nothing allocated and nothing written to the four.
+inline bool extents_owned(const BlockList& need, uint64_t bs, const uint64_t* want,
+                          const uint32_t* src, const uint64_t* file, const uint64_t* block,
+                          uint64_t** rec, size_t* count, uint64_t** fetch, uint64_t* left) {
+  const uint64_t nwords = (need.n + 63) / 64;
+  uint64_t* f = (uint64_t*)malloc((nwords ? nwords : 1) * sizeof(uint64_t));
+  if (!f) return false;
+  std::vector<Extent> ex;
+  uint64_t l = 0;
+  try {
+    l = extents_of(need, bs, want, src, file, block, &ex, f);
+  } catch (...) {
+    free(f);
+    throw;
+  }
+  uint64_t* r = nullptr;
+  if (!ex.empty()) {
+    r = (uint64_t*)malloc(ex.size() * sizeof(Extent));
+    if (!r) {
+      free(f);
+      return false;
+    }
+    memcpy(r, ex.data(), ex.size() * sizeof(Extent));
+  }
+  *rec = r;
+  *count = ex.size();
+  *fetch = f;
+  *left = l;
+  return true;
+}
+
+// The run table of list as the kernels read it: four u64 per run {first,
+// size, file, src} to out (4 x list.runs.size() words).
+inline void pack_runs(const BlockList& list, uint64_t* out) {
+  for (const FileRun& r : list.runs) {
+    *out++ = r.first;
+    *out++ = r.size;
+    *out++ = r.file;
+    *out++ = r.src;
+  }
 }
 
 }  // namespace sources

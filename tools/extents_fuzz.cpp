@@ -224,6 +224,21 @@ static void honest_case() {
   uint64_t sum = 0;
   for (const sources::Extent& e : ref) sum += e.bytes;
   CHECK(sum == bytes);
+  // the same through the tail the whole calls share: the records and the
+  // bitmap come back malloc'd and are this case's to free (the leak check
+  // watches the ownership)
+  uint64_t* o_rec = nullptr;
+  uint64_t* o_fetch = nullptr;
+  size_t o_count = ~(size_t)0;
+  uint64_t o_left = ~0ull;
+  CHECK(sources::extents_owned(need, B, want, so, fo, bo, &o_rec, &o_count, &o_fetch, &o_left));
+  CHECK(o_count == ref.size() && (o_rec == nullptr) == ref.empty());
+  CHECK(ref.empty() || memcmp(o_rec, ref.data(), ref.size() * sizeof(sources::Extent)) == 0);
+  CHECK(o_fetch != nullptr && o_left == wanted - found);
+  for (uint64_t g = 0; g < 64 * nwords; ++g)
+    CHECK((o_fetch[g / 64] >> (g % 64) & 1) == (uint64_t)(g < n && plain[g].wanted && !plain[g].found));
+  free(o_rec);
+  free(o_fetch);
   free(so);
   free(fo);
   free(bo);

@@ -201,6 +201,18 @@ static void one_case() {
   }
   CHECK(at == ex.size());
   for (uint64_t g = n; g < 64 * nwords; ++g) CHECK(!bit_of(fetch.p, g));  // no bit at or past n
+  // the tail cir_block_repeats runs with ctx = NULL hands the same over, malloc'd
+  uint64_t* o_rec = nullptr;
+  uint64_t* o_fetch = nullptr;
+  size_t o_count = 0;
+  uint64_t o_left = 0;
+  CHECK(sources::extents_owned(need, bs, want, src.p, sfile.p, sblock.p, &o_rec, &o_count, &o_fetch,
+                               &o_left));
+  CHECK(o_count == ex.size() && o_left == left && (o_rec == nullptr) == ex.empty());
+  CHECK(ex.empty() || memcmp(o_rec, ex.data(), ex.size() * sizeof(sources::Extent)) == 0);
+  CHECK(nwords == 0 || memcmp(o_fetch, fetch.p, 8 * nwords) == 0);
+  free(o_rec);
+  free(o_fetch);
   // no block is both a source and a destination
   for (uint64_t g = 0; g < n; ++g)
     if (pl[g].repeat) CHECK(!pl[pl[g].leader].repeat && pl[pl[g].leader].part);
