@@ -63,6 +63,15 @@ file_sources,                   link_candidates' rule with the texts parsed and 
   Context.index_files_dev,      joined on the device: file records, a fold of each
   Context.match_files_dev       file's digests, a table keyed by (source, path)
                                 (src/daemon/metadata/hardlink_sources.rs:107-153)
+file_copies,                    the step behind it: candidates matched by content at any
+  Context.match_copies_dev      path (a renamed directory, a moved file), the first
+                                source and the first place inside it; a table keyed by
+                                {size, exe, fold}; the reference has no counterpart
+                                (src/daemon/metadata/hardlink_sources.rs:121-146)
+check_links_at,                 check_links with a place per candidate: the verify of a
+  Context.check_links_at        file_copies candidate at the path where the source
+                                holds it (src/daemon/disk/public.rs:308-346 with
+                                another path)
 index_digests,                  what every consumer of an index starts with: its block
   Context.index_digests_dev     digests as one array and a run record per non-empty
                                 file, parsed on the device (the reference parses the
@@ -87,7 +96,7 @@ __all__ = [
     "check_blocks", "BlocksResult", "block_sources", "SourcesResult",
     "block_extents", "ExtentsResult", "Extent",
     "block_repeats", "RepeatsResult",
-    "index_digests", "IndexDigests", "file_sources",
+    "index_digests", "IndexDigests", "file_sources", "file_copies", "check_links_at",
 ]
 
 DEFAULT_BLOCK_SIZE = 32768
@@ -408,6 +417,24 @@ class Context:
                                             d_pool_verify, seed, d_work, work_bytes, d_cand_src,
                                             d_cand_file, d_res, stream))
 
+    def match_copies_dev(self, need, pool, d_src_first, nsrc, block_size, seed, d_work,
+                         work_bytes, d_cand_src, d_cand_file, d_cand_place, d_res, d_skip=0,
+                         d_pool_verify=0, stream=0):
+        """The join behind file_copies on device-resident records
+        (cir_match_copies_dev).  need / pool: (d_files, n_files, d_digests,
+        n_blocks); d_src_first: nsrc + 1 u64.  Per need file that is not empty
+        and whose bit in d_skip (u64 words over file ordinals; 0: none) is
+        clear, the pool file of the smallest ordinal with equal exe flag, size
+        and digests, at any path: d_cand_src[i] (u32; 2^32-1: none),
+        d_cand_file[i] (u64, the ordinal inside that source) and
+        d_cand_place[2 i ..] (u64: that pool record's name_off and dir_off);
+        d_res: 4 u64 {status, candidates, their bytes, need files}.  d_work:
+        cir_match_copies_work_bytes(n_need_files, n_pool_files) bytes that the
+        call initialises.  All written by the call, on `stream` alone."""
+        _n.check(_n.lib.cir_match_copies_dev(self._h, *need, *pool, d_src_first, nsrc, block_size,
+                                             d_skip, d_pool_verify, seed, d_work, work_bytes,
+                                             d_cand_src, d_cand_file, d_cand_place, d_res, stream))
+
     # ---- asynchronous per-block verify (FetchBlock::poll, fetch_blocks.rs:77)
     def verify_submit(self, data, expected, hash_type=None):
         """Queue one block with its expected digest; returns a ticket."""
@@ -502,6 +529,19 @@ class Context:
         `links`: (file ordinal, source ordinal) pairs as link_candidates
         returns them.  A LinksResult with one verdict per candidate; nothing
         is linked."""
+        return self._check_links(index, roots, links, None, threads, False)
+
+    def check_links_at(self, index, roots, links, paths, threads=0):
+        """check_links with a place per candidate (cir_check_links_at):
+        candidate i is looked for under its source root at paths[i] (bytes, as
+        file_copies returns them; b"": the entry's own path) and must have the
+        size, mode bits and digests of file entry links[i][0] of `index`.
+        paths=None is check_links.  A path with a `.` or `..` component, or
+        made of slashes only, raises CiruelaError (CIR_EINVAL) before any file
+        is opened."""
+        return self._check_links(index, roots, links, paths, threads, True)
+
+    def _check_links(self, index, roots, links, paths, threads, at):
         if len(index):
             ptr, keep = _buf(index)
         else:  # (an empty index is a parse error, not a null argument)
@@ -523,8 +563,23 @@ class Context:
         kinds = (ctypes.c_uint8 * max(n, 1))()
         errnos = (ctypes.c_int32 * max(n, 1))()
         stats = (ctypes.c_uint64 * _n.CIR_LINKS_STATS_FIELDS)()
-        _n.check(_n.lib.cir_check_links(self._h, ptr, len(index), fds, dirs, nsrc, lf, ls, n,
-                                        threads, kinds, errnos, stats))
+        if at:
+            offs, blob = None, None
+            if paths is not None:
+                paths = [bytes(p) for p in paths]
+                if len(paths) != n:
+                    raise ValueError("one path per candidate")
+                acc = [0]
+                for p in paths:
+                    acc.append(acc[-1] + len(p))
+                offs = (ctypes.c_uint64 * (n + 1))(*acc)
+                blob = ctypes.cast(ctypes.create_string_buffer(b"".join(paths), max(acc[-1], 1)),
+                                   ctypes.c_void_p)
+            _n.check(_n.lib.cir_check_links_at(self._h, ptr, len(index), fds, dirs, nsrc, lf, ls,
+                                               offs, blob, n, threads, kinds, errnos, stats))
+        else:
+            _n.check(_n.lib.cir_check_links(self._h, ptr, len(index), fds, dirs, nsrc, lf, ls, n,
+                                            threads, kinds, errnos, stats))
         del keep
         return LinksResult(index, links, list(kinds)[:n], list(errnos)[:n],
                            dict(zip(self.LINKS_STATS_FIELDS, list(stats))))
@@ -1413,6 +1468,11 @@ def check_links(index, roots, links, threads=0, context=None):
     return (context or default_context()).check_links(index, roots, links, threads)
 
 
+def check_links_at(index, roots, links, paths, threads=0, context=None):
+    """Context.check_links_at on the default context."""
+    return (context or default_context()).check_links_at(index, roots, links, paths, threads)
+
+
 def check_blocks(root, index, threads=0, dir_fd=None, context=None):
     """Context.check_blocks on the default context."""
     return (context or default_context()).check_blocks(root, index, threads, dir_fd)
@@ -1430,6 +1490,63 @@ def file_sources(index, sources, context=None):
     a context the host rule runs (no default context is opened).  Returns
     ([(file ordinal, source ordinal)], stats dict)."""
     return _candidates(index, sources, context, True)
+
+
+FILE_COPIES_STATS = FILE_SOURCES_STATS + ("skipped_files", "same_path")
+
+
+def file_copies(index, sources, context=None, skip=None):
+    """Hardlink candidates matched by content (cir_file_copies): for every file
+    entry of `index` that is not empty and not in `skip` (an iterable of file
+    ordinals, or None), the first of `sources` that holds a file with equal exe
+    flag, size and digests at any path, and the first such file inside it.
+    With a context the texts are parsed and the files joined on its first GPU;
+    whatever the device cannot answer exactly is answered by the host rule
+    (stats["why_host"]: a CIR_FILE_WHY_* code).  Without a context the host
+    rule runs (no default context is opened).  Returns ([(file ordinal, source
+    ordinal, file ordinal inside the source, source path bytes)], stats
+    dict)."""
+    if len(index):
+        ptr, keep = _buf(index)
+    else:
+        keep = ctypes.create_string_buffer(1)
+        ptr = ctypes.cast(keep, ctypes.c_void_p)
+    nsrc = len(sources)
+    bufs = [ctypes.create_string_buffer(bytes(s), max(len(s), 1)) for s in sources]
+    sp = (ctypes.c_void_p * max(nsrc, 1))(*[ctypes.cast(b, ctypes.c_void_p) for b in bufs])
+    sl = (ctypes.c_size_t * max(nsrc, 1))(*[len(s) for s in sources])
+    bitmap = None
+    if skip is not None:
+        # (sized for every ordinal the index can hold: its shortest file line is 8 bytes)
+        words = [0] * (len(index) // 512 + 1)
+        for i in skip:
+            if i < 0 or i >= 64 * len(words):
+                raise ValueError("no file entry %d in an index of %d bytes" % (i, len(index)))
+            words[i >> 6] |= 1 << (i & 63)
+        bitmap = (ctypes.c_uint64 * len(words))(*words)
+    outs = [ctypes.c_void_p() for _ in range(5)]
+    n = ctypes.c_size_t()
+    skipped = ctypes.c_size_t()
+    stats = (ctypes.c_uint64 * _n.CIR_FILE_COPIES_STATS_FIELDS)()
+    _n.check(_n.lib.cir_file_copies(context.handle if context is not None else None, ptr,
+                                    len(index), sp, sl, nsrc, bitmap,
+                                    *[ctypes.byref(o) for o in outs], ctypes.byref(n),
+                                    ctypes.byref(skipped), stats))
+    del keep
+    found = []
+    if n.value:
+        k = n.value
+        files = list((ctypes.c_uint64 * k).from_address(outs[0].value))
+        srcs = list((ctypes.c_uint32 * k).from_address(outs[1].value))
+        sfiles = list((ctypes.c_uint64 * k).from_address(outs[2].value))
+        offs = list((ctypes.c_uint64 * (k + 1)).from_address(outs[3].value))
+        paths = ctypes.string_at(outs[4].value, offs[k])
+        for o in outs:
+            _n.lib.cir_free(o)
+        found = [(files[i], srcs[i], sfiles[i], paths[offs[i]:offs[i + 1]]) for i in range(k)]
+    st = dict(zip(FILE_COPIES_STATS, list(stats)))
+    st["skipped"] = skipped.value
+    return found, st
 
 
 def link_candidates(index, sources):

@@ -70,6 +70,7 @@ CIR_FILE_WHY_DECLINED = 1
 CIR_FILE_WHY_COLLISION = 2
 CIR_FILE_WHY_LIMIT = 3
 CIR_FILE_WHY_ENV = 4
+CIR_FILE_COPIES_STATS_FIELDS = 10
 CIR_INDEX_STATS_FIELDS = 4
 CIR_INDEX_OK = 0
 CIR_INDEX_CAPACITY = 1
@@ -174,6 +175,11 @@ _SIGS = {
                                        ctypes.POINTER(ctypes.c_char_p), ctypes.c_size_t, c_u64p,
                                        c_u32p, ctypes.c_size_t, ctypes.c_uint32, c_u8p,
                                        ctypes.POINTER(ctypes.c_int32), c_u64p]),
+    "cir_check_links_at": (ctypes.c_int, [c_vp, c_vp, ctypes.c_size_t,
+                                          ctypes.POINTER(ctypes.c_int),
+                                          ctypes.POINTER(ctypes.c_char_p), ctypes.c_size_t, c_u64p,
+                                          c_u32p, c_u64p, c_vp, ctypes.c_size_t, ctypes.c_uint32,
+                                          c_u8p, ctypes.POINTER(ctypes.c_int32), c_u64p]),
     "cir_verify_bitmap_dev": (ctypes.c_int, [c_vp, ctypes.c_int, c_vp, ctypes.c_uint64, c_vp, c_vp,
                                              ctypes.c_size_t, c_vp, c_vp, c_vp, c_vp, c_vp]),
     "cir_check_blocks": (ctypes.c_int, [c_vp, ctypes.c_int, ctypes.c_char_p, c_vp, ctypes.c_size_t,
@@ -229,6 +235,17 @@ _SIGS = {
     "cir_file_sources": (ctypes.c_int, [c_vp, c_vp, ctypes.c_size_t, ctypes.POINTER(c_vp),
                                         c_sizep, ctypes.c_size_t, ctypes.POINTER(c_vp),
                                         ctypes.POINTER(c_vp), c_sizep, c_sizep, c_u64p]),
+    "cir_match_copies_work_bytes": (ctypes.c_uint64, [ctypes.c_uint64, ctypes.c_uint64]),
+    "cir_match_copies_dev": (ctypes.c_int, [c_vp, c_vp, ctypes.c_uint64, c_vp, ctypes.c_uint64,
+                                            c_vp, ctypes.c_uint64, c_vp, ctypes.c_uint64, c_vp,
+                                            ctypes.c_uint64, ctypes.c_uint64, c_vp, c_vp,
+                                            ctypes.c_uint64, c_vp, ctypes.c_uint64, c_vp, c_vp,
+                                            c_vp, c_vp, c_vp]),
+    "cir_file_copies": (ctypes.c_int, [c_vp, c_vp, ctypes.c_size_t, ctypes.POINTER(c_vp),
+                                       c_sizep, ctypes.c_size_t, c_u64p, ctypes.POINTER(c_vp),
+                                       ctypes.POINTER(c_vp), ctypes.POINTER(c_vp),
+                                       ctypes.POINTER(c_vp), ctypes.POINTER(c_vp), c_sizep,
+                                       c_sizep, c_u64p]),
     "cir_debug_compress_only_dev": (ctypes.c_int, [ctypes.c_uint64, ctypes.c_uint32, c_vp, c_vp]),
     "cir_debug_relay_blocks": (ctypes.c_uint64, [ctypes.c_uint64, ctypes.c_uint64]),
     "cir_debug_device_identity": (ctypes.c_int, [ctypes.c_int, ctypes.c_char_p, ctypes.c_size_t,

@@ -53,12 +53,15 @@
 #include <algorithm>
 #include <atomic>
 #include <chrono>
+#include <deque>
+#include <map>
 #include <mutex>
 #include <string>
 #include <vector>
 
 #include "bits.hpp"
 #include "dirsig.hpp"
+#include "linkpath.hpp"
 #include "pack.hpp"
 #include "runtime.hpp"
 #include "stripes.hpp"
@@ -708,12 +711,23 @@ int check_impl(cir_ctx* ctx, int dirfd, const char* dir, const uint8_t* index, s
 // segment table (one segment = one candidate's run of blocks in the batch)
 // travels up with the descriptors, k_seg_bad answers per segment, and 16 +
 // nseg bytes come back.
+//
+// cir_check_links_at is the same call with a place per candidate: the
+// candidate is looked for at a path the caller gives (cir_file_copies': the
+// file's path in the source) instead of the entry's own.  A candidate carries
+// its place, a directory and a name; the directories of the given paths are
+// interned behind the index's own in Layout::dirs, so DirCache and ReadJob
+// serve both.  What is expected of the file -- size, mode bits, digests -- is
+// the entry's either way.  The paths come from another party's index and are
+// validated before any I/O (linkpath.hpp).
 
 struct Cand {
-  size_t item = 0;         // index into Links::items
+  size_t item = 0;         // index into Links::items: what the file must be
   uint32_t src = 0;        // source root
   size_t out = 0;          // the caller's candidate number
   uint64_t first_blk = 0;  // global index of block 0 in the work order
+  size_t dir = 0;          // where it is looked for: index into Layout::dirs ...
+  const std::string* name = nullptr;  // ... and the name there (the item's, or one of Links::names)
 };
 
 // (Layout::nblk_total and Item::first_blk count every file entry's blocks;
@@ -722,6 +736,7 @@ struct Links : Layout {
   std::vector<int> roots;   // per source: its fd, or -1 with root_err
   std::vector<int> root_err;
   std::vector<Cand> cands;  // the non-empty candidates below a root that opened, in work order
+  std::deque<std::string> names;  // the names of the caller's paths (addresses stay)
   uint64_t nblk_cand = 0;
   std::mutex mu;
   uint8_t* kind = nullptr;  // per candidate of the caller
@@ -746,10 +761,11 @@ struct Links : Layout {
 // The packer's look at a candidate (try_hardlink without the read): READ,
 // CHECKSUM on a length or mode bits (public.rs:331-338) that are not the
 // entry's, else what identifies the file to the readers.
-int examine_link(Links& L, const DirFd& d, const Item& it, Seen* seen, int* err) {
+int examine_link(Links& L, const DirFd& d, const std::string& name, const Item& it, Seen* seen,
+                 int* err) {
   int fd = -1;
   struct stat st;
-  const int kind = open_listed(L.fds, d, it.name, &fd, &st, err);
+  const int kind = open_listed(L.fds, d, name, &fd, &st, err);
   if (kind) return kind;
   L.fds.close(fd);
   if ((uint64_t)st.st_size != it.size) return CIR_CHECK_CHECKSUM;
@@ -797,7 +813,7 @@ int links_range(cir_ctx* ctx, Device& d, Links& L, unsigned threads, const Block
       const Item& it = L.items[c.item];
       if (cur.looked != cur.ui) {
         int err = 0;
-        const int kind = examine_link(L, dir.of(L.roots[c.src], it.dir), it, &seen, &err);
+        const int kind = examine_link(L, dir.of(L.roots[c.src], c.dir), *c.name, it, &seen, &err);
         if (kind) {
           L.report(c.out, kind, err);
           cur.advance(cur.left());  // its blocks in this range are passed over
@@ -814,7 +830,7 @@ int links_range(cir_ctx* ctx, Device& d, Links& L, unsigned threads, const Block
       // a failed read makes READ of its own candidate and of nothing else (its
       // bytes in the slot are then whatever they are: READ wins over what the
       // compare finds)
-      cut_pieces(jobs, ReadJob{L.roots[c.src], it.dir, &it.name, seen, it.size, it.size,
+      cut_pieces(jobs, ReadJob{L.roots[c.src], c.dir, c.name, seen, it.size, it.size,
                                fblk * L.bs, r.bytes, s.h_data + r.pos, c.out});
       s.h_seg_end[segs.size()] = (uint32_t)b.n;  // (at most one segment per block: <= cap_blk)
       segs.push_back(c.out);
@@ -848,12 +864,16 @@ int links_range(cir_ctx* ctx, Device& d, Links& L, unsigned threads, const Block
   return CIR_OK;
 }
 
+// link_path_off == nullptr: cir_check_links, every candidate at its entry's own path.
 int links_impl(cir_ctx* ctx, const uint8_t* index, size_t len, const int* src_dirfd,
                const char* const* src_dir, size_t nsrc, const uint64_t* link_file,
-               const uint32_t* link_src, size_t nlinks, uint32_t threads, uint8_t* kind_out,
-               int32_t* errno_out, uint64_t* stats) {
+               const uint32_t* link_src, const uint64_t* link_path_off, const uint8_t* link_paths,
+               size_t nlinks, uint32_t threads, uint8_t* kind_out, int32_t* errno_out,
+               uint64_t* stats) {
   if (!ctx || !index || !stats || (nsrc && (!src_dirfd || !src_dir)) ||
       (nlinks && (!link_file || !link_src || !kind_out)))
+    return fail(CIR_EINVAL, "null pointer");
+  if (link_path_off && nlinks && link_path_off[nlinks] > link_path_off[0] && !link_paths)
     return fail(CIR_EINVAL, "null pointer");
   for (int i = 0; i < CIR_LINKS_STATS_FIELDS; ++i) stats[i] = 0;
   const auto t_start = std::chrono::steady_clock::now();
@@ -868,6 +888,36 @@ int links_impl(cir_ctx* ctx, const uint8_t* index, size_t len, const int* src_di
   for (size_t i = 0; i < nlinks; ++i)
     if (link_file[i] >= L.items.size())
       return fail(CIR_EINVAL, "link_file is past the last file entry");
+  // the candidates' places: the entry's own, or the caller's path split and
+  // validated, its directory interned behind the index's own
+  std::vector<size_t> place_dir(nlinks);
+  std::vector<const std::string*> place_name(nlinks);
+  std::vector<char> nul_path(nlinks, 0);
+  {
+    std::map<std::vector<std::string>, size_t> interned;
+    std::vector<std::string> comps;
+    for (size_t i = 0; i < nlinks; ++i) {
+      const Item& it = L.items[(size_t)link_file[i]];
+      place_dir[i] = it.dir;
+      place_name[i] = &it.name;
+      if (!link_path_off) continue;
+      if (link_path_off[i + 1] < link_path_off[i])
+        return fail(CIR_EINVAL, "link_path_off must not decrease");
+      const linkpath::Verdict v = linkpath::split(link_paths + link_path_off[i],
+                                                  (size_t)(link_path_off[i + 1] - link_path_off[i]),
+                                                  &comps);
+      if (v == linkpath::kInvalid)
+        return fail(CIR_EINVAL, "a candidate's path has a `.` or `..` component or no component");
+      if (v == linkpath::kNul) nul_path[i] = 1;
+      if (v != linkpath::kOk) continue;
+      L.names.push_back(std::move(comps.back()));
+      place_name[i] = &L.names.back();
+      comps.pop_back();
+      const auto at = interned.emplace(comps, L.dirs.size());
+      if (at.second) L.dirs.push_back(comps);
+      place_dir[i] = at.first->second;
+    }
+  }
   // ---- nothing above touched a file or a device
   const double ms_parse = ms_since(t_start);
   const auto t_roots = std::chrono::steady_clock::now();
@@ -890,11 +940,14 @@ int links_impl(cir_ctx* ctx, const uint8_t* index, size_t len, const int* src_di
   for (size_t i = 0; i < nlinks; ++i) used[link_src[i]] = 1;
   for (size_t j = 0; j < nsrc; ++j)
     if (used[j]) L.roots[j] = open_root(L.fds, src_dirfd[j], src_dir[j], &L.root_err[j]);
-  // the work order: by root, then by index order
+  // the work order: by root, then by directory, then by index order (the index's own
+  // directories ascend with the file ordinals: without paths this is root, then index order)
   std::vector<size_t> order(nlinks);
   for (size_t i = 0; i < nlinks; ++i) order[i] = i;
   std::stable_sort(order.begin(), order.end(), [&](size_t a, size_t b) {
-    return link_src[a] != link_src[b] ? link_src[a] < link_src[b] : link_file[a] < link_file[b];
+    if (link_src[a] != link_src[b]) return link_src[a] < link_src[b];
+    if (place_dir[a] != place_dir[b]) return place_dir[a] < place_dir[b];
+    return link_file[a] < link_file[b];
   });
   {
     DirCache cur(L);
@@ -903,14 +956,18 @@ int links_impl(cir_ctx* ctx, const uint8_t* index, size_t len, const int* src_di
       c.item = (size_t)link_file[i];
       c.src = link_src[i];
       c.out = i;
+      c.dir = place_dir[i];
+      c.name = place_name[i];
       const Item& it = L.items[c.item];
       if (L.roots[c.src] < 0) {
         L.report(i, CIR_CHECK_READ, L.root_err[c.src]);
+      } else if (nul_path[i]) {
+        L.report(i, CIR_CHECK_READ, EINVAL);  // (no such name can be opened)
       } else if (it.nblk == 0) {
         // a size-0 candidate: an empty regular file of the right mode, seen by the host alone
         Seen seen;
         int e = 0;
-        const int kind = examine_link(L, cur.of(L.roots[c.src], it.dir), it, &seen, &e);
+        const int kind = examine_link(L, cur.of(L.roots[c.src], c.dir), *c.name, it, &seen, &e);
         if (kind) L.report(i, kind, e);
         ++stats[7];
       } else {
@@ -929,9 +986,9 @@ int links_impl(cir_ctx* ctx, const uint8_t* index, size_t len, const int* src_di
   stats[6] = L.fds.peak.load();
   if (trace_enabled())
     fprintf(stderr,
-            "cir check_links: %zu candidates; index parse %.2f ms, roots, work order and size-0 "
+            "cir check_links%s: %zu candidates; index parse %.2f ms, roots, work order and size-0 "
             "candidates %.2f ms, pipeline %.2f ms\n",
-            nlinks, ms_parse, ms_roots, ms_since(t_pipe));
+            link_path_off ? "_at" : "", nlinks, ms_parse, ms_roots, ms_since(t_pipe));
   if (rc) return rc;
   for (size_t i = 0; i < nlinks; ++i) {
     ++stats[kind_out[i] == CIR_CHECK_OK ? 0 : kind_out[i] == CIR_CHECK_CHECKSUM ? 1 : 2];
@@ -1245,8 +1302,18 @@ extern "C" int cir_check_links(cir_ctx* ctx, const uint8_t* index, size_t len,
                                const uint64_t* link_file, const uint32_t* link_src, size_t nlinks,
                                uint32_t threads, uint8_t* kind_out, int32_t* errno_out,
                                uint64_t stats[CIR_LINKS_STATS_FIELDS]) try {
-  return cir::links_impl(ctx, index, len, src_dirfd, src_dir, nsrc, link_file, link_src, nlinks,
-                         threads, kind_out, errno_out, stats);
+  return cir::links_impl(ctx, index, len, src_dirfd, src_dir, nsrc, link_file, link_src, nullptr,
+                         nullptr, nlinks, threads, kind_out, errno_out, stats);
+} CIR_CATCH_BOUNDARY
+
+extern "C" int cir_check_links_at(cir_ctx* ctx, const uint8_t* index, size_t len,
+                                  const int* src_dirfd, const char* const* src_dir, size_t nsrc,
+                                  const uint64_t* link_file, const uint32_t* link_src,
+                                  const uint64_t* link_path_off, const uint8_t* link_paths,
+                                  size_t nlinks, uint32_t threads, uint8_t* kind_out,
+                                  int32_t* errno_out, uint64_t stats[CIR_LINKS_STATS_FIELDS]) try {
+  return cir::links_impl(ctx, index, len, src_dirfd, src_dir, nsrc, link_file, link_src,
+                         link_path_off, link_paths, nlinks, threads, kind_out, errno_out, stats);
 } CIR_CATCH_BOUNDARY
 
 extern "C" int cir_check_index(cir_ctx* ctx, int dirfd, const char* dir, const uint8_t* index,

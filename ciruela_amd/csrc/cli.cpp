@@ -20,6 +20,7 @@
 //       exit 0 when every listed file matches, else exit 1 with one line,
 //       `checksum: <path>` or `read: <path>: <strerror>`
 //   ciruela-index links INDEX SRCDIR=SRCINDEX [SRCDIR=SRCINDEX ...] [--disk-threads N] [--host]
+//                       [--any-path]
 //       the daemon's hardlink step before a download (scan_links, src/daemon/
 //       metadata/hardlink_sources.rs:107-153, then check_and_hardlink, src/
 //       daemon/disk/public.rs:285-346): which files of the new image INDEX
@@ -30,12 +31,26 @@
 //       stderr, and exits 0 when the check ran.  Nothing is linked.  The
 //       candidates come from cir_file_sources on the context the check uses;
 //       --host takes them from cir_link_candidates (the output is the same).
+//       --any-path adds, for the files without such a candidate, the ones
+//       cir_file_copies finds by content at another path, and verifies all of
+//       them in one cir_check_links_at call; those print
+//       `SRCDIR<TAB>PATH<TAB>SRCPATH` (the path in the source, escaped).
 //   ciruela-index candidates INDEX SRCINDEX [SRCINDEX ...] [--host]
 //       the first half of that step alone (cir_file_sources; no file is
 //       read): one line `FILE# SRC# PATH` per candidate -- the file ordinal in
 //       INDEX, the ordinal of the first SRCINDEX (best first) that lists the
 //       path with equal exe flag, size and digests, the path as the index
 //       spells it.  --host passes no context and opens no device.
+//   ciruela-index copies INDEX SRCINDEX [SRCINDEX ...] [--host] [--unlinked]
+//       the step behind that one (cir_file_copies; no file is read): the
+//       files an older image holds unchanged at any path -- below a renamed
+//       directory, moved, vendored twice.  One line `FILE# SRC# SRCFILE# PATH
+//       SRCPATH` per candidate: the file ordinal in INDEX, the first SRCINDEX
+//       (best first) that holds a file with equal exe flag, size and digests,
+//       the first such file's ordinal in it, the path in INDEX as the index
+//       spells it and the path in the source, escaped.  --unlinked first runs
+//       the `candidates` rule and leaves out the files it found.  --host
+//       passes no context and opens no device.
 //   ciruela-index blocks DIR INDEX_FILE [--list] [--disk-threads N]
 //       which blocks of INDEX_FILE the partial image in DIR already holds
 //       (cir_check_blocks); --list prints `PATH OFFSET` per missing block
@@ -83,8 +98,9 @@ static void usage() {
           "       ciruela-index hash [--block-size N] FILE...\n"
           "       ciruela-index check DIR INDEX_FILE [--disk-threads N]\n"
           "       ciruela-index links INDEX SRCDIR=SRCINDEX [SRCDIR=SRCINDEX ...]"
-          " [--disk-threads N] [--host]\n"
+          " [--disk-threads N] [--host] [--any-path]\n"
           "       ciruela-index candidates INDEX SRCINDEX [SRCINDEX ...] [--host]\n"
+          "       ciruela-index copies INDEX SRCINDEX [SRCINDEX ...] [--host] [--unlinked]\n"
           "       ciruela-index blocks DIR INDEX_FILE [--list] [--disk-threads N]\n"
           "       ciruela-index sources INDEX SRCINDEX [SRCINDEX ...] [--list] [--host]"
           " [--extents]\n"
@@ -97,6 +113,23 @@ static std::string hex(const uint8_t* p, size_t n) {
   for (size_t i = 0; i < n; ++i) {
     s += k[p[i] >> 4];
     s += k[p[i] & 15];
+  }
+  return s;
+}
+
+// A decoded path as an index spells it: bytes outside printable ASCII, the
+// space and the backslash as \xNN.
+static std::string escape_path(const uint8_t* p, size_t n) {
+  static const char k[] = "0123456789abcdef";
+  std::string s;
+  for (size_t i = 0; i < n; ++i) {
+    if (p[i] > 0x20 && p[i] < 0x7f && p[i] != '\\') {
+      s += (char)p[i];
+    } else {
+      s += "\\x";
+      s += k[p[i] >> 4];
+      s += k[p[i] & 15];
+    }
   }
   return s;
 }
@@ -264,6 +297,7 @@ int main(int argc, char** argv) {
   uint64_t bs = CIR_DEFAULT_BLOCK_SIZE;
   std::string index_dir;
   bool list_blocks = false, host_only = false, extents = false, host_candidates = false;
+  bool unlinked = false, any_path = false;
   std::vector<Job> jobs;
   std::vector<std::string> files;
   for (int i = 2; i < argc; ++i) {
@@ -294,9 +328,12 @@ int main(int argc, char** argv) {
     }
     else if (a == "--index-dir") index_dir = val();
     else if (a == "--list" && (cmd == "blocks" || cmd == "sources")) list_blocks = true;
-    else if (a == "--host" && (cmd == "sources" || cmd == "repeats" || cmd == "candidates"))
+    else if (a == "--host" &&
+             (cmd == "sources" || cmd == "repeats" || cmd == "candidates" || cmd == "copies"))
       host_only = true;
+    else if (a == "--unlinked" && cmd == "copies") unlinked = true;
     else if (a == "--host" && cmd == "links") host_candidates = true;
+    else if (a == "--any-path" && cmd == "links") any_path = true;
     else if (a == "--extents" && cmd == "sources") extents = true;
     else if (a == "--append" || a == "--append-weak" || a == "--replace") {
       Job j;
@@ -307,7 +344,7 @@ int main(int argc, char** argv) {
       }
       jobs.push_back(j);
     } else if ((cmd == "hash" || cmd == "check" || cmd == "links" || cmd == "blocks" ||
-                cmd == "sources" || cmd == "repeats" || cmd == "candidates") &&
+                cmd == "sources" || cmd == "repeats" || cmd == "candidates" || cmd == "copies") &&
                a.size() &&
                a[0] != '-') {
       files.push_back(a);
@@ -338,7 +375,7 @@ int main(int argc, char** argv) {
       if (!read_file(files[i].substr(eq + 1), &link_indexes.back())) return 2;
     }
   }
-  if (cmd == "sources" || cmd == "candidates") {
+  if (cmd == "sources" || cmd == "candidates" || cmd == "copies") {
     // the indexes are read (and a missing one reported) before any device is opened
     if (files.size() < 2) {
       usage();
@@ -354,11 +391,11 @@ int main(int argc, char** argv) {
     return 2;
   }
   std::vector<std::string> inputs = cmd == "links" ? link_dirs : files;
-  if (cmd == "sources" || cmd == "repeats" || cmd == "candidates")
+  if (cmd == "sources" || cmd == "repeats" || cmd == "candidates" || cmd == "copies")
     inputs.clear();  // (indexes only: nothing is staged)
   std::vector<uint8_t> check_index;
   // (read, and a missing one reported, before any device is opened)
-  if ((cmd == "sources" || cmd == "repeats" || cmd == "candidates") &&
+  if ((cmd == "sources" || cmd == "repeats" || cmd == "candidates" || cmd == "copies") &&
       !read_file(files[0], &check_index))
     return 2;
   if (cmd == "links" && !read_file(files[0], &check_index)) return 2;
@@ -530,24 +567,73 @@ int main(int argc, char** argv) {
     std::vector<int> dirfds(link_dirs.size(), AT_FDCWD);
     std::vector<const char*> dirs;
     for (const std::string& d : link_dirs) dirs.push_back(d.c_str());
-    std::vector<uint8_t> kinds(nl);
-    uint64_t st[CIR_LINKS_STATS_FIELDS];
-    rc = cir_check_links(ctx, index, check_index.size(), dirfds.data(), dirs.data(), dirs.size(),
-                         lf, ls, nl, threads, kinds.data(), nullptr, st);
-    if (rc) {
-      die(rc, files[0].c_str());
-      return 2;
-    }
     const std::vector<std::string> paths = index_file_paths(check_index);
-    for (size_t i = 0; i < nl; ++i)
-      if (kinds[i] == CIR_CHECK_OK && lf[i] < paths.size())
-        printf("%s\t%s\n", link_dirs[ls[i]].c_str(), paths[lf[i]].c_str());
-    fflush(stdout);
-    fprintf(stderr,
-            "links: %zu candidates: %llu ok, %llu checksum, %llu read; %zu source index(es) "
-            "skipped\n",
-            nl, (unsigned long long)st[0], (unsigned long long)st[1], (unsigned long long)st[2],
-            skipped);
+    uint64_t st[CIR_LINKS_STATS_FIELDS];
+    if (any_path) {
+      // the files without a same-path candidate, matched by content; all verified in one call
+      std::vector<uint64_t> skip(paths.size() / 64 + 1, 0);
+      for (size_t i = 0; i < nl; ++i)
+        if (lf[i] < paths.size()) skip[lf[i] >> 6] |= 1ull << (lf[i] & 63);
+      uint64_t* cf = nullptr;
+      uint32_t* cs = nullptr;
+      uint64_t* csf = nullptr;
+      uint64_t* off = nullptr;
+      uint8_t* sp = nullptr;
+      size_t nc = 0;
+      uint64_t cst[CIR_FILE_COPIES_STATS_FIELDS];
+      rc = cir_file_copies(host_candidates ? nullptr : ctx, index, check_index.size(), sidx.data(),
+                           slen.data(), sidx.size(), skip.data(), &cf, &cs, &csf, &off, &sp, &nc,
+                           nullptr, cst);
+      if (rc) {
+        die(rc, files[0].c_str());
+        return 2;
+      }
+      std::vector<uint64_t> all_f(lf, lf + nl), all_off(nl + 1, 0);  // (an empty path: the entry's own)
+      std::vector<uint32_t> all_s(ls, ls + nl);
+      all_f.insert(all_f.end(), cf, cf + nc);
+      all_s.insert(all_s.end(), cs, cs + nc);
+      for (size_t i = 0; i < nc; ++i) all_off.push_back(off[i + 1]);
+      std::vector<uint8_t> kinds(nl + nc);
+      rc = cir_check_links_at(ctx, index, check_index.size(), dirfds.data(), dirs.data(),
+                              dirs.size(), all_f.data(), all_s.data(), all_off.data(), sp, nl + nc,
+                              threads, kinds.data(), nullptr, st);
+      if (rc) {
+        die(rc, files[0].c_str());
+        return 2;
+      }
+      for (size_t i = 0; i < nl + nc; ++i) {
+        if (kinds[i] != CIR_CHECK_OK || all_f[i] >= paths.size()) continue;
+        if (i < nl)
+          printf("%s\t%s\n", link_dirs[all_s[i]].c_str(), paths[all_f[i]].c_str());
+        else
+          printf("%s\t%s\t%s\n", link_dirs[all_s[i]].c_str(), paths[all_f[i]].c_str(),
+                 escape_path(sp + off[i - nl], off[i - nl + 1] - off[i - nl]).c_str());
+      }
+      fflush(stdout);
+      fprintf(stderr,
+              "links: %zu candidates (%zu at their own path, %zu by content): %llu ok, %llu "
+              "checksum, %llu read; %zu source index(es) skipped\n",
+              nl + nc, nl, nc, (unsigned long long)st[0], (unsigned long long)st[1],
+              (unsigned long long)st[2], skipped);
+      for (void* p : {(void*)cf, (void*)cs, (void*)csf, (void*)off, (void*)sp}) cir_free(p);
+    } else {
+      std::vector<uint8_t> kinds(nl);
+      rc = cir_check_links(ctx, index, check_index.size(), dirfds.data(), dirs.data(), dirs.size(),
+                           lf, ls, nl, threads, kinds.data(), nullptr, st);
+      if (rc) {
+        die(rc, files[0].c_str());
+        return 2;
+      }
+      for (size_t i = 0; i < nl; ++i)
+        if (kinds[i] == CIR_CHECK_OK && lf[i] < paths.size())
+          printf("%s\t%s\n", link_dirs[ls[i]].c_str(), paths[lf[i]].c_str());
+      fflush(stdout);
+      fprintf(stderr,
+              "links: %zu candidates: %llu ok, %llu checksum, %llu read; %zu source index(es) "
+              "skipped\n",
+              nl, (unsigned long long)st[0], (unsigned long long)st[1], (unsigned long long)st[2],
+              skipped);
+    }
     cir_free(lf);
     cir_free(ls);
   } else if (cmd == "candidates") {
@@ -580,6 +666,60 @@ int main(int argc, char** argv) {
             skipped, fst[6] ? "device" : "host");
     cir_free(lf);
     cir_free(ls);
+  } else if (cmd == "copies") {
+    static const uint8_t none = 0;
+    const uint8_t* index = check_index.empty() ? &none : check_index.data();
+    std::vector<const uint8_t*> sidx;
+    std::vector<size_t> slen;
+    for (const std::vector<uint8_t>& v : link_indexes) {
+      sidx.push_back(v.empty() ? &none : v.data());
+      slen.push_back(v.size());
+    }
+    const std::vector<std::string> paths = index_file_paths(check_index);
+    std::vector<uint64_t> skip;
+    if (unlinked) {  // the files the same-path rule links are left out
+      uint64_t* lf = nullptr;
+      uint32_t* ls = nullptr;
+      size_t nl = 0;
+      uint64_t fst[CIR_FILE_SOURCES_STATS_FIELDS];
+      rc = cir_file_sources(ctx, index, check_index.size(), sidx.data(), slen.data(), sidx.size(),
+                            &lf, &ls, &nl, nullptr, fst);
+      if (rc) {
+        die(rc, files[0].c_str());
+        return 2;
+      }
+      skip.assign(paths.size() / 64 + 1, 0);
+      for (size_t i = 0; i < nl; ++i)
+        if (lf[i] < paths.size()) skip[lf[i] >> 6] |= 1ull << (lf[i] & 63);
+      cir_free(lf);
+      cir_free(ls);
+    }
+    uint64_t* cf = nullptr;
+    uint32_t* cs = nullptr;
+    uint64_t* csf = nullptr;
+    uint64_t* off = nullptr;
+    uint8_t* sp = nullptr;
+    size_t nc = 0, skipped = 0;
+    uint64_t cst[CIR_FILE_COPIES_STATS_FIELDS];
+    rc = cir_file_copies(ctx, index, check_index.size(), sidx.data(), slen.data(), sidx.size(),
+                         unlinked ? skip.data() : nullptr, &cf, &cs, &csf, &off, &sp, &nc, &skipped,
+                         cst);
+    if (rc) {
+      die(rc, files[0].c_str());
+      return 2;
+    }
+    for (size_t i = 0; i < nc; ++i)
+      if (cf[i] < paths.size())
+        printf("%llu %u %llu %s %s\n", (unsigned long long)cf[i], cs[i], (unsigned long long)csf[i],
+               paths[cf[i]].c_str(), escape_path(sp + off[i], off[i + 1] - off[i]).c_str());
+    fflush(stdout);
+    fprintf(stderr,
+            "copies: %llu files, %llu left out, %zu candidates (%llu at their own path), %llu bytes; "
+            "%llu source index(es) used, %zu skipped; matched on the %s\n",
+            (unsigned long long)cst[0], (unsigned long long)cst[8], nc, (unsigned long long)cst[9],
+            (unsigned long long)cst[2], (unsigned long long)cst[4], skipped,
+            cst[6] ? "device" : "host");
+    for (void* p : {(void*)cf, (void*)cs, (void*)csf, (void*)off, (void*)sp}) cir_free(p);
   } else if (cmd == "sources") {
     static const uint8_t none = 0;
     std::vector<const uint8_t*> sidx;

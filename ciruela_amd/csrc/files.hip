@@ -35,6 +35,16 @@
 //                  empty, atomicMin on equal, as join.hip;
 //   k_files_probe  one lane per need file: the sources in order;
 //   k_files_verify one lane per need block of a file with a candidate.
+//
+// cir_match_copies_dev (the device half of cir_file_copies; the rule and the
+// argument for it are copies.hpp): the same memset, k_files_fold for both
+// sides and k_files_verify, with a table keyed by content between them:
+//   k_copies_build one lane per non-empty pool file into a table of pool
+//                  ordinals + 1 keyed by {size, exe, fold}: CAS on empty,
+//                  atomicMin on an equal key;
+//   k_copies_probe one lane per need file that is neither empty nor skipped:
+//                  from the key's home slot to an equal key or an empty slot.
+#include "copies.hpp"
 #include "files.hpp"
 #include "idxwalk.hpp"
 #include "kernels.hpp"
@@ -524,6 +534,152 @@ hipError_t launch_match_files(const FilesSide& need, const FilesSide& pool,
   if (need.nfiles) {
     hipLaunchKernelGGL(k_files_probe, grid(need.nfiles), dim3(kThreads), 0, s, na, pa, src_first,
                        nsrc, table, slots, seed, need_fold, pool_fold, cand_src, cand_file, res);
+    if ((e = hipGetLastError()) != hipSuccess) return e;
+  }
+  if ((e = mark(3)) != hipSuccess) return e;
+  if (need.nblocks && need.nfiles && pool.nfiles && nsrc) {
+    hipLaunchKernelGGL(k_files_verify, grid(need.nblocks), dim3(kThreads), 0, s, na, pa,
+                       pool_verify ? pool_verify : pool.digests, src_first, nsrc, bs, cand_src,
+                       cand_file, res);
+    if ((e = hipGetLastError()) != hipSuccess) return e;
+  }
+  return mark(4);
+}
+
+// ---- the join by content (cir_match_copies_dev) ----------------------------------
+
+// Lane j puts pool file j into the table under its key {size, exe, fold}
+// (copies.hpp): k_files_build's walk with another equality.  The key of an
+// occupant is read through its record and fold (the folds are complete: the
+// fold kernels ran before on the stream).  Every occupant a slot ever has
+// carries the key of the lane that claimed it, since only a lane with an equal
+// key lowers it, so the slot ends holding the smallest ordinal with that key.
+// An empty file takes no part.  No lane waits for another; the loop is bounded
+// by the slot count.
+__global__ __launch_bounds__(kThreads) void k_copies_build(FilesSide pool,
+                                                           const uint64_t* __restrict__ pool_fold,
+                                                           uint32_t* __restrict__ table,
+                                                           uint64_t slots, uint64_t seed) {
+  const uint64_t j = (uint64_t)blockIdx.x * kThreads + threadIdx.x;
+  if (j >= pool.nfiles) return;
+  const uint64_t* r = pool.recs + files::kFileWords * j;
+  const uint64_t size = r[2], first = r[3];
+  if (size == 0) return;
+  const uint64_t f0 = pool_fold[files::kFoldWords * j], f1 = pool_fold[files::kFoldWords * j + 1];
+  const uint64_t mask = slots - 1;
+  uint64_t at = copies::home_slot(size, first & files::kExeBit, f0, f1, seed, mask);
+  const uint32_t mine = (uint32_t)j + 1;
+  for (uint64_t step = 0; step < slots; ++step) {
+    uint32_t v = __hip_atomic_load(table + at, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (v == 0) {
+      v = atomicCAS(table + at, 0u, mine);
+      if (v == 0) return;
+    }
+    if (v <= pool.nfiles) {
+      const uint64_t pv = v - 1;
+      const uint64_t* o = pool.recs + files::kFileWords * pv;
+      if (copies::same_key(o[2], o[3], pool_fold[files::kFoldWords * pv],
+                           pool_fold[files::kFoldWords * pv + 1], size, first, f0, f1)) {
+        if (v > mine) atomicMin(table + at, mine);  // (the value only ever falls)
+        return;
+      }
+    }
+    at = (at + 1) & mask;
+  }
+}
+
+// Lane i looks need file i up by its key, unless it is empty or the caller's
+// bitmap leaves it out: from the key's home slot to an equal key or an empty
+// slot.  The hit is the smallest pool ordinal with that key; its source,
+// its ordinal inside the source and the two text offsets of its record are
+// the outputs.
+__global__ __launch_bounds__(kThreads) void k_copies_probe(
+    FilesSide need, FilesSide pool, const uint64_t* __restrict__ src_first, uint64_t nsrc,
+    const uint64_t* __restrict__ skip, const uint32_t* __restrict__ table, uint64_t slots,
+    uint64_t seed, const uint64_t* __restrict__ need_fold, const uint64_t* __restrict__ pool_fold,
+    uint32_t* __restrict__ cand_src, uint64_t* __restrict__ cand_file,
+    uint64_t* __restrict__ cand_place, uint64_t* __restrict__ res) {
+  const uint64_t i = (uint64_t)blockIdx.x * kThreads + threadIdx.x;
+  uint64_t bytes = 0;
+  bool hit = false;
+  if (i < need.nfiles) {
+    const uint64_t* r = need.recs + files::kFileWords * i;
+    const uint64_t size = r[2], first = r[3];
+    uint32_t cs = files::kNoSrc;
+    uint64_t cf = files::kNoFile, name = copies::kNoPlace, dir = copies::kNoPlace;
+    if (size != 0 && nsrc != 0 && !copies::skipped(skip, i)) {
+      const uint64_t f0 = need_fold[files::kFoldWords * i], f1 = need_fold[files::kFoldWords * i + 1];
+      const uint64_t mask = slots - 1;
+      uint64_t at = copies::home_slot(size, first & files::kExeBit, f0, f1, seed, mask);
+      for (uint64_t step = 0; step < slots; ++step) {
+        const uint32_t v = table[at];
+        if (v == 0 || v > pool.nfiles) break;  // empty (or not an ordinal: never after the build)
+        const uint64_t pv = v - 1;
+        const uint64_t* o = pool.recs + files::kFileWords * pv;
+        if (copies::same_key(o[2], o[3], pool_fold[files::kFoldWords * pv],
+                             pool_fold[files::kFoldWords * pv + 1], size, first, f0, f1)) {
+          const uint64_t s = files::src_of(src_first, nsrc, pv);
+          hit = true;
+          cs = (uint32_t)s;
+          cf = pv - src_first[s];
+          name = o[0];
+          dir = o[1];
+          bytes = size;
+          break;
+        }
+        at = (at + 1) & mask;
+      }
+    }
+    cand_src[i] = cs;
+    cand_file[i] = cf;
+    cand_place[copies::kPlaceWords * i] = name;
+    cand_place[copies::kPlaceWords * i + 1] = dir;
+  }
+  // one add per wave and word
+  const uint64_t votes = __ballot(hit);
+#pragma unroll
+  for (int d = 32; d >= 1; d >>= 1) bytes += __shfl_down((unsigned long long)bytes, d, 64);
+  if (votes && (threadIdx.x & 63) == 0) {
+    atomicAdd(reinterpret_cast<unsigned long long*>(res + 1), (unsigned long long)__popcll(votes));
+    atomicAdd(reinterpret_cast<unsigned long long*>(res + 2), (unsigned long long)bytes);
+  }
+}
+
+hipError_t launch_match_copies(const FilesSide& need, const FilesSide& pool,
+                               const uint64_t* src_first, uint64_t nsrc, uint64_t bs,
+                               const uint64_t* skip, const uint8_t* pool_verify, uint64_t seed,
+                               uint64_t* work, uint32_t* cand_src, uint64_t* cand_file,
+                               uint64_t* cand_place, uint64_t* res, hipStream_t s,
+                               const hipEvent_t* tev) {
+  const uint64_t slots = join_table_slots(pool.nfiles);
+  uint64_t* need_fold = work;
+  uint64_t* pool_fold = work + files::kFoldWords * need.nfiles;
+  uint32_t* table = reinterpret_cast<uint32_t*>(pool_fold + files::kFoldWords * pool.nfiles);
+  const FilesSide &na = need, &pa = pool;
+  auto grid = [](uint64_t n) { return dim3((unsigned)((n + kThreads - 1) / kThreads)); };
+  auto mark = [&](int k) { return tev ? hipEventRecord(tev[k], s) : hipSuccess; };
+  hipError_t e = hipMemsetAsync(work, 0, match_files_work_bytes(need.nfiles, pool.nfiles), s);
+  if (e != hipSuccess || (e = mark(0)) != hipSuccess) return e;
+  // (the need side's fold always runs: it initialises res)
+  hipLaunchKernelGGL(k_files_fold, grid(need.nblocks ? need.nblocks : 1), dim3(kThreads), 0, s, na,
+                     bs, seed, need_fold, res, need.nfiles);
+  if ((e = hipGetLastError()) != hipSuccess) return e;
+  if (pool.nblocks && pool.nfiles) {
+    hipLaunchKernelGGL(k_files_fold, grid(pool.nblocks), dim3(kThreads), 0, s, pa, bs, seed,
+                       pool_fold, (uint64_t*)nullptr, 0ull);
+    if ((e = hipGetLastError()) != hipSuccess) return e;
+  }
+  if ((e = mark(1)) != hipSuccess) return e;
+  if (pool.nfiles && nsrc) {
+    hipLaunchKernelGGL(k_copies_build, grid(pool.nfiles), dim3(kThreads), 0, s, pa, pool_fold, table,
+                       slots, seed);
+    if ((e = hipGetLastError()) != hipSuccess) return e;
+  }
+  if ((e = mark(2)) != hipSuccess) return e;
+  if (need.nfiles) {
+    hipLaunchKernelGGL(k_copies_probe, grid(need.nfiles), dim3(kThreads), 0, s, na, pa, src_first,
+                       nsrc, skip, table, slots, seed, need_fold, pool_fold, cand_src, cand_file,
+                       cand_place, res);
     if ((e = hipGetLastError()) != hipSuccess) return e;
   }
   if ((e = mark(3)) != hipSuccess) return e;

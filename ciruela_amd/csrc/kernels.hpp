@@ -333,6 +333,21 @@ hipError_t launch_match_files(const FilesSide& need, const FilesSide& pool,
                               uint32_t* cand_src, uint64_t* cand_file, uint64_t* res, hipStream_t s,
                               const hipEvent_t* tev = nullptr);
 
+// Join of two file lists by content (files.hip; cir_match_copies_dev; the rule
+// is copies.hpp): per need file that is neither empty nor skipped (skip:
+// nullable bitmap of u64 words over need file ordinals) the pool file of the
+// smallest ordinal with the same exe flag, size and digests, at any path:
+// cand_src / cand_file as launch_match_files writes them and cand_place[2 i
+// ..] = that pool record's {name_off, dir_off} (UINT64_MAX: none).  The
+// sides' texts are not read.  work, res, pool_verify, tev and what is
+// unchecked: as launch_match_files.
+hipError_t launch_match_copies(const FilesSide& need, const FilesSide& pool,
+                               const uint64_t* src_first, uint64_t nsrc, uint64_t bs,
+                               const uint64_t* skip, const uint8_t* pool_verify, uint64_t seed,
+                               uint64_t* work, uint32_t* cand_src, uint64_t* cand_file,
+                               uint64_t* cand_place, uint64_t* res, hipStream_t s,
+                               const hipEvent_t* tev = nullptr);
+
 // nlanes x `lines` register-only compressions (diagnostic VALU ceiling).
 hipError_t launch_compress_only(uint64_t nlanes, uint32_t lines, uint8_t* out, hipStream_t s);
 

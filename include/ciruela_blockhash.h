@@ -51,8 +51,8 @@
  *                              cir_block_sources on the device from 16,384
  *                              needed blocks on;
  *       CIR_LINKS_MATCH=host   cir_file_sources with a context answers with the host
- *                              rule of cir_link_candidates (A/B measurement; read
- *                              per call);
+ *                              rule of cir_link_candidates, and cir_file_copies with
+ *                              its own host rule (A/B measurement; read per call);
  *       CIR_DEBUG_SPLIT=k      (tests) every opened GPU appears k times.
  *       CIR_DEBUG_STRIPE_BLOCKS=n  (tests) a scan over several devices deals
  *                              stripes of n blocks (default: one staging
@@ -473,6 +473,33 @@ int cir_check_links(cir_ctx* ctx, const uint8_t* index, size_t len,
                     const uint64_t* link_file, const uint32_t* link_src, size_t nlinks,
                     uint32_t threads, uint8_t* kind_out, int32_t* errno_out,
                     uint64_t stats[CIR_LINKS_STATS_FIELDS]);
+
+/* cir_check_links with a place per candidate: candidate i is still file entry link_file[i] of
+ * `index` -- the size, the exe mode bits and the digests expected are that entry's -- but it is
+ * looked for under source root link_src[i] at the path link_paths[link_path_off[i] ..
+ * link_path_off[i + 1]) (raw bytes, nlinks + 1 offsets, no terminators): exactly what
+ * cir_file_copies returns in paths_out / path_off_out, so a file an older image holds unchanged
+ * below a renamed directory is verified where it actually lies.  An empty path means the entry's
+ * own path; link_path_off == NULL makes the call cir_check_links.  The pipeline, the verdicts,
+ * the stats, the bound on file descriptors and the striping over devices are cir_check_links';
+ * the work order is by root, then by directory, then by index order, so neighbours still share a
+ * directory fd.
+ *
+ * The paths come from another party's index and are validated before any I/O: a path is split at
+ * '/', a leading '/' is allowed and empty components are dropped; a "." or ".." component, or a
+ * non-empty path without any component, makes the whole call CIR_EINVAL with no file opened; a
+ * component that holds a NUL byte makes CIR_CHECK_READ with EINVAL of that candidate alone.  Every
+ * component is opened with O_DIRECTORY | O_NOFOLLOW below the root fd and the file with
+ * O_NOFOLLOW, as in cir_check_links: a symlink in any component's place is READ.
+ *
+ * CIR_EINVAL additionally: link_path_off that decreases, a null link_paths with a non-empty
+ * path. */
+int cir_check_links_at(cir_ctx* ctx, const uint8_t* index, size_t len,
+                       const int* src_dirfd, const char* const* src_dir, size_t nsrc,
+                       const uint64_t* link_file, const uint32_t* link_src,
+                       const uint64_t* link_path_off, const uint8_t* link_paths, size_t nlinks,
+                       uint32_t threads, uint8_t* kind_out, int32_t* errno_out,
+                       uint64_t stats[CIR_LINKS_STATS_FIELDS]);
 
 /* Which blocks of an index a partial image directory already holds, for resume and repair.
  * The reference resumes by starting over: "Resuming download" (src/daemon/tracking/mod.rs:
@@ -1053,6 +1080,96 @@ int cir_file_sources(cir_ctx* ctx, const uint8_t* index, size_t len,
                      const uint8_t* const* src_index, const size_t* src_len, size_t nsrc,
                      uint64_t** file_out, uint32_t** src_out, size_t* n_out,
                      size_t* nskipped_out, uint64_t stats[CIR_FILE_SOURCES_STATS_FIELDS]);
+
+/* Bytes of device scratch cir_match_copies_dev needs: 16 per file of either side and 4 per table
+ * slot (cir_match_table_slots(n_pool_files)).  Pure; 0 when a count passes the call's limits. */
+uint64_t cir_match_copies_work_bytes(uint64_t n_need_files, uint64_t n_pool_files);
+
+/* The join behind cir_file_copies, device-resident: hardlink candidates matched by content, at
+ * any path.  The record arrays (CIR_FILE_WORDS u64 each), the flat digest lists, d_src_first
+ * (device u64 x (nsrc + 1)) and block_size are cir_match_files_dev's; no text arena is read, paths
+ * play no part.  Pool files are ordered by source in the order given, then in index order.
+ *
+ * The rule (ciruela_amd/csrc/copies.hpp): need file i has a candidate only if its size is greater
+ * than 0 and its bit in d_skip (device u64 x ceil(n_need_files / 64), bit i & 63 of word i / 64;
+ * NULL: nothing is skipped) is 0; empty files take part on neither side.  The candidate is the
+ * pool file with the smallest pool ordinal that has equal exe flag, equal size and an equal digest
+ * list: the first source that holds such a file and, inside it, its first place.  One candidate at
+ * most per need file; several need files may name one pool file.  d_cand_src[i] (device u32;
+ * UINT32_MAX: none), d_cand_file[i] (device u64, the file ordinal inside that source; UINT64_MAX:
+ * none) and d_cand_place[2 i .. 2 i + 2) (device u64: the name_off and dir_off of the candidate's
+ * pool record, so that its path can be decoded without the pool records; UINT64_MAX: none) are
+ * written for every need file.  d_res (device, CIR_FILES_RES_FIELDS u64): [0] CIR_FILES_OK or
+ * CIR_FILES_COLLISION, [1] candidates, [2] the sum of their sizes, [3] need files.
+ *
+ * All on `stream` behind one memset of d_work: cir_match_files_dev's fold of both sides, build
+ * (one lane per non-empty pool file into a table of pool ordinals keyed by {size, exe, the 128-bit
+ * fold}: claimed by compare-and-swap when empty, lowered by an atomic minimum when the occupant's
+ * key is equal, so that every occupant a slot ever has carries one key and the slot ends holding
+ * the smallest ordinal with it), probe (one lane per need file, from the key's home slot to an
+ * equal key or an empty slot) and cir_match_files_dev's verify, digest by digest, against
+ * d_pool_verify (NULL: d_pool_digests; tests pass another array to reach the status).  Files of
+ * equal content have equal keys, so once every candidate has passed the verify each is the
+ * smallest ordinal among the files equal to its need file: with CIR_FILES_OK the answer is exactly
+ * the rule's, whatever the seed and the timing.  A collided fold can only make a slot's minimum a
+ * file that fails the verify: CIR_FILES_COLLISION, and the arrays mean nothing.  No lane waits for
+ * another and every loop is bounded by an argument.  Whatever the records hold, nothing outside the
+ * arrays as sized by the arguments is read or written.  Like every *_dev call it allocates
+ * nothing and synchronises nothing; ctx may be NULL and is not used.
+ *
+ * CIR_EINVAL, decided before any HIP call: a null array with a non-zero count, a null
+ * d_src_first, d_work or d_res; a digest array not 16-byte aligned; records, d_src_first, d_skip,
+ * d_work, d_cand_file, d_cand_place or d_res not 8-byte aligned; d_cand_src not 4-byte aligned;
+ * block_size == 0; more than 2^31 - 1 pool files, 2^32 - 1 need files or 2^32 - 1 blocks on a
+ * side; work_bytes < cir_match_copies_work_bytes(n_need_files, n_pool_files). */
+int cir_match_copies_dev(cir_ctx* ctx, const uint64_t* d_need_files, uint64_t n_need_files,
+                         const uint8_t* d_need_digests, uint64_t n_need_blocks,
+                         const uint64_t* d_pool_files, uint64_t n_pool_files,
+                         const uint8_t* d_pool_digests, uint64_t n_pool_blocks,
+                         const uint64_t* d_src_first, uint64_t nsrc, uint64_t block_size,
+                         const uint64_t* d_skip, const uint8_t* d_pool_verify, uint64_t seed,
+                         void* d_work, uint64_t work_bytes, uint32_t* d_cand_src,
+                         uint64_t* d_cand_file, uint64_t* d_cand_place, uint64_t* d_res,
+                         void* stream);
+
+/* Hardlink candidates matched by content: for every file entry of `index` that is not empty and
+ * whose bit in `skip` (u64 words over file ordinals; NULL: nothing is skipped) is 0, the first
+ * source, in the order given, that holds a file with equal exe flag, size and digests at any
+ * path, and inside that source the first such file in index order (cir_match_copies_dev's rule).
+ * cir_file_sources finds a file only at its own path: below a renamed directory (/app-1.2.3
+ * becomes /app-1.2.4) or for a moved file it finds nothing, and the bytes are copied
+ * (cir_block_extents) where a link would do.  Run after it with skip = the files it linked, this
+ * call is a pure addition.  The reference has no counterpart
+ * (src/daemon/metadata/hardlink_sources.rs:121-146 matches by path).
+ *
+ * Candidate k: file_out[k] (file ordinal in `index`, strictly increasing), src_out[k] (source
+ * ordinal as the caller counts), src_file_out[k] (file ordinal inside that source) and its path in
+ * the source, decoded, in the form the index parser gives an entry's path ("/dir/name", raw
+ * bytes): paths_out[path_off_out[k] .. path_off_out[k + 1]); n + 1 offsets, no terminators.  All
+ * five arrays are malloc'd (cir_free) and NULL when *n_out == 0.  Sources are skipped and counted
+ * in *nskipped_out (nullable) exactly as in cir_file_sources.
+ *
+ * With ctx == NULL the host rule runs and no GPU is needed.  With a context the flow is
+ * cir_file_sources': texts framed on the host and uploaded once, the count pass (first
+ * synchronise), the emit and decode passes with cir_index_files_dev's kernels and biases, the skip
+ * bitmap, cir_match_copies_dev's kernels, and d_cand_src, d_cand_file, d_cand_place and the need
+ * records down with the verdicts (second synchronise); the host compacts them and decodes every
+ * candidate's path from the source text it holds.  The whole call is answered by the host rule
+ * instead, which is never an error, in the cases named at cir_file_sources (a declined text, a
+ * collision, a limit, CIR_LINKS_MATCH=host).  Both paths give identical output, stats [5] to [7]
+ * aside.
+ *
+ * stats: [0] file entries of `index`, [1] candidates, [2] their bytes, [3] pool files, [4] sources
+ * used, [5] table slots (0 on the host), [6] 1 if matched on the device, [7] why not: 0, or a
+ * CIR_FILE_WHY_*, [8] need files left out by `skip`, [9] candidates whose source path equals the
+ * entry's own path. */
+#define CIR_FILE_COPIES_STATS_FIELDS 10
+int cir_file_copies(cir_ctx* ctx, const uint8_t* index, size_t len,
+                    const uint8_t* const* src_index, const size_t* src_len, size_t nsrc,
+                    const uint64_t* skip, uint64_t** file_out, uint32_t** src_out,
+                    uint64_t** src_file_out, uint64_t** path_off_out, uint8_t** paths_out,
+                    size_t* n_out, size_t* nskipped_out,
+                    uint64_t stats[CIR_FILE_COPIES_STATS_FIELDS]);
 
 /* ---- index (DIRSIGNATURE.v1) ----------------------------------------- */
 
