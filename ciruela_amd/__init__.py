@@ -72,6 +72,13 @@ check_links_at,                 check_links with a place per candidate: the veri
   Context.check_links_at        file_copies candidate at the path where the source
                                 holds it (src/daemon/disk/public.rs:308-346 with
                                 another path)
+fetch_plan,                     the four answers above as one download plan: links at the
+  Context.plan_links_dev,       same path, links by content, extents from older images,
+  Context.plan_want_dev         extents inside the image and the bitmap left to fetch,
+                                with every text uploaded and parsed once; the reference
+                                plans nothing (src/daemon/metadata/
+                                hardlink_sources.rs:107-153, src/daemon/tracking/
+                                progress.rs:129-170)
 index_digests,                  what every consumer of an index starts with: its block
   Context.index_digests_dev     digests as one array and a run record per non-empty
                                 file, parsed on the device (the reference parses the
@@ -97,6 +104,7 @@ __all__ = [
     "block_extents", "ExtentsResult", "Extent",
     "block_repeats", "RepeatsResult",
     "index_digests", "IndexDigests", "file_sources", "file_copies", "check_links_at",
+    "fetch_plan", "PlanResult",
 ]
 
 DEFAULT_BLOCK_SIZE = 32768
@@ -434,6 +442,32 @@ class Context:
         _n.check(_n.lib.cir_match_copies_dev(self._h, *need, *pool, d_src_first, nsrc, block_size,
                                              d_skip, d_pool_verify, seed, d_work, work_bytes,
                                              d_cand_src, d_cand_file, d_cand_place, d_res, stream))
+
+    def plan_links_dev(self, d_cand_src, d_cand_file, n_files, d_skip, d_res, d_deny=0,
+                       stream=0):
+        """The glue between match_files_dev and match_copies_dev
+        (cir_plan_links_dev): the candidates of the files whose bit in d_deny
+        (u64 words over file ordinals; 0: none) is set are withdrawn
+        (d_cand_src[i] = 2^32-1, d_cand_file[i] = 2^64-1), and d_skip
+        (ceil(n_files / 64) u64, every word written) = deny | candidate kept,
+        match_copies_dev's d_skip.  d_res: 2 u64 {kept, withdrawn}.  All
+        written by the call, on `stream` alone."""
+        _n.check(_n.lib.cir_plan_links_dev(self._h, d_deny, n_files, d_cand_src, d_cand_file,
+                                           d_skip, d_res, stream))
+
+    def plan_want_dev(self, d_need_runs, n_need_runs, n_blocks, block_size, n_files, d_want,
+                      d_res, d_cand_a=0, d_cand_b=0, d_have=0, stream=0):
+        """The glue between match_copies_dev and match_extents_dev
+        (cir_plan_want_dev): d_want (ceil(n_blocks / 64) u64, every word
+        written) = the blocks of the file entries of the run table d_need_runs
+        (4 u64 per non-empty file, `first` ascending) whose file has a candidate
+        in neither d_cand_a nor d_cand_b (u32 x n_files; 0: no array) and whose
+        bit in d_have (0: none) is clear.  d_res: 3 u64 {wanted, blocks of
+        linked files, left out by have}.  All written by the call, on `stream`
+        alone."""
+        _n.check(_n.lib.cir_plan_want_dev(self._h, d_need_runs, n_need_runs, n_blocks, block_size,
+                                          n_files, d_cand_a, d_cand_b, d_have, d_want, d_res,
+                                          stream))
 
     # ---- asynchronous per-block verify (FetchBlock::poll, fetch_blocks.rs:77)
     def verify_submit(self, data, expected, hash_type=None):
@@ -1547,6 +1581,126 @@ def file_copies(index, sources, context=None, skip=None):
     st = dict(zip(FILE_COPIES_STATS, list(stats)))
     st["skipped"] = skipped.value
     return found, st
+
+
+class PlanResult:
+    """Answer of fetch_plan.  links: [(file ordinal, source ordinal)], the
+    hardlinks at the same path (file_sources' pairs, minus `deny`); copies:
+    [(file ordinal, source ordinal, file ordinal inside the source, source path
+    bytes)], the hardlinks by content (file_copies' tuples); extents: Extent
+    tuples, the local copies from older images (block_extents'); repeats:
+    Extent tuples inside the image (block_repeats': src 0 = present, 1 =
+    fetched); fetch: the bitmap of the blocks left to fetch (bytes, laid out as
+    BlocksResult.have); nblk: the index's blocks; skipped: sources that took no
+    part; stats: the four calls' stats under their own names ("sources",
+    "copies", "extents", "repeats") and the plan's own."""
+
+    __slots__ = ("links", "copies", "extents", "repeats", "fetch", "nblk", "stats", "skipped")
+    OWN_STATS = ("withdrawn", "linked", "linked_blocks", "have_blocks", "on_device", "why_host")
+
+    def __init__(self, links, copies, extents, repeats, fetch, nblk, stats, skipped):
+        self.links = links
+        self.copies = copies
+        self.extents = extents
+        self.repeats = repeats
+        self.fetch = fetch
+        self.nblk = nblk
+        self.stats = stats
+        self.skipped = skipped
+
+    def left_to_fetch(self):
+        return sum(bin(b).count("1") for b in self.fetch)
+
+    def __repr__(self):
+        return "PlanResult(%d links, %d copies, %d extents, %d repeats, %d of %d blocks to fetch)" % (
+            len(self.links), len(self.copies), len(self.extents), len(self.repeats),
+            self.left_to_fetch(), self.nblk)
+
+
+def _ordinal_bitmap(ordinals, nwords, what):
+    words = [0] * nwords
+    for i in ordinals:
+        if i < 0 or i >= 64 * nwords:
+            raise ValueError("no %s %d in this index" % (what, i))
+        words[i >> 6] |= 1 << (i & 63)
+    return (ctypes.c_uint64 * nwords)(*words)
+
+
+def fetch_plan(index, sources, context=None, deny=None, have=None):
+    """The whole download plan of a new image in one call (cir_fetch_plan):
+    file_sources' links minus `deny` (an iterable of file ordinals for which no
+    whole-file link may be proposed, or None), file_copies for the files still
+    unlinked, block_extents for the blocks of the files linked by neither,
+    minus `have` (the bitmap of the blocks already present and correct, bytes
+    laid out as BlocksResult.have, or None), and block_repeats over what is
+    still to fetch.  With a context every text is uploaded and parsed once and
+    the four joins run back to back on its first GPU; whatever the device
+    cannot answer exactly is answered by the same composition on the host
+    (stats["why_host"]).  Without a context the host composition runs (no
+    default context is opened).  Returns a PlanResult; no file is read and
+    nothing is linked or copied."""
+    if len(index):
+        ptr, keep = _buf(index)
+    else:  # (an empty index is a parse error, not a null argument)
+        keep = ctypes.create_string_buffer(1)
+        ptr = ctypes.cast(keep, ctypes.c_void_p)
+    sources = [bytes(s) for s in sources]
+    nsrc = len(sources)
+    bufs = [ctypes.create_string_buffer(s, max(len(s), 1)) for s in sources]
+    sp = (ctypes.c_void_p * max(nsrc, 1))(*[ctypes.cast(b, ctypes.c_void_p) for b in bufs])
+    sl = (ctypes.c_size_t * max(nsrc, 1))(*[len(s) for s in sources])
+    # (sized for every ordinal the index can hold: its shortest file line is 8
+    # bytes, a block's token 65)
+    dbuf = None if deny is None else _ordinal_bitmap(deny, len(index) // 512 + 1, "file entry")
+    hbuf = _bitmap_words(have, len(index) // (64 * 65) + 1)
+    outs = [ctypes.c_void_p() for _ in range(10)]
+    nl, nc, ne, nr, nskip = (ctypes.c_size_t() for _ in range(5))
+    nblk = ctypes.c_uint64()
+    stats = (ctypes.c_uint64 * _n.CIR_PLAN_STATS_FIELDS)()
+    ref = ctypes.byref
+    _n.check(_n.lib.cir_fetch_plan(context.handle if context is not None else None, ptr,
+                                   len(index), sp, sl, nsrc, dbuf, hbuf,
+                                   ref(outs[0]), ref(outs[1]), ref(nl),
+                                   ref(outs[2]), ref(outs[3]), ref(outs[4]), ref(outs[5]),
+                                   ref(outs[6]), ref(nc), ref(outs[7]), ref(ne), ref(outs[8]),
+                                   ref(nr), ref(outs[9]), ref(nblk), ref(nskip), stats))
+    del keep
+    try:
+        k = nl.value
+        links = []
+        if k:
+            links = list(zip((ctypes.c_uint64 * k).from_address(outs[0].value),
+                             (ctypes.c_uint32 * k).from_address(outs[1].value)))
+        k = nc.value
+        copies = []
+        if k:
+            files = list((ctypes.c_uint64 * k).from_address(outs[2].value))
+            srcs = list((ctypes.c_uint32 * k).from_address(outs[3].value))
+            sfiles = list((ctypes.c_uint64 * k).from_address(outs[4].value))
+            offs = list((ctypes.c_uint64 * (k + 1)).from_address(outs[5].value))
+            paths = ctypes.string_at(outs[6].value, offs[k])
+            copies = [(files[i], srcs[i], sfiles[i], paths[offs[i]:offs[i + 1]])
+                      for i in range(k)]
+        both = []
+        for o, cnt in ((outs[7], ne.value), (outs[8], nr.value)):
+            words = (ctypes.c_uint64 * (_n.CIR_EXTENT_WORDS * cnt)).from_address(o.value) \
+                if cnt else []
+            both.append([Extent(*words[8 * i:8 * i + 8]) for i in range(cnt)])
+        nwords = (nblk.value + 63) // 64
+        fetch = ctypes.string_at(outs[9].value, 8 * nwords) if nwords and outs[9].value else b""
+    finally:
+        for o in outs:
+            if o.value:
+                _n.lib.cir_free(o)
+    raw = list(stats)
+    st = {
+        "sources": dict(zip(FILE_SOURCES_STATS, raw[0:8])),
+        "copies": dict(zip(FILE_COPIES_STATS, raw[8:18])),
+        "extents": dict(zip(ExtentsResult.STATS_FIELDS, raw[18:28])),
+        "repeats": dict(zip(RepeatsResult.STATS_FIELDS, raw[28:38])),
+    }
+    st.update(zip(PlanResult.OWN_STATS, raw[38:44]))
+    return PlanResult(links, copies, both[0], both[1], fetch, nblk.value, st, nskip.value)
 
 
 def link_candidates(index, sources):

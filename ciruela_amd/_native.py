@@ -71,6 +71,10 @@ CIR_FILE_WHY_COLLISION = 2
 CIR_FILE_WHY_LIMIT = 3
 CIR_FILE_WHY_ENV = 4
 CIR_FILE_COPIES_STATS_FIELDS = 10
+CIR_PLAN_LINKS_RES_FIELDS = 2
+CIR_PLAN_WANT_RES_FIELDS = 3
+CIR_PLAN_STATS_FIELDS = 44
+CIR_PLAN_WHY_EMPTY = 5
 CIR_INDEX_STATS_FIELDS = 4
 CIR_INDEX_OK = 0
 CIR_INDEX_CAPACITY = 1
@@ -246,6 +250,19 @@ _SIGS = {
                                        ctypes.POINTER(c_vp), ctypes.POINTER(c_vp),
                                        ctypes.POINTER(c_vp), ctypes.POINTER(c_vp), c_sizep,
                                        c_sizep, c_u64p]),
+    "cir_plan_links_dev": (ctypes.c_int, [c_vp, c_vp, ctypes.c_uint64, c_vp, c_vp, c_vp, c_vp,
+                                          c_vp]),
+    "cir_plan_want_dev": (ctypes.c_int, [c_vp, c_vp, ctypes.c_uint64, ctypes.c_uint64,
+                                         ctypes.c_uint64, ctypes.c_uint64, c_vp, c_vp, c_vp, c_vp,
+                                         c_vp, c_vp]),
+    "cir_fetch_plan": (ctypes.c_int, [c_vp, c_vp, ctypes.c_size_t, ctypes.POINTER(c_vp), c_sizep,
+                                      ctypes.c_size_t, c_u64p, c_u64p,
+                                      ctypes.POINTER(c_vp), ctypes.POINTER(c_vp), c_sizep,
+                                      ctypes.POINTER(c_vp), ctypes.POINTER(c_vp),
+                                      ctypes.POINTER(c_vp), ctypes.POINTER(c_vp),
+                                      ctypes.POINTER(c_vp), c_sizep,
+                                      ctypes.POINTER(c_vp), c_sizep, ctypes.POINTER(c_vp), c_sizep,
+                                      ctypes.POINTER(c_vp), c_u64p, c_sizep, c_u64p]),
     "cir_debug_compress_only_dev": (ctypes.c_int, [ctypes.c_uint64, ctypes.c_uint32, c_vp, c_vp]),
     "cir_debug_relay_blocks": (ctypes.c_uint64, [ctypes.c_uint64, ctypes.c_uint64]),
     "cir_debug_device_identity": (ctypes.c_int, [ctypes.c_int, ctypes.c_char_p, ctypes.c_size_t,

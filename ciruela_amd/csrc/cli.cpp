@@ -51,6 +51,12 @@
 //       spells it and the path in the source, escaped.  --unlinked first runs
 //       the `candidates` rule and leaves out the files it found.  --host
 //       passes no context and opens no device.
+//   ciruela-index plan INDEX SRCINDEX [SRCINDEX ...] [--host]
+//       the whole download plan in one call (cir_fetch_plan; no file is
+//       read): the counts and bytes per class -- files to link at their own
+//       path, files to link by content, extents to copy from older images,
+//       extents to copy inside the image, blocks to fetch.  --host passes no
+//       context and opens no device.
 //   ciruela-index blocks DIR INDEX_FILE [--list] [--disk-threads N]
 //       which blocks of INDEX_FILE the partial image in DIR already holds
 //       (cir_check_blocks); --list prints `PATH OFFSET` per missing block
@@ -101,6 +107,7 @@ static void usage() {
           " [--disk-threads N] [--host] [--any-path]\n"
           "       ciruela-index candidates INDEX SRCINDEX [SRCINDEX ...] [--host]\n"
           "       ciruela-index copies INDEX SRCINDEX [SRCINDEX ...] [--host] [--unlinked]\n"
+          "       ciruela-index plan INDEX SRCINDEX [SRCINDEX ...] [--host]\n"
           "       ciruela-index blocks DIR INDEX_FILE [--list] [--disk-threads N]\n"
           "       ciruela-index sources INDEX SRCINDEX [SRCINDEX ...] [--list] [--host]"
           " [--extents]\n"
@@ -329,7 +336,8 @@ int main(int argc, char** argv) {
     else if (a == "--index-dir") index_dir = val();
     else if (a == "--list" && (cmd == "blocks" || cmd == "sources")) list_blocks = true;
     else if (a == "--host" &&
-             (cmd == "sources" || cmd == "repeats" || cmd == "candidates" || cmd == "copies"))
+             (cmd == "sources" || cmd == "repeats" || cmd == "candidates" || cmd == "copies" ||
+       cmd == "plan"))
       host_only = true;
     else if (a == "--unlinked" && cmd == "copies") unlinked = true;
     else if (a == "--host" && cmd == "links") host_candidates = true;
@@ -344,7 +352,8 @@ int main(int argc, char** argv) {
       }
       jobs.push_back(j);
     } else if ((cmd == "hash" || cmd == "check" || cmd == "links" || cmd == "blocks" ||
-                cmd == "sources" || cmd == "repeats" || cmd == "candidates" || cmd == "copies") &&
+                cmd == "sources" || cmd == "repeats" || cmd == "candidates" || cmd == "copies" ||
+       cmd == "plan") &&
                a.size() &&
                a[0] != '-') {
       files.push_back(a);
@@ -375,7 +384,8 @@ int main(int argc, char** argv) {
       if (!read_file(files[i].substr(eq + 1), &link_indexes.back())) return 2;
     }
   }
-  if (cmd == "sources" || cmd == "candidates" || cmd == "copies") {
+  if (cmd == "sources" || cmd == "candidates" || cmd == "copies" ||
+       cmd == "plan") {
     // the indexes are read (and a missing one reported) before any device is opened
     if (files.size() < 2) {
       usage();
@@ -391,11 +401,13 @@ int main(int argc, char** argv) {
     return 2;
   }
   std::vector<std::string> inputs = cmd == "links" ? link_dirs : files;
-  if (cmd == "sources" || cmd == "repeats" || cmd == "candidates" || cmd == "copies")
+  if (cmd == "sources" || cmd == "repeats" || cmd == "candidates" || cmd == "copies" ||
+       cmd == "plan")
     inputs.clear();  // (indexes only: nothing is staged)
   std::vector<uint8_t> check_index;
   // (read, and a missing one reported, before any device is opened)
-  if ((cmd == "sources" || cmd == "repeats" || cmd == "candidates" || cmd == "copies") &&
+  if ((cmd == "sources" || cmd == "repeats" || cmd == "candidates" || cmd == "copies" ||
+       cmd == "plan") &&
       !read_file(files[0], &check_index))
     return 2;
   if (cmd == "links" && !read_file(files[0], &check_index)) return 2;
@@ -720,6 +732,59 @@ int main(int argc, char** argv) {
             (unsigned long long)cst[2], (unsigned long long)cst[4], skipped,
             cst[6] ? "device" : "host");
     for (void* p : {(void*)cf, (void*)cs, (void*)csf, (void*)off, (void*)sp}) cir_free(p);
+  } else if (cmd == "plan") {
+    static const uint8_t none = 0;
+    const uint8_t* index = check_index.empty() ? &none : check_index.data();
+    std::vector<const uint8_t*> sidx;
+    std::vector<size_t> slen;
+    for (const std::vector<uint8_t>& v : link_indexes) {
+      sidx.push_back(v.empty() ? &none : v.data());
+      slen.push_back(v.size());
+    }
+    uint64_t* lf = nullptr;
+    uint32_t* ls = nullptr;
+    uint64_t* cf = nullptr;
+    uint32_t* cs = nullptr;
+    uint64_t* csf = nullptr;
+    uint64_t* off = nullptr;
+    uint8_t* sp = nullptr;
+    uint64_t* ext = nullptr;
+    uint64_t* rep = nullptr;
+    uint64_t* fetch = nullptr;
+    size_t nl = 0, nc = 0, ne = 0, nr = 0, skipped = 0;
+    uint64_t nblk = 0;
+    uint64_t pst[CIR_PLAN_STATS_FIELDS];
+    rc = cir_fetch_plan(ctx, index, check_index.size(), sidx.data(), slen.data(), sidx.size(),
+                        nullptr, nullptr, &lf, &ls, &nl, &cf, &cs, &csf, &off, &sp, &nc, &ext, &ne,
+                        &rep, &nr, &fetch, &nblk, &skipped, pst);
+    if (rc) {
+      die(rc, files[0].c_str());
+      return 2;
+    }
+    // every byte of a file entry is in exactly one class (nothing is denied or held here)
+    std::vector<uint64_t> sizes;
+    index_file_paths(check_index, &sizes);
+    uint64_t total = 0, left = 0;
+    for (uint64_t s : sizes) total += s;
+    for (uint64_t w = 0; w < (nblk + 63) / 64; ++w) left += (uint64_t)__builtin_popcountll(fetch[w]);
+    const uint64_t placed = pst[2] + pst[8 + 2] + pst[18 + 2] + pst[28 + 2];
+    printf("link %zu files at their own path, %llu bytes\n", nl, (unsigned long long)pst[2]);
+    printf("link %zu files by content, %llu bytes\n", nc, (unsigned long long)pst[8 + 2]);
+    printf("copy %zu extents from older images, %llu blocks, %llu bytes\n", ne,
+           (unsigned long long)pst[18 + 1], (unsigned long long)pst[18 + 2]);
+    printf("copy %zu extents inside the image, %llu blocks, %llu bytes\n", nr,
+           (unsigned long long)pst[28 + 1], (unsigned long long)pst[28 + 2]);
+    printf("fetch %llu blocks of %llu, %llu bytes\n", (unsigned long long)left,
+           (unsigned long long)nblk, (unsigned long long)(total >= placed ? total - placed : 0));
+    fflush(stdout);
+    fprintf(stderr,
+            "plan: %llu files, %llu blocks; %llu source index(es) used, %zu skipped; planned on the "
+            "%s\n",
+            (unsigned long long)pst[0], (unsigned long long)nblk, (unsigned long long)pst[4], skipped,
+            pst[42] ? "device" : "host");
+    for (void* p : {(void*)lf, (void*)ls, (void*)cf, (void*)cs, (void*)csf, (void*)off, (void*)sp,
+                    (void*)ext, (void*)rep, (void*)fetch})
+      cir_free(p);
   } else if (cmd == "sources") {
     static const uint8_t none = 0;
     std::vector<const uint8_t*> sidx;

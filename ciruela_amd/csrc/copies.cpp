@@ -23,6 +23,7 @@
 #include <vector>
 
 #include "copies.hpp"
+#include "decode.hpp"
 #include "devcall.hpp"
 #include "dirsig.hpp"
 #include "files.hpp"
@@ -221,25 +222,6 @@ int file_copies_host(const uint8_t* index, size_t len, const uint8_t* const* src
   o.stats[8] = left_out;
   o.stats[9] = same;
   return CIR_OK;
-}
-
-// Appends the decoded token at t[off ..): the stretch before its first escape in
-// one piece, the rest byte by byte (files::next_byte, which is the rule).
-void append_token(const uint8_t* t, uint64_t len, uint64_t off, std::string* p) {
-  const uint64_t lim = files::walk_lim(off, len);
-  uint64_t i = off;
-  while (i < lim && t[i] != ' ' && t[i] != '\n' && t[i] != '\\') ++i;
-  p->append(reinterpret_cast<const char*>(t) + off, i - off);
-  for (int c; (c = files::next_byte(t, &i, lim)) >= 0;) p->push_back((char)c);
-}
-
-// Appends the decoded path of the entry whose record holds (name_off, dir_off) in text t.
-void decode_path(const uint8_t* t, uint64_t len, uint64_t dir_off, uint64_t name_off,
-                 std::string* p) {
-  const size_t at = p->size();
-  append_token(t, len, dir_off, p);
-  if (p->size() != at + 1) p->push_back('/');  // (every directory but "/" gets its separator)
-  append_token(t, len, name_off, p);
 }
 
 // One text of the call on the device, beside its TextSet item.

@@ -348,6 +348,23 @@ hipError_t launch_match_copies(const FilesSide& need, const FilesSide& pool,
                                uint64_t* cand_place, uint64_t* res, hipStream_t s,
                                const hipEvent_t* tev = nullptr);
 
+// The glue of a download plan (plan.hip; cir_plan_links_dev, cir_plan_want_dev;
+// the rule is plan.hpp).  launch_plan_links: behind launch_match_files, the
+// candidates of files whose bit in deny (nullable) is set are withdrawn, skip
+// (ceil(n_files / 64) u64, every word written) = deny | candidate kept, res = 2
+// u64 {kept, withdrawn}.  launch_plan_want: behind launch_match_copies, want
+// (ceil(n_blocks / 64) u64, every word written) = blocks of the file entries of
+// the run table `runs` (4 u64 per non-empty file, `first` ascending) whose file
+// has a candidate in neither cand_a nor cand_b (n_files u32 each, nullable) and
+// whose bit in have (nullable) is 0; res = 3 u64 {wanted, blocks of linked
+// files, left out by have}.  res is zeroed here, all on `s`.  Unchecked: bs !=
+// 0, n_files and n_blocks < 2^32.
+hipError_t launch_plan_links(const uint64_t* deny, uint64_t n_files, uint32_t* cand_src,
+                             uint64_t* cand_file, uint64_t* skip, uint64_t* res, hipStream_t s);
+hipError_t launch_plan_want(const uint64_t* runs, uint64_t n_runs, uint64_t n_blocks, uint64_t bs,
+                            uint64_t n_files, const uint32_t* cand_a, const uint32_t* cand_b,
+                            const uint64_t* have, uint64_t* want, uint64_t* res, hipStream_t s);
+
 // nlanes x `lines` register-only compressions (diagnostic VALU ceiling).
 hipError_t launch_compress_only(uint64_t nlanes, uint32_t lines, uint8_t* out, hipStream_t s);
 

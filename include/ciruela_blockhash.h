@@ -53,6 +53,9 @@
  *       CIR_LINKS_MATCH=host   cir_file_sources with a context answers with the host
  *                              rule of cir_link_candidates, and cir_file_copies with
  *                              its own host rule (A/B measurement; read per call);
+ *       CIR_PLAN=host          cir_fetch_plan with a context answers with the host
+ *                              composition of the four calls it is defined by (A/B
+ *                              measurement; read per call);
  *       CIR_DEBUG_SPLIT=k      (tests) every opened GPU appears k times.
  *       CIR_DEBUG_STRIPE_BLOCKS=n  (tests) a scan over several devices deals
  *                              stripes of n blocks (default: one staging
@@ -1170,6 +1173,106 @@ int cir_file_copies(cir_ctx* ctx, const uint8_t* index, size_t len,
                     uint64_t** src_file_out, uint64_t** path_off_out, uint8_t** paths_out,
                     size_t* n_out, size_t* nskipped_out,
                     uint64_t stats[CIR_FILE_COPIES_STATS_FIELDS]);
+
+/* ---- the download plan ------------------------------------------------ */
+
+/* The glue between cir_match_files_dev and cir_match_copies_dev, device-resident
+ * (ciruela_amd/csrc/plan.hpp, plan.hip): behind cir_match_files_dev's candidates, one lane per need
+ * file i.  If d_deny (device u64 x ceil(n_files / 64), bit i & 63 of word i / 64; NULL: nothing is
+ * denied) has bit i and d_cand_src[i] != UINT32_MAX, the candidate is withdrawn: d_cand_src[i] =
+ * UINT32_MAX, d_cand_file[i] = UINT64_MAX.  d_skip (device u64 x ceil(n_files / 64)) = deny | a
+ * candidate kept: the `d_skip` of cir_match_copies_dev.  Every word of d_skip is written by the
+ * call, the bits at and past n_files as 0, with one aligned 64-bit store per wave; no atomic
+ * touches it.  d_res (device, CIR_PLAN_LINKS_RES_FIELDS u64): [0] candidates kept, [1] withdrawn;
+ * zeroed on `stream` in front of the kernel (also when n_files == 0), then one atomic add per wave
+ * that has something to add.  Like every *_dev call it allocates nothing and synchronises
+ * nothing; ctx may be NULL and is not used.
+ *
+ * CIR_EINVAL, decided before any HIP call: a null d_res; a null d_cand_src, d_cand_file or d_skip
+ * with n_files > 0; d_deny, d_cand_file, d_skip or d_res not 8-byte aligned; d_cand_src not 4-byte
+ * aligned; more than 2^32 - 1 files. */
+#define CIR_PLAN_LINKS_RES_FIELDS 2
+int cir_plan_links_dev(cir_ctx* ctx, const uint64_t* d_deny, uint64_t n_files,
+                       uint32_t* d_cand_src, uint64_t* d_cand_file, uint64_t* d_skip,
+                       uint64_t* d_res, void* stream);
+
+/* The glue between cir_match_copies_dev and cir_match_extents_dev, device-resident: the `d_want`
+ * of the latter, one lane per global block g < n_blocks.  d_need_runs is the new index's run table
+ * (cir_index_digests_dev's, or the packed form cir_match_extents_dev takes: four u64 per non-empty
+ * file {first, size, file, x}, `first` ascending; x is not read).  The table is bisected for the
+ * last run with first <= g; block g is in a file iff there is one and g - first < size /
+ * block_size + (size % block_size != 0).  The file is linked iff its ordinal f is below n_files
+ * and d_cand_a[f] != UINT32_MAX or d_cand_b[f] != UINT32_MAX (device u32 x n_files each, either
+ * may be NULL: the candidates after cir_plan_links_dev and after cir_match_copies_dev); f is
+ * checked before either array is read.  The want bit is set iff the block is in a file that is not
+ * linked and d_have (device u64 x ceil(n_blocks / 64), NULL: none) does not hold it.  Every word
+ * of d_want [0, ceil(n_blocks / 64)) is written, the bits at and past n_blocks as 0, as in
+ * cir_plan_links_dev.  d_res (device, CIR_PLAN_WANT_RES_FIELDS u64, zeroed on `stream` first): [0]
+ * blocks wanted, [1] blocks of linked files, [2] blocks left out by d_have.
+ *
+ * A table that is sorted but lies gets the answer these words define (an ordinal >= n_files is not
+ * linked; a `first` >= n_blocks covers nothing; a size of 2^64 - 1 covers every block from its
+ * `first` to the next run's); an unsorted table gets an unspecified answer.  In neither case is
+ * anything read or written outside the arrays as sized by the arguments.  No lane waits for
+ * another and the only loop, the bisection, is bounded by n_need_runs.
+ *
+ * CIR_EINVAL, decided before any HIP call: a null d_res; a null d_need_runs with n_need_runs > 0
+ * or d_want with n_blocks > 0; the run table, a bitmap or d_res not 8-byte aligned; a candidate
+ * array not 4-byte aligned; block_size == 0; more than 2^32 - 1 blocks, runs or files. */
+#define CIR_PLAN_WANT_RES_FIELDS 3
+int cir_plan_want_dev(cir_ctx* ctx, const uint64_t* d_need_runs, uint64_t n_need_runs,
+                      uint64_t n_blocks, uint64_t block_size, uint64_t n_files,
+                      const uint32_t* d_cand_a, const uint32_t* d_cand_b, const uint64_t* d_have,
+                      uint64_t* d_want, uint64_t* d_res, void* stream);
+
+/* The whole download plan of a new image in one call: what to hardlink, what to copy from older
+ * images, what to copy inside the image and what to fetch.  It is defined as this composition of
+ * the four calls above (ciruela_amd/csrc/plan.hpp), none of which changes:
+ *   1. L1 = cir_file_sources' candidates, minus the files in `deny`;
+ *   2. L2 = cir_file_copies with skip = deny | files(L1);
+ *   3. linked = files(L1) | files(L2); want1 = every block of a file entry that is not linked,
+ *      minus the 1-bits of `have`;
+ *   4. (E1, fetch1) = cir_block_extents with want = want1;
+ *   5. (E2, fetch2) = cir_block_repeats with want = fetch1 and present = every block not in
+ *      fetch1 (the linked files' blocks, the `have` blocks and the blocks E1 covers are all in
+ *      place before any copy inside the image).
+ * deny (u64 words over file ordinals, NULL: none): files for which no whole-file link may be
+ * proposed -- a candidate failed cir_check_links on an earlier pass, or the partial directory
+ * already holds an object at that path.  have (u64 words over global blocks, NULL: none): blocks
+ * already present and correct (cir_check_blocks' bitmap).  Bits past the counts are ignored.
+ *
+ * Outputs: L1 as cir_file_sources returns its pairs (link_file_out, link_src_out); L2 as
+ * cir_file_copies returns its five arrays; E1 (extents_out) and E2 (repeat_extents_out) as
+ * CIR_EXTENT_WORDS-u64 extent records; fetch2 (fetch_out, ceil(*nblk_out / 64) words).  All
+ * malloc'd (cir_free) and NULL when their count is 0.  Skipped sources are counted once
+ * (*nskipped_out, nullable).  Errors are whatever the composition would meet first; they are
+ * decided before any output is made: on error every output is NULL / 0 and the stats are zero.
+ *
+ * With a context every text is uploaded and parsed once (the four calls each do it again) and the
+ * four joins run back to back in device memory with cir_plan_links_dev and cir_plan_want_dev
+ * between them: five synchronises (the counts, the verdicts with the run tables and the
+ * candidates, the two extent counts, each extent tail).  The whole call is answered by the host
+ * composition -- the four calls with ctx = NULL -- when ctx == NULL, with CIR_PLAN=host, for a text
+ * the device declines, a collided fold, a count past a device limit, or a new index without
+ * blocks.  None of these is an error, and both paths give identical output (the stats that name
+ * the path aside).
+ *
+ * stats: [0..8) cir_file_sources' (taken before `deny` is applied), [8..18) cir_file_copies',
+ * [18..28) cir_block_extents', [28..38) cir_block_repeats', [38] same-path candidates withdrawn by
+ * `deny`, [39] files linked, [40] blocks of linked files, [41] blocks left out by `have`, [42] 1
+ * if planned on the device, [43] why not: 0, a CIR_FILE_WHY_* value (CIR_FILE_WHY_ENV:
+ * CIR_PLAN=host), or CIR_PLAN_WHY_EMPTY. */
+#define CIR_PLAN_STATS_FIELDS 44
+#define CIR_PLAN_WHY_EMPTY 5 /* the new index has no block */
+int cir_fetch_plan(cir_ctx* ctx, const uint8_t* index, size_t len,
+                   const uint8_t* const* src_index, const size_t* src_len, size_t nsrc,
+                   const uint64_t* deny, const uint64_t* have, uint64_t** link_file_out,
+                   uint32_t** link_src_out, size_t* nlinks_out, uint64_t** copy_file_out,
+                   uint32_t** copy_src_out, uint64_t** copy_src_file_out,
+                   uint64_t** copy_path_off_out, uint8_t** copy_paths_out, size_t* ncopies_out,
+                   uint64_t** extents_out, size_t* nextents_out, uint64_t** repeat_extents_out,
+                   size_t* nrepeats_out, uint64_t** fetch_out, uint64_t* nblk_out,
+                   size_t* nskipped_out, uint64_t stats[CIR_PLAN_STATS_FIELDS]);
 
 /* ---- index (DIRSIGNATURE.v1) ----------------------------------------- */
 
