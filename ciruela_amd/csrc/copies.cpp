@@ -8,10 +8,11 @@
 // below a renamed directory every file loses its hardlink and is copied
 // instead.  The rule, the key of the table and the argument that the device's
 // answer is the rule's are copies.hpp; the kernels are files.hip.  The device
-// flow is cir_file_sources' (files.cpp) through devcall.hpp: the texts framed
-// on the host and uploaded once, the count pass, the emit and decode passes
-// with cir_index_files_dev's kernels and biases, then the skip bitmap, the
-// join, and the candidates' places downloaded with the verdicts.  Whatever
+// flow is cir_file_sources' (files.cpp), the steps of devcall.hpp's FileStage:
+// the texts framed on the host and uploaded once, the count pass, the emit and
+// decode passes with cir_index_files_dev's kernels and biases; then, here, the
+// skip bitmap, the join, and the candidates' places downloaded with the
+// verdicts and compacted by copies::compact.  Whatever
 // the device cannot answer exactly is answered by the host rule here, which
 // restates copies.hpp over dirsig::parse.
 #include <stdio.h>
@@ -23,7 +24,6 @@
 #include <vector>
 
 #include "copies.hpp"
-#include "decode.hpp"
 #include "devcall.hpp"
 #include "dirsig.hpp"
 #include "files.hpp"
@@ -74,13 +74,6 @@ int match_copies_dev_impl(const dev::FilesSide& need, const dev::FilesSide& pool
 
 // ---- the whole call ------------------------------------------------------------
 
-constexpr int kHostFlow = 2;  // (no CIR_* code is positive) the host rule decides this call
-
-bool match_on_host() {  // CIR_LINKS_MATCH=host, read per call, as cir_file_sources reads it
-  const char* v = getenv("CIR_LINKS_MATCH");
-  return v && strcmp(v, "host") == 0;
-}
-
 struct Outs {
   uint64_t** file_out;
   uint32_t** src_out;
@@ -92,48 +85,12 @@ struct Outs {
   uint64_t* stats;
 };
 
-// The candidates of a call, before they become the caller's arrays.
-struct Found {
-  std::vector<uint64_t> file, src_file, path_off{0};
-  std::vector<uint32_t> src;
-  std::string paths;
-  void reserve(size_t n) {
-    file.reserve(n);
-    src.reserve(n);
-    src_file.reserve(n);
-    path_off.reserve(n + 1);
-    paths.reserve(48 * n);
-  }
-  void add(uint64_t f, uint32_t s, uint64_t sf) {  // (its path was appended to `paths`)
-    file.push_back(f);
-    src.push_back(s);
-    src_file.push_back(sf);
-    path_off.push_back(paths.size());
-  }
-};
-
-template <class T>
-bool dup(const T* p, size_t n, T** out) {
-  *out = (T*)malloc(n * sizeof(T) + !n);
-  if (*out && n) memcpy(*out, p, n * sizeof(T));
-  return *out != nullptr;
-}
+using copies::Found;
 
 int report(const Found& f, const Outs& o) {
-  const size_t n = f.file.size();
-  if (n == 0) return CIR_OK;  // (every output is null already)
-  if (!dup(f.file.data(), n, o.file_out) || !dup(f.src.data(), n, o.src_out) ||
-      !dup(f.src_file.data(), n, o.src_file_out) || !dup(f.path_off.data(), n + 1, o.path_off_out) ||
-      !dup((const uint8_t*)f.paths.data(), f.paths.size(), o.paths_out)) {
-    for (void* p : {(void*)*o.file_out, (void*)*o.src_out, (void*)*o.src_file_out,
-                    (void*)*o.path_off_out, (void*)*o.paths_out})
-      free(p);
-    *o.file_out = *o.src_file_out = *o.path_off_out = nullptr;
-    *o.src_out = nullptr;
-    *o.paths_out = nullptr;
+  if (!f.give(o.file_out, o.src_out, o.src_file_out, o.path_off_out, o.paths_out))
     return fail(CIR_ENOMEM, "malloc");
-  }
-  *o.n_out = n;
+  *o.n_out = f.file.size();
   return CIR_OK;
 }
 
@@ -224,183 +181,74 @@ int file_copies_host(const uint8_t* index, size_t len, const uint8_t* const* src
   return CIR_OK;
 }
 
-// One text of the call on the device, beside its TextSet item.
-struct Text {
-  uint32_t ordinal = 0;  // the source's, as the caller counts
-  uint64_t fwork_off = 0;
-  uint64_t nfiles = 0, nblk = 0;
-};
-
 // With a context: on its first device, under that device's lock.  Returns a
 // CIR_* code, or kHostFlow with *why set and nothing reported.
 int file_copies_dev(cir_ctx* ctx, const uint8_t* index, size_t len,
                     const uint8_t* const* src_index, const size_t* src_len, size_t nsrc,
                     const uint64_t* skip, const Outs& o, bool trace, uint64_t* why) {
   if (ctx->devs.empty()) return fail(CIR_EINVAL, "context without a device");
-  if (nsrc > 0xFFFFFFFEull) return fail(CIR_EINVAL, "too many sources");
   const auto t0 = Clock::now();
-  dirsig::Header h;
-  std::string err;
   // host memory that asynchronous copies read or write: declared before the call
-  TextSet ts;  // the new index, then the sources that take part
-  std::vector<Text> tx(1);  // (tx[k] goes with ts.item[k])
-  size_t body_off = 0, body_end = 0;
-  *why = CIR_FILE_WHY_DECLINED;  // (a frame that does not parse is the host parser's to report)
-  if (!dirsig::frame(index, len, &h, &body_off, &body_end, &err)) return kHostFlow;
-  ts.add(index, len, body_off, body_end);
-  bool fits = device_takes(len);
-  uint64_t fwork_bytes = dev::files_work_bytes(len);
-  for (size_t j = 0; j < nsrc; ++j) {
-    Text t;
-    dirsig::Header sh;
-    std::string serr;
-    if (!src_index[j] || !dirsig::frame(src_index[j], src_len[j], &sh, &body_off, &body_end, &serr) ||
-        sh.hash != h.hash || sh.block_size != h.block_size)
-      continue;  // skipped, and not uploaded
-    ts.add(src_index[j], src_len[j], body_off, body_end);
-    t.ordinal = (uint32_t)j;
-    t.fwork_off = fwork_bytes;
-    fwork_bytes += dev::files_work_bytes(src_len[j]);
-    fits = fits && device_takes(src_len[j]);
-    tx.push_back(t);
-  }
-  *why = CIR_FILE_WHY_LIMIT;
-  if (!fits) return kHostFlow;
-  const uint64_t bs = h.block_size, text_bytes = ts.text_bytes;
-  const size_t nt = tx.size(), used = nt - 1;
-  std::vector<uint64_t> f_res(files::kResFields * nt);
-  std::vector<uint64_t> src_first(used + 1);
+  FileStage st;
   std::vector<uint32_t> cand;
   std::vector<uint64_t> cfile, cplace;
   std::vector<files::Rec> nrec;
   uint64_t m_res[files::kResFields] = {0, 0, 0, 0};
   TraceEvents<5> mev;
+  int rc;
+  if ((rc = st.frame(index, len, src_index, src_len, nsrc, why))) return rc;
 
   DeviceCall c(ctx);
   hipStream_t s = c.s;
-  uint8_t* d_fwork = nullptr;
-  uint64_t* d_fres = nullptr;
-  int rc;
-  // (the text buffer with 16 bytes to spare, as cir_index_files_dev's callers give it)
-  if ((rc = c.begin()) || (rc = ts.count(c, bs, 16, trace))) return rc;
-  const auto t1 = ts.t_bufs, t2 = ts.t_up, t3 = ts.t_counted;
-  uint8_t* const d_text = ts.d_text;
-  uint64_t pool_files = 0, pool_blocks = 0;
-  for (size_t k = 0; k < nt; ++k) {
-    const uint64_t* r = ts.item[k].cnt;
-    if (r[0] != CIR_INDEX_OK) {
-      *why = CIR_FILE_WHY_DECLINED;
-      return kHostFlow;
-    }
-    tx[k].nfiles = r[1];
-    tx[k].nblk = r[3];
-    if (k) {
-      src_first[k - 1] = pool_files;
-      pool_files += r[1];
-      pool_blocks += r[3];
-    }
-  }
-  src_first[used] = pool_files;
-  const uint64_t need_files = tx[0].nfiles, need_blocks = tx[0].nblk;
+  if ((rc = c.begin()) || (rc = st.count(c, trace, why))) return rc;
+  const auto t1 = st.ts.t_bufs, t2 = st.ts.t_up, t3 = st.ts.t_counted;
+  const uint64_t need_files = st.need_files(), pool_files = st.pool_files;
   const uint64_t skip_words = (need_files + 63) / 64;
-  if (pool_files > files::kMaxPoolFiles || need_files > files::kMaxNeedFiles ||
-      pool_blocks > 0xFFFFFFFFull)
-    return kHostFlow;  // (*why is CIR_FILE_WHY_LIMIT)
-  // the join's buffers; the digests and the records are written straight into them
-  uint8_t* d_ndig = nullptr;
-  uint8_t* d_pdig = nullptr;
-  uint64_t* d_nrec = nullptr;
-  uint64_t* d_prec = nullptr;
-  uint64_t* d_first = nullptr;
+  const size_t used = st.used;
   uint64_t* d_skip = nullptr;
   uint64_t* d_mwork = nullptr;
   uint32_t* d_csrc = nullptr;
   uint64_t* d_cfile = nullptr;
   uint64_t* d_cplace = nullptr;
   uint64_t* d_mres = nullptr;
-  if ((rc = c.alloc(&d_fwork, fwork_bytes)) || (rc = c.alloc(&d_fres, 8 * f_res.size())) ||
-      (rc = c.alloc(&d_ndig, 32 * need_blocks + 32)) ||
-      (rc = c.alloc(&d_pdig, 32 * pool_blocks + 32)) ||
-      (rc = c.alloc(&d_nrec, 32 * need_files)) || (rc = c.alloc(&d_prec, 32 * pool_files)) ||
-      (rc = c.alloc(&d_first, 8 * (used + 1))) ||
-      (skip && (rc = c.alloc(&d_skip, 8 * skip_words))) ||
+  if ((rc = st.alloc(c)) || (skip && (rc = c.alloc(&d_skip, 8 * skip_words))) ||
       (rc = c.alloc(&d_mwork, dev::match_files_work_bytes(need_files, pool_files))) ||
       (rc = c.alloc(&d_csrc, 4 * need_files)) || (rc = c.alloc(&d_cfile, 8 * need_files)) ||
       (rc = c.alloc(&d_cplace, 16 * need_files)) || (rc = c.alloc(&d_mres, sizeof m_res)))
     return rc;
   if (trace && (rc = mev.create())) return rc;
-  CIR_HIP(hipMemcpyAsync(d_first, src_first.data(), 8 * (used + 1), hipMemcpyHostToDevice, s));
-  uint64_t file_at = 0, block_at = 0;  // pool ordinals of the next source's first file and block
-  for (size_t k = 0; k < nt; ++k) {
-    const Text& t = tx[k];
-    const TextSet::Item& it = ts.item[k];
-    uint8_t* dig = k ? d_pdig + 32 * block_at : d_ndig;
-    uint64_t* rec = k ? d_prec + files::kFileWords * file_at : d_nrec;
-    if ((rc = ts.emit(c, k, dig, t.nblk))) return rc;
-    CIR_HIP(dev::launch_index_files(d_text + it.text_off, it.len, it.body_off, it.body_end, bs,
-                                    it.text_off, k ? block_at : 0, rec, t.nfiles,
-                                    (uint64_t*)(d_fwork + t.fwork_off),
-                                    d_fres + files::kResFields * k, s, false));
-    if (k) {
-      file_at += t.nfiles;
-      block_at += t.nblk;
-    }
-  }
+  if ((rc = st.emit(c))) return rc;
   if (skip && skip_words)
     CIR_HIP(hipMemcpyAsync(d_skip, skip, 8 * skip_words, hipMemcpyHostToDevice, s));
   if (trace) CIR_HIP(hipStreamSynchronize(s));
   const auto t4 = Clock::now();
-  const dev::FilesSide need{d_text, text_bytes, d_nrec, need_files, d_ndig, need_blocks};
-  const dev::FilesSide pool{d_text, text_bytes, d_prec, pool_files, d_pdig, pool_blocks};
-  CIR_HIP(dev::launch_match_copies(need, pool, d_first, used, bs, skip_words ? d_skip : nullptr,
-                                   nullptr, draw_seed(), d_mwork, d_csrc, d_cfile, d_cplace, d_mres,
-                                   s, trace ? mev.ev : nullptr));
+  CIR_HIP(dev::launch_match_copies(st.need(), st.pool(), st.d_first, used, st.h.block_size,
+                                   skip_words ? d_skip : nullptr, nullptr, draw_seed(), d_mwork,
+                                   d_csrc, d_cfile, d_cplace, d_mres, s, trace ? mev.ev : nullptr));
   cand.resize(need_files);
   cfile.resize(need_files);
   cplace.resize(copies::kPlaceWords * need_files);
   nrec.resize(need_files);
-  CIR_HIP(hipMemcpyAsync(f_res.data(), d_fres, 8 * f_res.size(), hipMemcpyDeviceToHost, s));
+  if ((rc = st.queue_verdicts(c))) return rc;
   CIR_HIP(hipMemcpyAsync(m_res, d_mres, sizeof m_res, hipMemcpyDeviceToHost, s));
   if (need_files) {
     CIR_HIP(hipMemcpyAsync(cand.data(), d_csrc, 4 * need_files, hipMemcpyDeviceToHost, s));
     CIR_HIP(hipMemcpyAsync(cfile.data(), d_cfile, 8 * need_files, hipMemcpyDeviceToHost, s));
     CIR_HIP(hipMemcpyAsync(cplace.data(), d_cplace, 16 * need_files, hipMemcpyDeviceToHost, s));
     // (the need records: where each entry's own path stands, for stats[9])
-    CIR_HIP(hipMemcpyAsync(nrec.data(), d_nrec, 32 * need_files, hipMemcpyDeviceToHost, s));
+    CIR_HIP(hipMemcpyAsync(nrec.data(), st.d_nrec, 32 * need_files, hipMemcpyDeviceToHost, s));
   }
-  if ((rc = ts.finish(c, false))) return rc;  // (the run tables stay on the device)
+  if ((rc = st.ts.finish(c, false))) return rc;  // (the run tables stay on the device)
   const auto t5 = Clock::now();
-  // every verdict is in: a bad token shows only after the decode pass
-  for (size_t k = 0; k < nt; ++k) {
-    const uint64_t* fr = f_res.data() + files::kResFields * k;
-    if (ts.status(k) != CIR_INDEX_OK || fr[0] != CIR_INDEX_OK || fr[1] != tx[k].nfiles ||
-        fr[2] != tx[k].nblk) {
-      *why = CIR_FILE_WHY_DECLINED;
-      return kHostFlow;
-    }
-  }
-  if (m_res[0] != files::kOk) {
-    *why = CIR_FILE_WHY_COLLISION;
-    return kHostFlow;
-  }
+  if ((rc = st.verdicts_ok(m_res[0] == files::kOk, why))) return rc;
   // compact, and decode each candidate's path from the source text held here
   Found found;
   found.reserve(m_res[1] <= need_files ? m_res[1] : 0);
-  uint64_t left_out = 0, same = 0;
-  const TextSet::Item& ni = ts.item[0];
-  for (uint64_t i = 0; i < need_files; ++i) {
-    left_out += copies::skipped(skip, i);
-    if (cand[i] == files::kNoSrc) continue;
-    if (cand[i] >= used) return fail(CIR_EHIP, "candidate source out of range");
-    const TextSet::Item& it = ts.item[1 + cand[i]];
-    const uint64_t name = cplace[2 * i] - it.text_off, dir = cplace[2 * i + 1] - it.text_off;
-    const uint64_t nname = nrec[i].name_off - ni.text_off, ndir = nrec[i].dir_off - ni.text_off;
-    if (name >= it.len || dir >= it.len || nname >= ni.len || ndir >= ni.len ||
-        cfile[i] >= tx[1 + cand[i]].nfiles)
-      return fail(CIR_EHIP, "candidate place out of range");
-    decode_path(it.p, it.len, dir, name, &found.paths);
-    found.add(i, tx[1 + cand[i]].ordinal, cfile[i]);
-    same += files::same_path(ni.p, ni.len, ndir, nname, it.p, it.len, dir, name);
+  switch (copies::compact(cand.data(), cfile.data(), cplace.data(), nrec.data(), need_files,
+                          st.placed().data(), used, skip, &found)) {
+    case copies::kBadSource: return fail(CIR_EHIP, "candidate source out of range");
+    case copies::kBadPlace: return fail(CIR_EHIP, "candidate place out of range");
+    case copies::kCompacted: break;
   }
   if (found.file.size() != m_res[1]) return fail(CIR_EHIP, "candidate count mismatch");
   if ((rc = report(found, o))) return rc;
@@ -414,8 +262,8 @@ int file_copies_dev(cir_ctx* ctx, const uint8_t* index, size_t len,
   o.stats[5] = dev::join_table_slots(pool_files);
   o.stats[6] = 1;
   o.stats[7] = 0;
-  o.stats[8] = left_out;
-  o.stats[9] = same;
+  o.stats[8] = found.left_out;
+  o.stats[9] = found.same;
   if (trace) {
     const float lap[4] = {mev.lap(0), mev.lap(1), mev.lap(2), mev.lap(3)};
     fprintf(stderr,
@@ -424,12 +272,12 @@ int file_copies_dev(cir_ctx* ctx, const uint8_t* index, size_t len,
             "kernels %.2f ms, emit kernels %.2f ms, fold kernels %.3f ms, build kernel %.3f ms, "
             "probe kernel %.3f ms, verify kernel %.3f ms, join and download %.2f ms, compact and "
             "decode %.2f ms; %llu candidates, %llu skipped, %llu at their own path\n",
-            (unsigned long long)need_files, (unsigned long long)need_blocks,
-            (unsigned long long)pool_files, (unsigned long long)pool_blocks, used,
-            ms_between(t0, t1), ms_between(t1, t2), (unsigned long long)text_bytes,
+            (unsigned long long)need_files, (unsigned long long)st.need_blocks(),
+            (unsigned long long)pool_files, (unsigned long long)st.pool_blocks, used,
+            ms_between(t0, t1), ms_between(t1, t2), (unsigned long long)st.ts.text_bytes,
             ms_between(t2, t3), ms_between(t3, t4), lap[0], lap[1], lap[2], lap[3],
             ms_between(t4, t5), ms_between(t5, Clock::now()), (unsigned long long)n,
-            (unsigned long long)left_out, (unsigned long long)same);
+            (unsigned long long)found.left_out, (unsigned long long)found.same);
   }
   return CIR_OK;
 }

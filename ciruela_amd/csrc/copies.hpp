@@ -1,7 +1,10 @@
 // The rule of cir_file_copies / cir_match_copies_dev, written once for the
 // host and the device: which need files take part, the key of the table, and
-// the host form of the device join.  No HIP runtime call; compiled by
-// files.hip (the kernels), copies.cpp and, under the sanitizers, by
+// the host form of the device join; and the compaction of the device's
+// content candidates into the caller's arrays (Found, compact), the one piece
+// of host code that trusts nothing the device wrote, shared by cir_file_copies
+// and cir_fetch_plan.  No HIP runtime call; compiled by files.hip (the
+// kernels), copies.cpp, plan.cpp and, under the sanitizers, by
 // tools/copies_fuzz.cpp.  Records, fold term and src_of are files.hpp's.
 //
 // The rule.  Pool files are ordered by source in the order given, then in
@@ -31,8 +34,13 @@
 #include <stddef.h>
 #include <stdint.h>
 
+#include <stdlib.h>
+#include <string.h>
+
+#include <string>
 #include <vector>
 
+#include "decode.hpp"
 #include "files.hpp"
 
 namespace cir {
@@ -140,6 +148,98 @@ inline void host_match(const files::Side& need, const files::Side& pool, const u
         break;
       }
   }
+}
+
+// A malloc'd copy of p[0, n) for the caller; null when n == 0.
+template <class T>
+bool dup(const T* p, size_t n, T** out) {
+  *out = n ? (T*)malloc(n * sizeof(T)) : nullptr;
+  if (*out) memcpy(*out, p, n * sizeof(T));
+  return !n || *out != nullptr;
+}
+
+// The content candidates of a call, before they become the caller's arrays.
+struct Found {
+  std::vector<uint64_t> file, src_file, path_off{0};
+  std::vector<uint32_t> src;
+  std::string paths;
+  uint64_t left_out = 0, same = 0;  // need files the bitmap skips; candidates at their own path
+  void reserve(size_t n) {
+    file.reserve(n);
+    src.reserve(n);
+    src_file.reserve(n);
+    path_off.reserve(n + 1);
+    paths.reserve(48 * n);
+  }
+  void add(uint64_t f, uint32_t s, uint64_t sf) {  // (its path was appended to `paths`)
+    file.push_back(f);
+    src.push_back(s);
+    src_file.push_back(sf);
+    path_off.push_back(paths.size());
+  }
+  // The five arrays malloc'd for the caller, all null when there is no
+  // candidate; false, and all null, when a malloc fails.
+  bool give(uint64_t** file_out, uint32_t** src_out, uint64_t** src_file_out,
+            uint64_t** path_off_out, uint8_t** paths_out) const {
+    const size_t n = file.size();
+    *file_out = *src_file_out = *path_off_out = nullptr;
+    *src_out = nullptr;
+    *paths_out = nullptr;
+    if (dup(file.data(), n, file_out) && dup(src.data(), n, src_out) &&
+        dup(src_file.data(), n, src_file_out) &&
+        dup(path_off.data(), n ? n + 1 : 0, path_off_out) &&
+        dup((const uint8_t*)paths.data(), paths.size(), paths_out))
+      return true;
+    for (void* p : {(void*)*file_out, (void*)*src_out, (void*)*src_file_out, (void*)*path_off_out,
+                    (void*)*paths_out})
+      free(p);
+    *file_out = *src_file_out = *path_off_out = nullptr;
+    *src_out = nullptr;
+    *paths_out = nullptr;
+    return false;
+  }
+};
+
+// One text of a call as compact() reads it: its bytes on the host, where it
+// stands in the device's text arena (from whose start the records' offsets
+// count), its file entries, and the source's ordinal as the caller counts.
+struct PlacedText {
+  const uint8_t* p;
+  uint64_t len, text_off, nfiles;
+  uint32_t ordinal;
+};
+
+enum Compacted { kCompacted = 0, kBadSource, kBadPlace };
+
+// The join's downloaded answer (cand_src, cand_file, need_recs: one entry per
+// need file; cand_place: kPlaceWords) into `found`, each candidate's path
+// decoded from its source's text; found->left_out counts the 1-bits of `skip`
+// (null: none).  text[0] is the need's, text[1 + s] source s of `used`.
+// Nothing the device wrote is trusted: a source >= used is kBadSource, a file
+// >= the source's nfiles or a place of either side outside its text kBadPlace,
+// and nothing is read outside the texts and the arrays.
+inline Compacted compact(const uint32_t* cand_src, const uint64_t* cand_file,
+                         const uint64_t* cand_place, const files::Rec* need_recs,
+                         uint64_t need_files, const PlacedText* text, size_t used,
+                         const uint64_t* skip, Found* found) {
+  const PlacedText& ni = text[0];
+  for (uint64_t i = 0; i < need_files; ++i) {
+    found->left_out += skipped(skip, i);
+    if (cand_src[i] == files::kNoSrc) continue;
+    if (cand_src[i] >= used) return kBadSource;
+    const PlacedText& it = text[1 + cand_src[i]];
+    const uint64_t name = cand_place[kPlaceWords * i] - it.text_off;
+    const uint64_t dir = cand_place[kPlaceWords * i + 1] - it.text_off;
+    const uint64_t nname = need_recs[i].name_off - ni.text_off;
+    const uint64_t ndir = need_recs[i].dir_off - ni.text_off;
+    if (name >= it.len || dir >= it.len || nname >= ni.len || ndir >= ni.len ||
+        cand_file[i] >= it.nfiles)
+      return kBadPlace;
+    decode_path(it.p, it.len, dir, name, &found->paths);
+    found->add(i, it.ordinal, cand_file[i]);
+    found->same += files::same_path(ni.p, ni.len, ndir, nname, it.p, it.len, dir, name);
+  }
+  return kCompacted;
 }
 
 }  // namespace copies

@@ -1,7 +1,10 @@
 // The device flow of the whole-call entry points over index texts
-// (devcall.hpp): the two parses and the extent tail.
+// (devcall.hpp): the two parses, the file-level stage and the extent tail.
 #include "devcall.hpp"
 
+#include <string>
+
+#include "files.hpp"
 #include "sources.hpp"
 
 namespace cir {
@@ -75,6 +78,124 @@ int TextSet::finish(DeviceCall& c, bool with_runs) {
   }
   CIR_HIP(hipStreamSynchronize(c.s));
   return CIR_OK;
+}
+
+int FileStage::frame(const uint8_t* index, size_t len, const uint8_t* const* src_index,
+                     const size_t* src_len, size_t nsrc, uint64_t* why) {
+  if (nsrc > 0xFFFFFFFEull) return fail(CIR_EINVAL, "too many sources");
+  std::string err;
+  size_t body_off = 0, body_end = 0;
+  *why = CIR_FILE_WHY_DECLINED;  // (a frame that does not parse is the host parser's to report)
+  if (!dirsig::frame(index, len, &h, &body_off, &body_end, &err)) return kHostFlow;
+  ts.add(index, len, body_off, body_end);
+  tx.assign(1, Text{});
+  bool fits = device_takes(len);
+  fwork_bytes_ = dev::files_work_bytes(len);
+  for (size_t j = 0; j < nsrc; ++j) {
+    Text t;
+    dirsig::Header sh;
+    std::string serr;
+    if (!src_index[j] ||
+        !dirsig::frame(src_index[j], src_len[j], &sh, &body_off, &body_end, &serr) ||
+        sh.hash != h.hash || sh.block_size != h.block_size)
+      continue;  // skipped, and not uploaded
+    ts.add(src_index[j], src_len[j], body_off, body_end);
+    t.ordinal = (uint32_t)j;
+    t.fwork_off = fwork_bytes_;
+    fwork_bytes_ += dev::files_work_bytes(src_len[j]);
+    fits = fits && device_takes(src_len[j]);
+    tx.push_back(t);
+  }
+  *why = CIR_FILE_WHY_LIMIT;
+  if (!fits) return kHostFlow;
+  used = tx.size() - 1;
+  f_res.assign(files::kResFields * tx.size(), 0);
+  src_first.assign(used + 1, 0);
+  return CIR_OK;
+}
+
+int FileStage::count(DeviceCall& c, bool trace, uint64_t* why) {
+  // (the text buffer with 16 bytes to spare, as cir_index_files_dev's callers give it)
+  if (const int rc = ts.count(c, h.block_size, 16, trace)) return rc;
+  for (size_t k = 0; k < tx.size(); ++k) {
+    const uint64_t* r = ts.item[k].cnt;
+    if (r[0] != CIR_INDEX_OK) {
+      *why = CIR_FILE_WHY_DECLINED;
+      return kHostFlow;
+    }
+    tx[k].nfiles = r[1];
+    tx[k].nblk = r[3];
+    if (k) {
+      src_first[k - 1] = pool_files;
+      pool_files += r[1];
+      pool_blocks += r[3];
+    }
+  }
+  src_first[used] = pool_files;
+  *why = CIR_FILE_WHY_LIMIT;
+  if (pool_files > files::kMaxPoolFiles || need_files() > files::kMaxNeedFiles ||
+      pool_blocks > 0xFFFFFFFFull)
+    return kHostFlow;
+  return CIR_OK;
+}
+
+// The digests and the records are written straight into the joins' buffers.
+// The record kernels' small scratch and results are allocated here and not in
+// front of the texts: with them first, case (c) of DESIGN 4.5h was 0.15 to 0.3
+// ms slower (profiles/index_calls/ab.json, alloc_order).
+int FileStage::alloc(DeviceCall& c) {
+  int rc;
+  (rc = c.alloc(&d_fwork, fwork_bytes_)) || (rc = c.alloc(&d_fres, 8 * f_res.size())) ||
+      (rc = c.alloc(&d_ndig, 32 * need_blocks() + 32)) ||
+      (rc = c.alloc(&d_pdig, 32 * pool_blocks + 32)) ||
+      (rc = c.alloc(&d_nrec, 32 * need_files())) || (rc = c.alloc(&d_prec, 32 * pool_files)) ||
+      (rc = c.alloc(&d_first, 8 * (used + 1)));
+  return rc;
+}
+
+int FileStage::emit(DeviceCall& c) {
+  CIR_HIP(hipMemcpyAsync(d_first, src_first.data(), 8 * (used + 1), hipMemcpyHostToDevice, c.s));
+  uint64_t file_at = 0, block_at = 0;  // pool ordinals of the next source's first file and block
+  for (size_t k = 0; k < tx.size(); ++k) {
+    const Text& t = tx[k];
+    const TextSet::Item& it = ts.item[k];
+    uint8_t* dig = k ? d_pdig + 32 * block_at : d_ndig;
+    uint64_t* rec = k ? d_prec + files::kFileWords * file_at : d_nrec;
+    if (const int rc = ts.emit(c, k, dig, t.nblk)) return rc;
+    CIR_HIP(dev::launch_index_files(ts.d_text + it.text_off, it.len, it.body_off, it.body_end,
+                                    h.block_size, it.text_off, k ? block_at : 0, rec, t.nfiles,
+                                    (uint64_t*)(d_fwork + t.fwork_off),
+                                    d_fres + files::kResFields * k, c.s, false));
+    if (k) {
+      file_at += t.nfiles;
+      block_at += t.nblk;
+    }
+  }
+  return CIR_OK;
+}
+
+int FileStage::verdicts_ok(bool joins_ok, uint64_t* why) const {
+  for (size_t k = 0; k < tx.size(); ++k) {
+    const uint64_t* fr = f_res.data() + files::kResFields * k;
+    if (ts.status(k) != CIR_INDEX_OK || fr[0] != CIR_INDEX_OK || fr[1] != tx[k].nfiles ||
+        fr[2] != tx[k].nblk) {
+      *why = CIR_FILE_WHY_DECLINED;
+      return kHostFlow;
+    }
+  }
+  if (!joins_ok) {
+    *why = CIR_FILE_WHY_COLLISION;
+    return kHostFlow;
+  }
+  return CIR_OK;
+}
+
+std::vector<copies::PlacedText> FileStage::placed() const {
+  std::vector<copies::PlacedText> out;
+  out.reserve(tx.size());
+  for (size_t k = 0; k < tx.size(); ++k)
+    out.push_back({ts.item[k].p, ts.item[k].len, ts.item[k].text_off, tx[k].nfiles, tx[k].ordinal});
+  return out;
 }
 
 int parse_one_text(DeviceCall& c, const uint8_t* text, size_t len, uint64_t body_off,

@@ -1,9 +1,11 @@
 // What the whole-call entry points over index texts share (sources.cpp,
-// repeats.cpp, files.cpp, idxscan.cpp): the per-call seed and lap clock, the
-// call's hold on the context's first device (DeviceCall), the trace events,
-// the size test, the two device parses of index texts (TextSet: k framed
-// texts in two passes; parse_one_text: one text in one shot) and the extent
-// tail on the device.  The bodies are devcall.cpp.
+// repeats.cpp, files.cpp, copies.cpp, plan.cpp, idxscan.cpp): the per-call
+// seed and lap clock, the call's hold on the context's first device
+// (DeviceCall), the trace events, the size test, the two device parses of
+// index texts (TextSet: k framed texts in two passes; parse_one_text: one text
+// in one shot), the file-level stage over a TextSet (FileStage: files.cpp,
+// copies.cpp, plan.cpp) and the extent tail on the device.  The bodies are
+// devcall.cpp.
 #pragma once
 #include <stdlib.h>
 #include <string.h>
@@ -14,6 +16,8 @@
 #include <random>
 #include <vector>
 
+#include "copies.hpp"
+#include "dirsig.hpp"
 #include "idxscan.hpp"
 #include "runtime.hpp"
 
@@ -31,10 +35,20 @@ inline double ms_between(Clock::time_point a, Clock::time_point b) {
   return std::chrono::duration<double, std::milli>(b - a).count();
 }
 
+// (no CIR_* code is positive) the host rule decides this call
+constexpr int kHostFlow = 2;
+
 // CIR_SOURCES_PARSE=host: with a context, parse every text on the host as
 // before the device parse existed (A/B measurement).
 inline bool parse_on_host() {
   const char* v = getenv("CIR_SOURCES_PARSE");
+  return v && strcmp(v, "host") == 0;
+}
+
+// CIR_LINKS_MATCH=host, read per call: cir_file_sources and cir_file_copies
+// with a context answer with the host rule (A/B measurement).
+inline bool match_on_host() {
+  const char* v = getenv("CIR_LINKS_MATCH");
   return v && strcmp(v, "host") == 0;
 }
 
@@ -149,6 +163,71 @@ struct TextSet {
 
  private:
   uint64_t bs_ = 0;
+};
+
+// The file-level stage over a TextSet, which cir_file_sources, cir_file_copies
+// and cir_fetch_plan share: the new index and the sources that take part are
+// counted, then emitted with their file records (launch_index_files) into one
+// need side and one pool side, the inputs of the file joins.  A text the
+// device declines, at any step, sends the whole call to the host rule: every
+// step returns a CIR_* code, or kHostFlow with *why set to a CIR_FILE_WHY_*
+// reason.  The steps run once each, in the order declared; the caller's own
+// allocations, uploads, launches and downloads go between them.  Like TextSet
+// it owns host memory that asynchronous copies read and write, so it is
+// declared before the DeviceCall it works on.
+struct FileStage {
+  struct Text {            // beside ts.item[k]
+    uint32_t ordinal = 0;  // the source's, as the caller counts
+    uint64_t fwork_off = 0;
+    uint64_t nfiles = 0, nblk = 0;
+  };
+  TextSet ts;  // the new index, then the sources that take part
+  std::vector<Text> tx;
+  dirsig::Header h;                        // the new index's
+  size_t used = 0;                         // sources that take part
+  std::vector<uint64_t> src_first, f_res;  // used + 1 pool ordinals; kResFields words per text
+  uint64_t pool_files = 0, pool_blocks = 0;
+  // the record kernels' scratch and results; the joins' inputs: digests and
+  // records of either side, and src_first
+  uint8_t *d_fwork = nullptr, *d_ndig = nullptr, *d_pdig = nullptr;
+  uint64_t *d_fres = nullptr, *d_nrec = nullptr, *d_prec = nullptr, *d_first = nullptr;
+
+  // Frames the new index and every source; a source that is null, does not
+  // frame, or has another hash or block size is skipped and not uploaded.
+  int frame(const uint8_t* index, size_t len, const uint8_t* const* src_index,
+            const size_t* src_len, size_t nsrc, uint64_t* why);
+  // TextSet::count (the first synchronise), then the counts per text, the
+  // sources' first pool ordinals and the joins' limits.
+  int count(DeviceCall& c, bool trace, uint64_t* why);
+  // d_fwork, d_fres, d_ndig, d_pdig, d_nrec, d_prec, d_first, in that order
+  // (devcall.cpp says why), behind the texts' and in front of the caller's own.
+  int alloc(DeviceCall& c);
+  // Queues the upload of src_first, then per text the emit pass and the record
+  // kernels, into the need side or the pool side's next slice.
+  int emit(DeviceCall& c);
+  // Queues the download of f_res.  The caller queues its own downloads behind
+  // it and calls ts.finish(c, with_runs), which synchronises.
+  int queue_verdicts(DeviceCall& c) {
+    CIR_HIP(hipMemcpyAsync(f_res.data(), d_fres, 8 * f_res.size(), hipMemcpyDeviceToHost, c.s));
+    return CIR_OK;
+  }
+  // Every verdict is in: a bad token shows only after the decode pass.
+  // joins_ok: did every file join of the caller end with files::kOk?
+  int verdicts_ok(bool joins_ok, uint64_t* why) const;
+
+  uint64_t need_files() const { return tx[0].nfiles; }
+  uint64_t need_blocks() const { return tx[0].nblk; }
+  dev::FilesSide need() const {
+    return {ts.d_text, ts.text_bytes, d_nrec, need_files(), d_ndig, need_blocks()};
+  }
+  dev::FilesSide pool() const {
+    return {ts.d_text, ts.text_bytes, d_prec, pool_files, d_pdig, pool_blocks};
+  }
+  // The texts as copies::compact reads them: the need's, then the sources'.
+  std::vector<copies::PlacedText> placed() const;
+
+ private:
+  uint64_t fwork_bytes_ = 0;
 };
 
 // The one-shot device parse of one framed text: upload, launch_index_digests

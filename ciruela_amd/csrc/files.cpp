@@ -9,10 +9,11 @@
 // digests already are: the records, the path hash and the fold are files.hpp,
 // the kernels files.hip and idxscan.hip.  Whatever the device cannot answer
 // exactly -- a text it declines, a collided fold, a count past a limit -- is
-// answered by the host rule, unchanged.  The hold on the device and the
-// two-pass parse of the texts are devcall.hpp's (DeviceCall, TextSet); the
-// file records' scratch and results, and the policy -- any text declined sends
-// the whole call to the host rule, with a reason -- are here.
+// answered by the host rule, unchanged.  The hold on the device, the two-pass
+// parse of the texts, the file records and the policy -- any text declined
+// sends the whole call to the host rule, with a reason -- are devcall.hpp's
+// (DeviceCall, TextSet, FileStage), shared with copies.cpp and plan.cpp; the
+// join, its buffers and the compaction of its answer are here.
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -92,20 +93,6 @@ int match_files_dev_impl(const dev::FilesSide& need, const dev::FilesSide& pool,
 
 // ---- the whole call ------------------------------------------------------------
 
-enum Why : uint64_t { kWhyNone = 0, kWhyDeclined = 1, kWhyCollision = 2, kWhyLimit = 3, kWhyEnv = 4 };
-static_assert(CIR_FILE_WHY_DECLINED == kWhyDeclined && CIR_FILE_WHY_COLLISION == kWhyCollision &&
-                  CIR_FILE_WHY_LIMIT == kWhyLimit && CIR_FILE_WHY_ENV == kWhyEnv,
-              "the header's reasons");
-
-constexpr int kHostFlow = 2;  // (no CIR_* code is positive) the host rule decides this call
-
-// CIR_LINKS_MATCH=host, read per call: cir_file_sources with a context answers
-// with the host rule (A/B measurement).
-bool match_on_host() {
-  const char* v = getenv("CIR_LINKS_MATCH");
-  return v && strcmp(v, "host") == 0;
-}
-
 struct Outs {
   uint64_t** file_out;
   uint32_t** src_out;
@@ -114,151 +101,51 @@ struct Outs {
   uint64_t* stats;
 };
 
-// One text of the call on the device, beside its TextSet item.
-struct Text {
-  uint32_t ordinal = 0;  // the source's, as the caller counts
-  uint64_t fwork_off = 0;
-  uint64_t nfiles = 0, nblk = 0;
-};
-
 // With a context: on its first device, under that device's lock.  Returns a
 // CIR_* code, or kHostFlow with *why set and nothing reported.
 int file_sources_dev(cir_ctx* ctx, const uint8_t* index, size_t len,
                      const uint8_t* const* src_index, const size_t* src_len, size_t nsrc,
                      const Outs& o, bool trace, uint64_t* why) {
   if (ctx->devs.empty()) return fail(CIR_EINVAL, "context without a device");
-  if (nsrc > 0xFFFFFFFEull) return fail(CIR_EINVAL, "too many sources");
   const auto t0 = Clock::now();
-  dirsig::Header h;
-  std::string err;
   // host memory that asynchronous copies read or write: declared before the call
-  TextSet ts;  // the new index, then the sources that take part
-  std::vector<Text> tx(1);  // (tx[k] goes with ts.item[k])
-  size_t body_off = 0, body_end = 0;
-  *why = kWhyDeclined;  // (a frame that does not parse is the host parser's to report)
-  if (!dirsig::frame(index, len, &h, &body_off, &body_end, &err)) return kHostFlow;
-  ts.add(index, len, body_off, body_end);
-  bool fits = device_takes(len);
-  uint64_t fwork_bytes = dev::files_work_bytes(len);
-  for (size_t j = 0; j < nsrc; ++j) {
-    Text t;
-    dirsig::Header sh;
-    std::string serr;
-    if (!src_index[j] || !dirsig::frame(src_index[j], src_len[j], &sh, &body_off, &body_end, &serr) ||
-        sh.hash != h.hash || sh.block_size != h.block_size)
-      continue;  // skipped, and not uploaded
-    ts.add(src_index[j], src_len[j], body_off, body_end);
-    t.ordinal = (uint32_t)j;
-    t.fwork_off = fwork_bytes;
-    fwork_bytes += dev::files_work_bytes(src_len[j]);
-    fits = fits && device_takes(src_len[j]);
-    tx.push_back(t);
-  }
-  *why = kWhyLimit;
-  if (!fits) return kHostFlow;
-  const uint64_t bs = h.block_size, text_bytes = ts.text_bytes;
-  const size_t nt = tx.size(), used = nt - 1;
-  std::vector<uint64_t> f_res(files::kResFields * nt);
-  std::vector<uint64_t> src_first(used + 1);
+  FileStage st;
   std::vector<uint32_t> cand;
   uint64_t m_res[files::kResFields] = {0, 0, 0, 0};
   TraceEvents<5> mev;
+  int rc;
+  if ((rc = st.frame(index, len, src_index, src_len, nsrc, why))) return rc;
 
   DeviceCall c(ctx);
   hipStream_t s = c.s;
-  uint8_t* d_fwork = nullptr;
-  uint64_t* d_fres = nullptr;
-  int rc;
-  // (the text buffer with 16 bytes to spare, as cir_index_files_dev's callers give it)
-  if ((rc = c.begin()) || (rc = ts.count(c, bs, 16, trace))) return rc;
-  const auto t1 = ts.t_bufs, t2 = ts.t_up, t3 = ts.t_counted;
-  uint8_t* const d_text = ts.d_text;
-  uint64_t pool_files = 0, pool_blocks = 0;
-  for (size_t k = 0; k < nt; ++k) {
-    const uint64_t* r = ts.item[k].cnt;
-    if (r[0] != CIR_INDEX_OK) {
-      *why = kWhyDeclined;
-      return kHostFlow;
-    }
-    tx[k].nfiles = r[1];
-    tx[k].nblk = r[3];
-    if (k) {
-      src_first[k - 1] = pool_files;
-      pool_files += r[1];
-      pool_blocks += r[3];
-    }
-  }
-  src_first[used] = pool_files;
-  const uint64_t need_files = tx[0].nfiles, need_blocks = tx[0].nblk;
-  if (pool_files > files::kMaxPoolFiles || need_files > files::kMaxNeedFiles ||
-      pool_blocks > 0xFFFFFFFFull)
-    return kHostFlow;  // (*why is kWhyLimit)
-  // the join's buffers; the digests and the records are written straight into them.
-  // The record kernels' small scratch and results are allocated here and not
-  // in front of the texts: with them first, case (c) of DESIGN 4.5h was 0.15 to
-  // 0.3 ms slower (profiles/index_calls/ab.json, alloc_order).
-  uint8_t* d_ndig = nullptr;
-  uint8_t* d_pdig = nullptr;
-  uint64_t* d_nrec = nullptr;
-  uint64_t* d_prec = nullptr;
-  uint64_t* d_first = nullptr;
+  if ((rc = c.begin()) || (rc = st.count(c, trace, why))) return rc;
+  const auto t1 = st.ts.t_bufs, t2 = st.ts.t_up, t3 = st.ts.t_counted;
+  const uint64_t need_files = st.need_files(), pool_files = st.pool_files;
+  const size_t used = st.used;
   uint64_t* d_mwork = nullptr;
   uint32_t* d_csrc = nullptr;
   uint64_t* d_cfile = nullptr;
   uint64_t* d_mres = nullptr;
-  if ((rc = c.alloc(&d_fwork, fwork_bytes)) || (rc = c.alloc(&d_fres, 8 * f_res.size())) ||
-      (rc = c.alloc(&d_ndig, 32 * need_blocks + 32)) ||
-      (rc = c.alloc(&d_pdig, 32 * pool_blocks + 32)) ||
-      (rc = c.alloc(&d_nrec, 32 * need_files)) || (rc = c.alloc(&d_prec, 32 * pool_files)) ||
-      (rc = c.alloc(&d_first, 8 * (used + 1))) ||
+  if ((rc = st.alloc(c)) ||
       (rc = c.alloc(&d_mwork, dev::match_files_work_bytes(need_files, pool_files))) ||
       (rc = c.alloc(&d_csrc, 4 * need_files)) || (rc = c.alloc(&d_cfile, 8 * need_files)) ||
       (rc = c.alloc(&d_mres, sizeof m_res)))
     return rc;
   if (trace && (rc = mev.create())) return rc;
-  CIR_HIP(hipMemcpyAsync(d_first, src_first.data(), 8 * (used + 1), hipMemcpyHostToDevice, s));
-  uint64_t file_at = 0, block_at = 0;  // pool ordinals of the next source's first file and block
-  for (size_t k = 0; k < nt; ++k) {
-    const Text& t = tx[k];
-    const TextSet::Item& it = ts.item[k];
-    uint8_t* dig = k ? d_pdig + 32 * block_at : d_ndig;
-    uint64_t* rec = k ? d_prec + files::kFileWords * file_at : d_nrec;
-    if ((rc = ts.emit(c, k, dig, t.nblk))) return rc;
-    CIR_HIP(dev::launch_index_files(d_text + it.text_off, it.len, it.body_off, it.body_end, bs,
-                                    it.text_off, k ? block_at : 0, rec, t.nfiles,
-                                    (uint64_t*)(d_fwork + t.fwork_off),
-                                    d_fres + files::kResFields * k, s, false));
-    if (k) {
-      file_at += t.nfiles;
-      block_at += t.nblk;
-    }
-  }
+  if ((rc = st.emit(c))) return rc;
   if (trace) CIR_HIP(hipStreamSynchronize(s));
   const auto t4 = Clock::now();
-  const dev::FilesSide need{d_text, text_bytes, d_nrec, need_files, d_ndig, need_blocks};
-  const dev::FilesSide pool{d_text, text_bytes, d_prec, pool_files, d_pdig, pool_blocks};
-  CIR_HIP(dev::launch_match_files(need, pool, d_first, used, bs, nullptr, draw_seed(), d_mwork,
-                                  d_csrc, d_cfile, d_mres, s, trace ? mev.ev : nullptr));
+  CIR_HIP(dev::launch_match_files(st.need(), st.pool(), st.d_first, used, st.h.block_size, nullptr,
+                                  draw_seed(), d_mwork, d_csrc, d_cfile, d_mres, s,
+                                  trace ? mev.ev : nullptr));
   cand.resize(need_files);
-  CIR_HIP(hipMemcpyAsync(f_res.data(), d_fres, 8 * f_res.size(), hipMemcpyDeviceToHost, s));
+  if ((rc = st.queue_verdicts(c))) return rc;
   CIR_HIP(hipMemcpyAsync(m_res, d_mres, sizeof m_res, hipMemcpyDeviceToHost, s));
   if (need_files)
     CIR_HIP(hipMemcpyAsync(cand.data(), d_csrc, 4 * need_files, hipMemcpyDeviceToHost, s));
-  if ((rc = ts.finish(c, false))) return rc;  // (the run tables stay on the device)
+  if ((rc = st.ts.finish(c, false))) return rc;  // (the run tables stay on the device)
   const auto t5 = Clock::now();
-  // every verdict is in: a bad token shows only after the decode pass
-  for (size_t k = 0; k < nt; ++k) {
-    const uint64_t* fr = f_res.data() + files::kResFields * k;
-    if (ts.status(k) != CIR_INDEX_OK || fr[0] != CIR_INDEX_OK ||
-        fr[1] != tx[k].nfiles || fr[2] != tx[k].nblk) {
-      *why = kWhyDeclined;
-      return kHostFlow;
-    }
-  }
-  if (m_res[0] != files::kOk) {
-    *why = kWhyCollision;
-    return kHostFlow;
-  }
+  if ((rc = st.verdicts_ok(m_res[0] == files::kOk, why))) return rc;
   const uint64_t n = m_res[1];
   uint64_t* fo = nullptr;
   uint32_t* so = nullptr;
@@ -270,7 +157,7 @@ int file_sources_dev(cir_ctx* ctx, const uint8_t* index, size_t len,
       for (uint64_t i = 0; i < need_files; ++i)
         if (cand[i] != files::kNoSrc && cand[i] < used && at < n) {
           fo[at] = i;
-          so[at++] = tx[1 + cand[i]].ordinal;
+          so[at++] = st.tx[1 + cand[i]].ordinal;
         }
     if (!fo || !so || at != n) {
       free(fo);
@@ -289,7 +176,7 @@ int file_sources_dev(cir_ctx* ctx, const uint8_t* index, size_t len,
   o.stats[4] = used;
   o.stats[5] = dev::join_table_slots(pool_files);
   o.stats[6] = 1;
-  o.stats[7] = kWhyNone;
+  o.stats[7] = 0;
   if (trace) {
     const float lap[4] = {mev.lap(0), mev.lap(1), mev.lap(2), mev.lap(3)};
     fprintf(stderr,
@@ -298,9 +185,9 @@ int file_sources_dev(cir_ctx* ctx, const uint8_t* index, size_t len,
             "kernels %.2f ms, emit kernels %.2f ms, fold kernels %.3f ms, build kernel %.3f ms, "
             "probe kernel %.3f ms, verify kernel %.3f ms, join and download %.2f ms, compact %.2f "
             "ms; %llu candidates\n",
-            (unsigned long long)need_files, (unsigned long long)need_blocks,
-            (unsigned long long)pool_files, (unsigned long long)pool_blocks, used,
-            ms_between(t0, t1), ms_between(t1, t2), (unsigned long long)text_bytes,
+            (unsigned long long)need_files, (unsigned long long)st.need_blocks(),
+            (unsigned long long)pool_files, (unsigned long long)st.pool_blocks, used,
+            ms_between(t0, t1), ms_between(t1, t2), (unsigned long long)st.ts.text_bytes,
             ms_between(t2, t3), ms_between(t3, t4), lap[0], lap[1], lap[2], lap[3],
             ms_between(t4, t5), ms_between(t5, Clock::now()), (unsigned long long)n);
   }
@@ -319,10 +206,10 @@ int file_sources_impl(cir_ctx* ctx, const uint8_t* index, size_t len,
   if (o.nskipped_out) *o.nskipped_out = 0;
   for (int i = 0; i < CIR_FILE_SOURCES_STATS_FIELDS; ++i) o.stats[i] = 0;
   const bool trace = trace_enabled();
-  uint64_t why = kWhyNone;
+  uint64_t why = 0;
   if (ctx) {
     if (match_on_host()) {
-      why = kWhyEnv;
+      why = CIR_FILE_WHY_ENV;
     } else {
       const int rc = file_sources_dev(ctx, index, len, src_index, src_len, nsrc, o, trace, &why);
       if (rc != kHostFlow) return rc;  // (nothing was reported yet)

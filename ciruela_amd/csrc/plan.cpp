@@ -13,12 +13,12 @@
 // once: the four joins run back to back in device memory, with plan.hip's two
 // kernels between them.
 //
-// The device flow goes through devcall.hpp like copies.cpp's: TextSet frames
+// The device flow goes through devcall.hpp like copies.cpp's: FileStage frames
 // and uploads the texts, the count pass (first synchronise), the emit and
-// decode passes into shared digest and record buffers, then launch_match_files,
-// k_plan_links, launch_match_copies, k_plan_want; the run tables, the verdicts
-// and the candidates come down (second synchronise); the host packs the run
-// tables; launch_join, launch_extent_map, launch_repeat_join and
+// decode passes into shared digest and record buffers; then, here,
+// launch_match_files, k_plan_links, launch_match_copies, k_plan_want; the run
+// tables, the verdicts and the candidates come down (second synchronise); the
+// host packs the run tables; launch_join, launch_extent_map, launch_repeat_join and
 // launch_extent_map again run behind one upload (third synchronise, for the two
 // extent counts), and two extent tails bring the records down (fourth and
 // fifth).  Whatever the device cannot answer exactly is answered by the host
@@ -31,7 +31,6 @@
 #include <vector>
 
 #include "copies.hpp"
-#include "decode.hpp"
 #include "devcall.hpp"
 #include "dirsig.hpp"
 #include "files.hpp"
@@ -93,8 +92,6 @@ int plan_want_dev_impl(const uint64_t* d_need_runs, uint64_t n_need_runs, uint64
 
 // ---- the whole call ------------------------------------------------------------
 
-constexpr int kHostFlow = 2;  // (no CIR_* code is positive) the host composition decides this call
-
 bool plan_on_host() {  // CIR_PLAN=host, read per call
   const char* v = getenv("CIR_PLAN");
   return v && strcmp(v, "host") == 0;
@@ -149,58 +146,16 @@ struct HostSiblings {
   }
 };
 
-template <class T>
-bool dup(const T* p, size_t n, T** out) {
-  *out = n ? (T*)malloc(n * sizeof(T)) : nullptr;
-  if (*out) memcpy(*out, p, n * sizeof(T));
-  return !n || *out != nullptr;
-}
-
-// One text of the call on the device, beside its TextSet item.
-struct Text {
-  uint32_t ordinal = 0;  // the source's, as the caller counts
-  uint64_t fwork_off = 0;
-  uint64_t nfiles = 0, nblk = 0;
-};
+using copies::dup;
 
 // With a context: on its first device, under that device's lock.  Returns a
-// CIR_* code (with *r dropped on failure), or kHostFlow with *why set and
-// nothing reported.
+// CIR_* code (with *r dropped on failure), or kHostFlow (devcall.hpp: here the
+// host composition decides the call) with *why set and nothing reported.
 int fetch_plan_dev(cir_ctx* ctx, const Inputs& in, plan::Result* r, bool trace, uint64_t* why) {
   if (ctx->devs.empty()) return fail(CIR_EINVAL, "context without a device");
-  if (in.nsrc > 0xFFFFFFFEull) return fail(CIR_EINVAL, "too many sources");
   const auto t0 = Clock::now();
-  dirsig::Header h;
-  std::string err;
   // host memory that asynchronous copies read or write: declared before the call
-  TextSet ts;  // the new index, then the sources that take part
-  std::vector<Text> tx(1);  // (tx[k] goes with ts.item[k])
-  size_t body_off = 0, body_end = 0;
-  *why = CIR_FILE_WHY_DECLINED;  // (a frame that does not parse is the host parser's to report)
-  if (!dirsig::frame(in.index, in.len, &h, &body_off, &body_end, &err)) return kHostFlow;
-  ts.add(in.index, in.len, body_off, body_end);
-  bool fits = device_takes(in.len);
-  uint64_t fwork_bytes = dev::files_work_bytes(in.len);
-  for (size_t j = 0; j < in.nsrc; ++j) {
-    Text t;
-    dirsig::Header sh;
-    std::string serr;
-    if (!in.src_index[j] ||
-        !dirsig::frame(in.src_index[j], in.src_len[j], &sh, &body_off, &body_end, &serr) ||
-        sh.hash != h.hash || sh.block_size != h.block_size)
-      continue;  // skipped, and not uploaded
-    ts.add(in.src_index[j], in.src_len[j], body_off, body_end);
-    t.ordinal = (uint32_t)j;
-    t.fwork_off = fwork_bytes;
-    fwork_bytes += dev::files_work_bytes(in.src_len[j]);
-    fits = fits && device_takes(in.src_len[j]);
-    tx.push_back(t);
-  }
-  *why = CIR_FILE_WHY_LIMIT;
-  if (!fits) return kHostFlow;
-  const uint64_t bs = h.block_size, text_bytes = ts.text_bytes;
-  const size_t nt = tx.size(), used = nt - 1;
-  std::vector<uint64_t> f_res(files::kResFields * nt), src_first(used + 1);
+  FileStage stage;
   std::vector<uint32_t> c1src, c2src;
   std::vector<uint64_t> c2file, c2place, tabs;
   std::vector<files::Rec> nrec;
@@ -210,49 +165,28 @@ int fetch_plan_dev(cir_ctx* ctx, const Inputs& in, plan::Result* r, bool trace, 
   uint64_t x2_res[extents::kResFields] = {0, 0, 0, 0, 0, 0};
   TraceEvents<5> ev;   // around the two file joins and the glue behind each
   TraceEvents<5> xev;  // around the two block joins and their extent maps
+  int rc;
+  if ((rc = stage.frame(in.index, in.len, in.src_index, in.src_len, in.nsrc, why))) return rc;
 
   DeviceCall c(ctx);
   hipStream_t s = c.s;
-  int rc;
-  // (the text buffer with 16 bytes to spare, as cir_index_files_dev's callers give it)
-  if ((rc = c.begin()) || (rc = ts.count(c, bs, 16, trace))) return rc;
+  if ((rc = c.begin()) || (rc = stage.count(c, trace, why))) return rc;
+  const TextSet& ts = stage.ts;
+  const std::vector<FileStage::Text>& tx = stage.tx;
   const auto t1 = ts.t_bufs, t2 = ts.t_up, t3 = ts.t_counted;
-  uint8_t* const d_text = ts.d_text;
-  uint64_t pool_files = 0, pool_blocks = 0;
-  for (size_t k = 0; k < nt; ++k) {
-    const uint64_t* cnt = ts.item[k].cnt;
-    if (cnt[0] != CIR_INDEX_OK) {
-      *why = CIR_FILE_WHY_DECLINED;
-      return kHostFlow;
-    }
-    tx[k].nfiles = cnt[1];
-    tx[k].nblk = cnt[3];
-    if (k) {
-      src_first[k - 1] = pool_files;
-      pool_files += cnt[1];
-      pool_blocks += cnt[3];
-    }
-  }
-  src_first[used] = pool_files;
-  const uint64_t need_files = tx[0].nfiles, n = tx[0].nblk, need_runs = ts.item[0].cnt[2];
+  const uint64_t bs = stage.h.block_size, pool_files = stage.pool_files;
+  const uint64_t pool_blocks = stage.pool_blocks, need_files = stage.need_files();
+  const uint64_t n = stage.need_blocks(), need_runs = ts.item[0].cnt[2];
+  const size_t nt = tx.size(), used = stage.used;
   const uint64_t file_words = (need_files + 63) / 64, nwords = (n + 63) / 64;
-  // (the block joins' limits are the narrower ones: the pool's ordinals are
-  // u32 below 2^31, and the repeats' pool is the need list twice)
-  if (pool_files > files::kMaxPoolFiles || need_files > files::kMaxNeedFiles ||
-      !sources::pool_count_ok(pool_blocks) || n > repeats::kMaxBlocks)
+  // (the block joins' limits are narrower than the stage's: the pool's ordinals
+  // are u32 below 2^31, and the repeats' pool is the need list twice)
+  if (!sources::pool_count_ok(pool_blocks) || n > repeats::kMaxBlocks)
     return kHostFlow;  // (*why is CIR_FILE_WHY_LIMIT)
   if (n == 0) {  // nothing to join block by block: the composition ends in its host rules
     *why = CIR_PLAN_WHY_EMPTY;
     return kHostFlow;
   }
-  // the file joins' buffers; the digests and the records are written straight into them
-  uint8_t* d_fwork = nullptr;
-  uint64_t* d_fres = nullptr;
-  uint8_t* d_ndig = nullptr;
-  uint8_t* d_pdig = nullptr;
-  uint64_t* d_nrec = nullptr;
-  uint64_t* d_prec = nullptr;
-  uint64_t* d_first = nullptr;
   uint64_t* d_deny = nullptr;
   uint64_t* d_have = nullptr;
   uint64_t* d_skip = nullptr;
@@ -266,11 +200,7 @@ int fetch_plan_dev(cir_ctx* ctx, const Inputs& in, plan::Result* r, bool trace, 
   uint64_t* d_want = nullptr;
   constexpr size_t kSmall = 2 * files::kResFields + plan::kLinksResFields + plan::kWantResFields +
                             2 * extents::kResFields;
-  if ((rc = c.alloc(&d_fwork, fwork_bytes)) || (rc = c.alloc(&d_fres, 8 * f_res.size())) ||
-      (rc = c.alloc(&d_ndig, 32 * n + 32)) || (rc = c.alloc(&d_pdig, 32 * pool_blocks + 32)) ||
-      (rc = c.alloc(&d_nrec, 32 * need_files)) || (rc = c.alloc(&d_prec, 32 * pool_files)) ||
-      (rc = c.alloc(&d_first, 8 * (used + 1))) ||
-      (in.deny && (rc = c.alloc(&d_deny, 8 * file_words))) ||
+  if ((rc = stage.alloc(c)) || (in.deny && (rc = c.alloc(&d_deny, 8 * file_words))) ||
       (in.have && (rc = c.alloc(&d_have, 8 * nwords))) || (rc = c.alloc(&d_skip, 8 * file_words)) ||
       (rc = c.alloc(&d_mwork, dev::match_files_work_bytes(need_files, pool_files))) ||
       (rc = c.alloc(&d_c1src, 4 * need_files)) || (rc = c.alloc(&d_c1file, 8 * need_files)) ||
@@ -285,31 +215,17 @@ int fetch_plan_dev(cir_ctx* ctx, const Inputs& in, plan::Result* r, bool trace, 
   uint64_t* const d_x1res = d_wres + plan::kWantResFields;
   uint64_t* const d_x2res = d_x1res + extents::kResFields;
   if (trace && ((rc = ev.create()) || (rc = xev.create()))) return rc;
-  CIR_HIP(hipMemcpyAsync(d_first, src_first.data(), 8 * (used + 1), hipMemcpyHostToDevice, s));
+  // (both bitmaps go up in front of the stage's emit pass, as they always did;
+  // since the stage, also in front of its src_first: DESIGN 4.5l)
   if (d_deny && file_words)
     CIR_HIP(hipMemcpyAsync(d_deny, in.deny, 8 * file_words, hipMemcpyHostToDevice, s));
   if (d_have) CIR_HIP(hipMemcpyAsync(d_have, in.have, 8 * nwords, hipMemcpyHostToDevice, s));
-  uint64_t file_at = 0, block_at = 0;  // pool ordinals of the next source's first file and block
-  for (size_t k = 0; k < nt; ++k) {
-    const Text& t = tx[k];
-    const TextSet::Item& it = ts.item[k];
-    uint8_t* dig = k ? d_pdig + 32 * block_at : d_ndig;
-    uint64_t* rec = k ? d_prec + files::kFileWords * file_at : d_nrec;
-    if ((rc = ts.emit(c, k, dig, t.nblk))) return rc;
-    CIR_HIP(dev::launch_index_files(d_text + it.text_off, it.len, it.body_off, it.body_end, bs,
-                                    it.text_off, k ? block_at : 0, rec, t.nfiles,
-                                    (uint64_t*)(d_fwork + t.fwork_off),
-                                    d_fres + files::kResFields * k, s, false));
-    if (k) {
-      file_at += t.nfiles;
-      block_at += t.nblk;
-    }
-  }
+  if ((rc = stage.emit(c))) return rc;
   if (trace) CIR_HIP(hipStreamSynchronize(s));
   const auto t4 = Clock::now();
   // steps 1 to 3: the two file joins and the glue, back to back
-  const dev::FilesSide need{d_text, text_bytes, d_nrec, need_files, d_ndig, n};
-  const dev::FilesSide pool{d_text, text_bytes, d_prec, pool_files, d_pdig, pool_blocks};
+  const dev::FilesSide need = stage.need(), pool = stage.pool();
+  uint64_t* const d_first = stage.d_first;
   if (trace) CIR_HIP(hipEventRecord(ev.ev[0], s));
   CIR_HIP(dev::launch_match_files(need, pool, d_first, used, bs, nullptr, draw_seed(), d_mwork,
                                   d_c1src, d_c1file, d_m1res, s));
@@ -329,7 +245,7 @@ int fetch_plan_dev(cir_ctx* ctx, const Inputs& in, plan::Result* r, bool trace, 
   c2file.resize(need_files);
   c2place.resize(copies::kPlaceWords * need_files);
   nrec.resize(need_files);
-  CIR_HIP(hipMemcpyAsync(f_res.data(), d_fres, 8 * f_res.size(), hipMemcpyDeviceToHost, s));
+  if ((rc = stage.queue_verdicts(c))) return rc;
   CIR_HIP(hipMemcpyAsync(m1_res, d_m1res, sizeof m1_res, hipMemcpyDeviceToHost, s));
   CIR_HIP(hipMemcpyAsync(m2_res, d_m2res, sizeof m2_res, hipMemcpyDeviceToHost, s));
   CIR_HIP(hipMemcpyAsync(l_res, d_lres, sizeof l_res, hipMemcpyDeviceToHost, s));
@@ -340,23 +256,12 @@ int fetch_plan_dev(cir_ctx* ctx, const Inputs& in, plan::Result* r, bool trace, 
     CIR_HIP(hipMemcpyAsync(c2file.data(), d_c2file, 8 * need_files, hipMemcpyDeviceToHost, s));
     CIR_HIP(hipMemcpyAsync(c2place.data(), d_c2place, 16 * need_files, hipMemcpyDeviceToHost, s));
     // (the need records: where each entry's own path stands, for the copies' stats[9])
-    CIR_HIP(hipMemcpyAsync(nrec.data(), d_nrec, 32 * need_files, hipMemcpyDeviceToHost, s));
+    CIR_HIP(hipMemcpyAsync(nrec.data(), stage.d_nrec, 32 * need_files, hipMemcpyDeviceToHost, s));
   }
-  if ((rc = ts.finish(c, true))) return rc;  // (with the run tables: the extent maps need them)
+  // (with the run tables: the extent maps need them)
+  if ((rc = stage.ts.finish(c, true))) return rc;
   const auto t5 = Clock::now();
-  // every verdict is in: a bad token shows only after the decode pass
-  for (size_t k = 0; k < nt; ++k) {
-    const uint64_t* fr = f_res.data() + files::kResFields * k;
-    if (ts.status(k) != CIR_INDEX_OK || fr[0] != CIR_INDEX_OK || fr[1] != tx[k].nfiles ||
-        fr[2] != tx[k].nblk) {
-      *why = CIR_FILE_WHY_DECLINED;
-      return kHostFlow;
-    }
-  }
-  if (m1_res[0] != files::kOk || m2_res[0] != files::kOk) {
-    *why = CIR_FILE_WHY_COLLISION;
-    return kHostFlow;
-  }
+  if ((rc = stage.verdicts_ok(m1_res[0] == files::kOk && m2_res[0] == files::kOk, why))) return rc;
   // steps 4 and 5.  The run tables: the need's twice (its first copy is the need
   // table of both maps, both copies the pool of the repeats), then the pool's.
   sources::BlockList nl, pl;
@@ -400,15 +305,15 @@ int fetch_plan_dev(cir_ctx* ctx, const Inputs& in, plan::Result* r, bool trace, 
   const dev::ExtentArgs a1{d_match1, n, d_nruns, nr, d_pruns, pr, pool_blocks, bs, d_want};
   const dev::ExtentArgs a2{d_match2, n, d_nruns, nr, d_nruns, 2 * nr, 2 * n, bs, d_fetch1};
   if (trace) CIR_HIP(hipEventRecord(xev.ev[0], s));
-  CIR_HIP(dev::launch_join(d_ndig, n, d_pdig, pool_blocks, d_table, slots1, draw_seed(), d_match1,
-                           d_match1 + n, s));
+  CIR_HIP(dev::launch_join(stage.d_ndig, n, stage.d_pdig, pool_blocks, d_table, slots1, draw_seed(),
+                           d_match1, d_match1 + n, s));
   if (trace) CIR_HIP(hipEventRecord(xev.ev[1], s));
   // (no cap: the count decides the allocation, not the other way round)
   CIR_HIP(dev::launch_extent_map(a1, nullptr, nullptr, nullptr, d_fetch1, ~0ull, d_xwork1, d_x1res,
                                  s));
   if (trace) CIR_HIP(hipEventRecord(xev.ev[2], s));
-  CIR_HIP(dev::launch_repeat_join(d_ndig, n, d_fetch1, d_present, d_table, slots2, draw_seed(),
-                                  d_match2, d_match2 + n, s));
+  CIR_HIP(dev::launch_repeat_join(stage.d_ndig, n, d_fetch1, d_present, d_table, slots2,
+                                  draw_seed(), d_match2, d_match2 + n, s));
   if (trace) CIR_HIP(hipEventRecord(xev.ev[3], s));
   CIR_HIP(dev::launch_extent_map(a2, nullptr, nullptr, nullptr, d_fetch2, ~0ull, d_xwork2, d_x2res,
                                  s));
@@ -438,41 +343,28 @@ int fetch_plan_dev(cir_ctx* ctx, const Inputs& in, plan::Result* r, bool trace, 
   const auto t8 = Clock::now();
   // compact the candidates, and decode each content candidate's path from the
   // source text held here
-  std::vector<uint64_t> l1file, l2file, l2sfile, l2off{0};
-  std::vector<uint32_t> l1src, l2src;
-  std::string paths;
-  uint64_t left_out = 0, same = 0;
-  const TextSet::Item& ni = ts.item[0];
+  std::vector<uint64_t> l1file;
+  std::vector<uint32_t> l1src;
+  uint64_t left_out = 0;  // (the skip bitmap is the device's: deny | candidate kept)
   for (uint64_t i = 0; i < need_files; ++i) {
     left_out += plan::skip_bit(in.deny, i, c1src[i]);
-    if (c1src[i] != files::kNoSrc) {
-      if (c1src[i] >= used) return drop(fail(CIR_EHIP, "candidate source out of range"));
-      l1file.push_back(i);
-      l1src.push_back(tx[1 + c1src[i]].ordinal);
-    }
-    if (c2src[i] == files::kNoSrc) continue;
-    if (c2src[i] >= used) return drop(fail(CIR_EHIP, "candidate source out of range"));
-    const TextSet::Item& it = ts.item[1 + c2src[i]];
-    const uint64_t name = c2place[2 * i] - it.text_off, dir = c2place[2 * i + 1] - it.text_off;
-    const uint64_t nname = nrec[i].name_off - ni.text_off, ndir = nrec[i].dir_off - ni.text_off;
-    if (name >= it.len || dir >= it.len || nname >= ni.len || ndir >= ni.len ||
-        c2file[i] >= tx[1 + c2src[i]].nfiles)
-      return drop(fail(CIR_EHIP, "candidate place out of range"));
-    decode_path(it.p, it.len, dir, name, &paths);
-    l2file.push_back(i);
-    l2src.push_back(tx[1 + c2src[i]].ordinal);
-    l2sfile.push_back(c2file[i]);
-    l2off.push_back(paths.size());
-    same += files::same_path(ni.p, ni.len, ndir, nname, it.p, it.len, dir, name);
+    if (c1src[i] == files::kNoSrc) continue;
+    if (c1src[i] >= used) return drop(fail(CIR_EHIP, "candidate source out of range"));
+    l1file.push_back(i);
+    l1src.push_back(tx[1 + c1src[i]].ordinal);
   }
-  if (l1file.size() != l_res[0] || l_res[0] + l_res[1] != m1_res[1] || l2file.size() != m2_res[1])
+  copies::Found l2;
+  switch (copies::compact(c2src.data(), c2file.data(), c2place.data(), nrec.data(), need_files,
+                          stage.placed().data(), used, nullptr, &l2)) {
+    case copies::kBadSource: return drop(fail(CIR_EHIP, "candidate source out of range"));
+    case copies::kBadPlace: return drop(fail(CIR_EHIP, "candidate place out of range"));
+    case copies::kCompacted: break;
+  }
+  const size_t n1 = l1file.size(), n2 = l2.file.size();
+  if (n1 != l_res[0] || l_res[0] + l_res[1] != m1_res[1] || n2 != m2_res[1])
     return drop(fail(CIR_EHIP, "candidate count mismatch"));
-  const size_t n1 = l1file.size(), n2 = l2file.size();
   if (!dup(l1file.data(), n1, &r->link_file) || !dup(l1src.data(), n1, &r->link_src) ||
-      !dup(l2file.data(), n2, &r->copy_file) || !dup(l2src.data(), n2, &r->copy_src) ||
-      !dup(l2sfile.data(), n2, &r->copy_src_file) ||
-      (n2 && (!dup(l2off.data(), n2 + 1, &r->copy_path_off) ||
-              !dup((const uint8_t*)paths.data(), paths.size(), &r->copy_paths))))
+      !l2.give(&r->copy_file, &r->copy_src, &r->copy_src_file, &r->copy_path_off, &r->copy_paths))
     return drop(fail(CIR_ENOMEM, "malloc"));
   r->nlinks = n1;
   r->ncopies = n2;
@@ -494,7 +386,7 @@ int fetch_plan_dev(cir_ctx* ctx, const Inputs& in, plan::Result* r, bool trace, 
   st[5] = dev::join_table_slots(pool_files);
   st[6] = 1;
   st[8] = left_out;
-  st[9] = same;
+  st[9] = l2.same;
   st = r->stats + plan::kStatExtents;
   st[0] = x1_res[1];
   st[1] = x1_res[2];

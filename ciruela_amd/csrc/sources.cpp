@@ -251,8 +251,6 @@ struct Text {
 
 // What an attempt returns besides a CIR_* code (none of those is positive).
 constexpr int kRetry = 1;     // again, with more texts on the host
-constexpr int kHostFlow = 2;  // the host flow decides this call
-
 struct DevLaps {
   double frame = 0, text_upload = 0, count = 0, host_parse = 0, decode = 0, runs_download = 0;
   double upload = 0, build = 0, probe = 0, download = 0, map = 0;

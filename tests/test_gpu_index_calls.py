@@ -1,14 +1,17 @@
-"""The five whole-call entry points over index texts on one device flow
+"""The whole-call entry points over index texts on one device flow
 (ciruela_amd/csrc/devcall.hpp): cir_block_sources, cir_block_extents,
-cir_block_repeats, cir_file_sources and cir_index_digests.
+cir_block_repeats, cir_file_sources, cir_index_digests, cir_file_copies and
+cir_fetch_plan.
 
 One child process under CIR_TRACE=1 makes one lazy-staging context and runs
 every call on every path -- with the context, under CIR_SOURCES_PARSE=host,
 CIR_SOURCES_MAP=host and =device, CIR_LINKS_MATCH=host, and with ctx = NULL --
-on the smallest shared cases.  Per path, the trace lines with every number
+on the smallest shared cases (cir_fetch_plan: with the context, under
+CIR_PLAN=host and with ctx = NULL).  Per path, the trace lines with every number
 replaced by N equal literals written from the format strings, and the parsers
 the bench tools read those lines with (tools/block_sources_bench.py,
-tools/block_repeats_bench.py, tools/file_sources_bench.py) find every lap they
+tools/block_repeats_bench.py, tools/file_sources_bench.py,
+tools/file_copies_bench.py, tools/fetch_plan_bench.py) find every lap they
 name; the results of all paths of a call are equal.
 
 And ctx against NULL on a set of texts on which the two-pass parse's offsets,
@@ -25,7 +28,9 @@ import sys
 
 import pytest
 
+import copies_restate
 import files_cases
+import plan_restate
 import sources_cases
 from sources_cases import BS, _emit, _file
 
@@ -35,17 +40,35 @@ _CHILD = r"""
 import json, os, sys
 sys.path[:0] = [sys.argv[1], sys.argv[1] + "/tests", sys.argv[1] + "/oracle"]
 import ciruela_amd as ca
-import files_cases, repeats_cases, sources_cases
+import copies_cases, files_cases, plan_cases, plan_restate, repeats_cases, sources_cases
 _, index, sources, _, _ = next(c for c in sources_cases.cases() if c[0] == "skipped_sources")
 _, rep, _, _, _ = next(c for c in repeats_cases.cases() if c[0] == "duplicated_file")
 _, fnew, fsrc = next(c for c in files_cases.families() if c[0] == "order_12")
+# (moved files, a skip bitmap; and a source that is skipped, in front of the one that counts)
+_, cnew, csrc, cskip = next(c for c in copies_cases.families() if c[0] == "renamed_dir_unlinked")
+csrc = [b"garbage"] + csrc
+pnew, psrc = plan_cases.hand_made()
+psrc = psrc + [b"garbage"]
+pwant = plan_restate.expected(pnew, psrc)
 ctx = ca.Context(device_mask=1, staging_bytes=ca._n.CIR_STAGING_LAZY)
-SWITCHES = ("CIR_SOURCES_PARSE", "CIR_SOURCES_MAP", "CIR_LINKS_MATCH")
+SWITCHES = ("CIR_SOURCES_PARSE", "CIR_SOURCES_MAP", "CIR_LINKS_MATCH", "CIR_PLAN")
+PATH_STATS = ("on_device", "table_slots", "why_host")
 
 def ext(r):
     return [r.nblk, [tuple(getattr(e, f) for f in ("first", "count", "need_file", "need_block",
                                                   "src", "src_file", "src_block", "bytes"))
                      for e in r.extents], list(bytes(r.fetch)), sorted(r.stats.items())]
+
+def copies(found):
+    return [[f, s, sf, path.hex()] for f, s, sf, path in found]
+
+def plan(r):
+    # (the siblings' stats without what says where they ran; the plan's own with it)
+    stats = [[k, sorted((a, b) for a, b in v.items() if a not in PATH_STATS)
+              if isinstance(v, dict) else v] for k, v in sorted(r.stats.items())]
+    return [plan_restate.same(r, pwant), r.links, copies(r.copies),
+            [list(e) for e in r.extents], [list(e) for e in r.repeats], r.fetch.hex(), r.nblk,
+            r.skipped, stats]
 
 CALLS = {
     "block_sources": lambda c: (lambda r: [r.src, r.file, r.block, r.skipped,
@@ -59,6 +82,9 @@ CALLS = {
     "index_digests": lambda c: (lambda r: [r.hash_type, r.block_size, r.digests.tobytes().hex(),
                                            r.runs.tolist(), r.nfiles])(
         ca.index_digests(index, c)),
+    "file_copies": lambda c: (lambda r: [copies(r[0]), sorted(r[1].items())])(
+        ca.file_copies(cnew, csrc, c, skip=cskip)),
+    "fetch_plan": lambda c: plan(ca.fetch_plan(pnew, psrc, c)),
 }
 out = {}
 for spec in sys.argv[2:]:
@@ -93,6 +119,23 @@ FS_DEV = ("cir file_sources: N files (N blocks) against N pool files (N blocks) 
           "N ms, join and download N ms, compact N ms; N candidates")
 FS_HOST = ("cir file_sources: N files against N pool files of N source(s), host (why N); N ms; "
            "N candidates")
+FC_DEV = ("cir file_copies: N files (N blocks) against N pool files (N blocks) of N source(s), "
+          "device; frame and buffers N ms, text upload N ms (N bytes), count kernels N ms, emit "
+          "kernels N ms, fold kernels N ms, build kernel N ms, probe kernel N ms, verify kernel "
+          "N ms, join and download N ms, compact and decode N ms; N candidates, N skipped, N at "
+          "their own path")
+FC_HOST = ("cir file_copies: N files against N pool files of N source(s), host (why N); N ms; "
+           "N candidates, N skipped, N at their own path")
+FP_DEV = ("cir fetch_plan: N files (N blocks) against N pool files (N blocks) of N source(s), "
+          "device; frame and buffers N ms, text upload N ms (N bytes), count kernels N ms, emit "
+          "kernels N ms, path join N ms, links glue N ms, content join N ms, want glue N ms, joins "
+          "and download N ms, block join N ms, extent map N ms, repeat join N ms, repeat map N ms, "
+          "tables to counts N ms, extent tail N ms, repeat tail N ms, compact and decode N ms; "
+          "N links, N copies, N extents, N repeats, N blocks to fetch")
+FP_HOST = ("cir fetch_plan: N files (N blocks) against N pool files of N source(s), host (why N); "
+           "N ms; N links, N copies, N extents, N repeats, N blocks to fetch")
+# (the host composition makes the four sibling calls with ctx = NULL, in the plan's order)
+FP_HOST_LINES = [FS_HOST, FC_HOST, BS_HOST, REP_HOST, FP_HOST]
 
 # call:ctx or null:switch -> the trace lines of that path, in order
 PATHS = {
@@ -126,8 +169,21 @@ PATHS = {
     "index_digests:ctx:CIR_SOURCES_MAP=device": [],
     "index_digests:ctx:CIR_LINKS_MATCH=host": [],
     "index_digests:null:": [],
+    "file_copies:ctx:": [FC_DEV],
+    "file_copies:ctx:CIR_SOURCES_PARSE=host": [FC_DEV],
+    "file_copies:ctx:CIR_SOURCES_MAP=host": [FC_DEV],
+    "file_copies:ctx:CIR_SOURCES_MAP=device": [FC_DEV],
+    "file_copies:ctx:CIR_LINKS_MATCH=host": [FC_HOST],
+    "file_copies:null:": [FC_HOST],
+    "fetch_plan:ctx:": [FP_DEV],
+    "fetch_plan:ctx:CIR_PLAN=host": FP_HOST_LINES,
+    "fetch_plan:null:": FP_HOST_LINES,
 }
-TRACED = ("cir block_sources:", "cir extents map", "cir block_repeats:", "cir file_sources:")
+TRACED = ("cir block_sources:", "cir extents map", "cir block_repeats:", "cir file_sources:",
+          "cir file_copies:", "cir fetch_plan:")
+# (the paths with a context that an environment switch sends to the host)
+HOST_BY_ENV = ("file_sources:ctx:CIR_LINKS_MATCH=host", "file_copies:ctx:CIR_LINKS_MATCH=host",
+               "fetch_plan:ctx:CIR_PLAN=host")
 # (what differs between the paths of one call by design: where it ran and why)
 PATH_STATS = ("on_device", "table_slots", "why_host")
 
@@ -137,7 +193,7 @@ def child():
     """({path: result}, {path: [trace line, ...]}) of the one child."""
     from conftest import ROOT
     env = dict(os.environ, CIR_TRACE="1")
-    for k in ("CIR_SOURCES_PARSE", "CIR_SOURCES_MAP", "CIR_LINKS_MATCH"):
+    for k in ("CIR_SOURCES_PARSE", "CIR_SOURCES_MAP", "CIR_LINKS_MATCH", "CIR_PLAN"):
         env.pop(k, None)
     p = subprocess.run([sys.executable, "-c", _CHILD, ROOT] + list(PATHS), env=env,
                        capture_output=True, timeout=120)
@@ -174,9 +230,9 @@ def _without_path_stats(v):
 def test_every_path_gives_the_same_answer(child):
     results, _ = child
     for call in ("block_sources", "block_extents", "block_repeats", "file_sources",
-                 "index_digests"):
+                 "index_digests", "file_copies", "fetch_plan"):
         got = {p: _without_path_stats(r) for p, r in results.items() if p.startswith(call + ":")}
-        assert len(got) == 6
+        assert len(got) == (3 if call == "fetch_plan" else 6)
         first = got[call + ":null:"]
         assert first and all(r == first for r in got.values()), call
     # (and the stats that say where it ran)
@@ -184,12 +240,20 @@ def test_every_path_gives_the_same_answer(child):
           for p, r in results.items() if not p.startswith("index_digests")}
     for p, s in st.items():
         on = s["on_device"]
-        if p.endswith(":null:") or p == "file_sources:ctx:CIR_LINKS_MATCH=host":
+        if p.endswith(":null:") or p in HOST_BY_ENV:
             assert on == 0, p
         else:
             assert on == 1, p
     assert st["file_sources:ctx:CIR_LINKS_MATCH=host"]["why_host"] == 4
     assert st["file_sources:ctx:"]["why_host"] == st["file_sources:null:"]["why_host"] == 0
+    for call in ("file_copies", "fetch_plan"):
+        for p, s in st.items():
+            if p.startswith(call + ":"):
+                assert s["why_host"] == (4 if p in HOST_BY_ENV else 0), p
+    # (every array of cir_file_copies with its path bytes was compared above; the plan also
+    # against the restatement, in the child)
+    assert results["file_copies:null:"][0] and all(
+        r[0] is True for p, r in results.items() if p.startswith("fetch_plan:"))
 
 
 def _lap_names(regex):
@@ -209,6 +273,8 @@ def test_the_bench_tools_parsers_find_their_laps(child):
     try:
         import block_repeats_bench
         import block_sources_bench
+        import fetch_plan_bench
+        import file_copies_bench
         import file_sources_bench
     finally:
         sys.path.remove(os.path.join(ROOT, "tools"))
@@ -230,10 +296,12 @@ def test_the_bench_tools_parsers_find_their_laps(child):
         got = block_sources_bench.parse_extents_trace(_twice("c v", lines[path][:1]))["c"]["v"]
         assert sorted(got) == sorted(_lap_names(block_sources_bench.XLAP)), path
         assert all(len(v) == 1 for v in got.values())
-    # cir block_repeats: and cir file_sources: on the device
+    # cir block_repeats:, cir file_sources:, cir file_copies: and cir fetch_plan: on the device
     for mod, path in ((block_repeats_bench, "block_repeats:ctx:"),
                       (block_repeats_bench, "block_repeats:ctx:CIR_SOURCES_PARSE=host"),
-                      (file_sources_bench, "file_sources:ctx:")):
+                      (file_sources_bench, "file_sources:ctx:"),
+                      (file_copies_bench, "file_copies:ctx:"),
+                      (fetch_plan_bench, "fetch_plan:ctx:")):
         got = mod.parse_trace(_twice("c", lines[path]))["c"]
         assert sorted(got) == sorted(_lap_names(mod.LAP)), path
         assert all(len(v) == 1 for v in got.values()), path
@@ -268,12 +336,13 @@ def _text_set():
 
 def _clean_set():
     """The same with three well-formed sources, so that cir_file_sources stays
-    on the device: files of `new` under their own paths in the sources."""
+    on the device: files of `new` under their own paths in the sources, and
+    one that only the third source holds, under another name."""
     rng = random.Random(20261021)
     d = [rng.randbytes(32) for _ in range(200)]
     f0, f1, f2 = (_file(b"big", 131 * BS, d[0:131]), _file(b"m", 2 * BS + 1, d[140:143]),
                   _file(b"s", BS, [d[150]]))
-    new = _emit([(b"/", [f0, f1, f2])])
+    new = _emit([(b"/", [f0, f1, f2, _file(b"moved", 2 * BS, d[160:162])])])
     srcs = [_emit([(b"/", [f0, _file(b"s", BS, [d[151]])])]), _emit([(b"/", [f1, f2])]),
             _emit([(b"/", [_file(b"another", 2 * BS, d[160:162]), f2])])]
     assert len({len(t) % 16 for t in srcs}) == 3 and len(srcs[0]) > 2 * 4096 + 65
@@ -317,3 +386,27 @@ def test_multi_tile_text_set_ctx_against_null(gpu, ctx, make):
         assert dev[1]["on_device"] == 1 and dev[1]["why_host"] == 0 and len(dev[0]) == 3
     else:
         assert dev[1]["on_device"] == 0 and dev[1]["why_host"] == gpu._n.CIR_FILE_WHY_DECLINED
+    # cir_file_copies and cir_fetch_plan: the file-level stage's offsets over the same texts
+    declined = gpu._n.CIR_FILE_WHY_DECLINED
+    dev, host = gpu.file_copies(new, srcs, ctx), gpu.file_copies(new, srcs)
+    assert dev[0] == host[0]
+    assert _same_but(dev[1], host[1], "on_device", "table_slots", "why_host")
+    plan, hplan = gpu.fetch_plan(new, srcs, ctx), gpu.fetch_plan(new, srcs)
+    for field in ("links", "copies", "extents", "repeats", "fetch", "nblk", "skipped"):
+        assert getattr(plan, field) == getattr(hplan, field), field
+    flat = lambda st: {(k, a): b for k, v in st.items()
+                       for a, b in (v.items() if isinstance(v, dict) else [("", v)])
+                       if "on_device" not in (k, a) and "table_slots" not in (k, a) and
+                       "why_host" not in (k, a)}
+    assert flat(plan.stats) == flat(hplan.stats)
+    assert hplan.stats["on_device"] == 0 and hplan.stats["why_host"] == 0
+    if make is _clean_set:
+        assert dev[1]["on_device"] == 1 and dev[1]["why_host"] == 0
+        assert dev[0] == copies_restate.expected_copies(new, srcs, None)[0]
+        assert (3, 2, 0, b"/another") in dev[0]
+        assert plan_restate.same(plan, plan_restate.expected(new, srcs), 1)
+        assert plan.stats["why_host"] == 0
+        assert len(plan.links) == 3 and plan.copies == [(3, 2, 0, b"/another")]
+    else:
+        assert dev[1]["on_device"] == 0 and dev[1]["why_host"] == declined
+        assert plan.stats["on_device"] == 0 and plan.stats["why_host"] == declined

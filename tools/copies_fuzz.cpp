@@ -1,7 +1,8 @@
 // Seeded fuzz of the content-match rule (ciruela_amd/csrc/copies.hpp: skipped,
 // home_slot, same_key, host_match -- the text the kernels k_copies_build and
 // k_copies_probe of files.hip compile) against a brute-force loop over
-// dirsig::parse's entries.  Stand-alone: build with
+// dirsig::parse's entries, and of copies::compact, the host's reading of the
+// device's answer.  Stand-alone: build with
 //   g++ -std=c++17 -O1 -g -fsanitize=address,undefined -fno-sanitize-recover=all \
 //       -D__HIP_PLATFORM_AMD__ -I/opt/rocm/include -Iinclude -Iciruela_amd/csrc \
 //       tools/copies_fuzz.cpp ciruela_amd/csrc/dirsig.cpp -o build/copies_fuzz
@@ -24,7 +25,16 @@
 //      when it belongs to a candidate;
 //   4. linkpath::split (linkpath.hpp: the paths cir_check_links_at takes) on a
 //      random byte string over '/', '.', NUL and two letters, held in a buffer of
-//      exactly its length, against a restatement that goes byte by byte.
+//      exactly its length, against a restatement that goes byte by byte;
+//   5. copies::compact (what cir_file_copies and cir_fetch_plan make of the
+//      join's downloaded answer) on the answer of 1, the texts laid out as in
+//      the device's arena and held in buffers of exactly their length: the
+//      candidates, the sources' ordinals and the decoded paths are the
+//      parser's, `same` and `left_out` counted here; then one candidate's
+//      answer spoilt -- a source ordinal >= used, a file >= the source's
+//      files, a place of either side at len, text_off - 1 or ~0 -- must give
+//      the out-of-range result, and a place at len - 1 none, with no byte
+//      read outside.
 //
 // usage: copies_fuzz [cases [seed]]
 #include <stdint.h>
@@ -32,6 +42,7 @@
 #include <stdlib.h>
 #include <string.h>
 
+#include <memory>
 #include <string>
 #include <vector>
 
@@ -51,7 +62,7 @@ static uint64_t rnd() {  // splitmix64
   return z ^ (z >> 31);
 }
 
-static uint64_t g_case, g_joins, g_cands, g_collisions, g_moved, g_paths[4];
+static uint64_t g_case, g_joins, g_cands, g_collisions, g_moved, g_paths[4], g_compact[3];
 #define CHECK(c)                                                                 \
   do {                                                                           \
     if (!(c)) {                                                                  \
@@ -144,6 +155,97 @@ static void parse_text(Text* x, uint64_t bs) {
   CHECK(c.declined == idxscan::kBad && c.files == x->files.size() && c.blocks == x->nblk);
 }
 
+// Check 5.  The answer of a join over tx (offsets relative to each text) as the
+// device would give it: every offset biased by the text's place in the arena.
+static void check_compact(const std::vector<Text>& tx, const files::Rec* nrec, const uint32_t* csrc,
+                          const uint64_t* cfile, const uint64_t* cplace, const uint64_t* skip) {
+  const size_t used = tx.size() - 1;
+  const uint64_t nf = tx[0].files.size();
+  std::vector<std::unique_ptr<Exact<uint8_t>>> bytes;
+  Exact<copies::PlacedText> pt(used + 1);
+  uint64_t at = 16 * (rnd() % 3);
+  for (size_t k = 0; k <= used; ++k) {
+    const std::string& t = tx[k].t;
+    bytes.emplace_back(new Exact<uint8_t>(t.size()));
+    memcpy(bytes[k]->p, t.data(), t.size());
+    pt.p[k] = {bytes[k]->p, t.size(), at, tx[k].files.size(), (uint32_t)(7 * k + 3)};
+    at += (t.size() + 15) & ~(uint64_t)15;
+  }
+  Exact<files::Rec> nr(nf);
+  Exact<uint32_t> cs(nf);
+  Exact<uint64_t> cf(nf), cp(copies::kPlaceWords * nf);
+  auto reset = [&] {
+    for (uint64_t i = 0; i < nf; ++i) {
+      nr.p[i] = nrec[i];
+      nr.p[i].name_off += pt.p[0].text_off;
+      nr.p[i].dir_off += pt.p[0].text_off;
+      cs.p[i] = csrc[i];
+      cf.p[i] = cfile[i];
+      for (int w = 0; w < copies::kPlaceWords; ++w)
+        cp.p[2 * i + w] = cplace[2 * i + w] +
+                          (csrc[i] == files::kNoSrc ? 0 : pt.p[1 + csrc[i]].text_off);
+    }
+  };
+  auto run = [&](copies::Found* f) {
+    return copies::compact(cs.p, cf.p, cp.p, nr.p, nf, pt.p, used, skip, f);
+  };
+  reset();
+  copies::Found f;
+  CHECK(run(&f) == copies::kCompacted);
+  uint64_t n = 0, same = 0, left = 0;
+  std::vector<uint64_t> hits;
+  for (uint64_t i = 0; i < nf; ++i) {
+    left += copies::skipped(skip, i);
+    if (csrc[i] == files::kNoSrc) continue;
+    const dirsig::Entry& want = *tx[1 + csrc[i]].files[cfile[i]];
+    CHECK(n < f.file.size() && f.file[n] == i && f.src[n] == pt.p[1 + csrc[i]].ordinal &&
+          f.src_file[n] == cfile[i]);
+    CHECK(f.paths.substr(f.path_off[n], f.path_off[n + 1] - f.path_off[n]) == want.path);
+    same += want.path == tx[0].files[i]->path;
+    hits.push_back(i);
+    ++n;
+  }
+  CHECK(f.file.size() == n && f.path_off.size() == n + 1 && f.path_off[n] == f.paths.size());
+  CHECK(f.same == same && f.left_out == left);
+  uint64_t *o_file, *o_sfile, *o_off;
+  uint32_t* o_src;
+  uint8_t* o_paths;
+  CHECK(f.give(&o_file, &o_src, &o_sfile, &o_off, &o_paths));
+  CHECK(n ? o_file && o_src && o_sfile && o_off && o_paths && o_off[n] == f.paths.size()
+          : !o_file && !o_src && !o_sfile && !o_off && !o_paths);
+  for (void* p : {(void*)o_file, (void*)o_src, (void*)o_sfile, (void*)o_off, (void*)o_paths})
+    free(p);
+  ++g_compact[0];
+  if (!n) return;
+  // one candidate's answer spoilt, one word at a time
+  const uint64_t i = hits[rnd() % n];
+  const copies::PlacedText &st = pt.p[1 + csrc[i]], &nt = pt.p[0];
+  auto spoilt = [&](copies::Compacted want) {
+    copies::Found g;
+    CHECK(run(&g) == want);
+    ++g_compact[want == copies::kCompacted ? 1 : 2];
+    reset();
+  };
+  cs.p[i] = (uint32_t)(used + rnd() % 3);
+  spoilt(copies::kBadSource);
+  cs.p[i] = 0xFFFFFFFEu;
+  spoilt(copies::kBadSource);
+  cf.p[i] = st.nfiles + rnd() % 2;
+  spoilt(copies::kBadPlace);
+  cf.p[i] = ~0ull;
+  spoilt(copies::kBadPlace);
+  uint64_t* const words[4] = {&cp.p[2 * i], &cp.p[2 * i + 1], &nr.p[i].name_off, &nr.p[i].dir_off};
+  for (int w = 0; w < 4; ++w) {
+    const copies::PlacedText& t = w < 2 ? st : nt;
+    *words[w] = t.text_off + t.len - 1;  // (the last byte: in range, whatever it decodes to)
+    spoilt(copies::kCompacted);
+    for (uint64_t bad : {t.text_off + t.len, t.text_off - 1, ~(uint64_t)0}) {
+      *words[w] = bad;
+      spoilt(copies::kBadPlace);
+    }
+  }
+}
+
 static void one_case() {
   const uint64_t bs = 1 + rnd() % 4;
   const size_t nsrc = rnd() % 5;
@@ -222,6 +324,7 @@ static void one_case() {
   CHECK(res[1] == n && res[2] == bytes);
   ++g_joins;
   g_cands += n;
+  check_compact(tx, nrec.p, csrc.p, cfile.p, cplace.p, skip.p);
   // a digest changed behind the folds: a collision exactly when a candidate holds it
   if (pool_blocks) {
     const uint64_t g = rnd() % pool_blocks;
@@ -290,11 +393,13 @@ int main(int argc, char** argv) {
   }
   fprintf(stderr,
           "copies_fuzz: %llu joins, %llu candidates (%llu at another path), %llu collisions; paths: "
-          "%llu own, %llu ok, %llu invalid, %llu with a NUL\n",
+          "%llu own, %llu ok, %llu invalid, %llu with a NUL; compact: %llu answers, %llu spoilt "
+          "in range, %llu out of range\n",
           (unsigned long long)g_joins, (unsigned long long)g_cands, (unsigned long long)g_moved,
           (unsigned long long)g_collisions, (unsigned long long)g_paths[0],
           (unsigned long long)g_paths[1], (unsigned long long)g_paths[2],
-          (unsigned long long)g_paths[3]);
+          (unsigned long long)g_paths[3], (unsigned long long)g_compact[0],
+          (unsigned long long)g_compact[1], (unsigned long long)g_compact[2]);
   printf("copies_fuzz: %llu cases ok\n", (unsigned long long)cases);
   return 0;
 }
