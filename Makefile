@@ -2,6 +2,7 @@
 #   make            -> ciruela_amd/libciruela_amd.so, bin/ciruela-index, the two
 #                      load drivers under build/, oracle
 #   make oracle     -> oracle/build/liboracle_blake2b.so (test infrastructure)
+#   make sketch_fuzz -> build/sketch_fuzz (the sketch rule under ASan + UBSan; not in `all`)
 #   make asan/tsan  -> build/host_{asan,tsan}_driver (host code under the
 #                      sanitizers; `make sanitizers` = both; not in `all`)
 HIPCC ?= /opt/rocm/bin/hipcc
@@ -20,10 +21,10 @@ CLI := bin/ciruela-index
 
 SRCS_HIP := $(CSRC)/kernels.hip $(CSRC)/order.hip $(CSRC)/join.hip \
             $(CSRC)/idxscan.hip $(CSRC)/extents.hip $(CSRC)/repeats.hip \
-            $(CSRC)/files.hip $(CSRC)/plan.hip
+            $(CSRC)/files.hip $(CSRC)/plan.hip $(CSRC)/sketch.hip
 SRCS_CPP := $(CSRC)/runtime.cpp $(CSRC)/dirsig.cpp $(CSRC)/scan.cpp $(CSRC)/check.cpp \
             $(CSRC)/links.cpp $(CSRC)/sources.cpp $(CSRC)/repeats.cpp $(CSRC)/idxscan.cpp \
-            $(CSRC)/files.cpp $(CSRC)/copies.cpp $(CSRC)/plan.cpp $(CSRC)/devcall.cpp $(CSRC)/registry.cpp $(CSRC)/blake2b_host.cpp \
+            $(CSRC)/files.cpp $(CSRC)/copies.cpp $(CSRC)/plan.cpp $(CSRC)/sketch.cpp $(CSRC)/devcall.cpp $(CSRC)/registry.cpp $(CSRC)/blake2b_host.cpp \
             $(CSRC)/sha512_host.cpp
 OBJS := $(patsubst $(CSRC)/%.hip,$(OBJDIR)/%.hip.o,$(SRCS_HIP)) \
         $(patsubst $(CSRC)/%.cpp,$(OBJDIR)/%.o,$(SRCS_CPP))
@@ -94,6 +95,14 @@ tsan: build/host_tsan_driver
 
 sanitizers: asan tsan
 
+# the sketch rule (sketch.hpp) and the index parser under ASan + UBSan: a
+# stand-alone host program (tools/sketch_fuzz.cpp), no device code
+build/sketch_fuzz: tools/sketch_fuzz.cpp $(CSRC)/sketch.hpp $(CSRC)/dirsig.hpp $(CSRC)/dirsig.cpp
+	@mkdir -p build
+	$(CXX) -std=c++17 -O1 -g -fsanitize=address,undefined -fno-sanitize-recover=all \
+	    -I$(CSRC) tools/sketch_fuzz.cpp $(CSRC)/dirsig.cpp -o $@
+sketch_fuzz: build/sketch_fuzz
+
 oracle:
 	$(MAKE) -C oracle
 
@@ -101,4 +110,4 @@ clean:
 	rm -rf build $(LIB) $(CLI)
 	$(MAKE) -C oracle clean
 
-.PHONY: all oracle clean asan tsan sanitizers
+.PHONY: all oracle clean asan tsan sanitizers sketch_fuzz

@@ -83,6 +83,14 @@ index_digests,                  what every consumer of an index starts with: its
   Context.index_digests_dev     digests as one array and a run record per non-empty
                                 file, parsed on the device (the reference parses the
                                 text on a host thread: src/blocks.rs:150-183)
+index_sketch, sketch_rank,      the question before the plan: which older images are
+  sketch_key,                   worth handing to it.  A fixed-size content sketch per
+  Context.sketch_digests_dev    index (the k smallest distinct keys of its block
+                                digests, made on the device behind the parse) and a
+                                host-only ranking of candidate sources from sketches
+                                alone; the reference takes the 37 most recent images
+                                by timestamp (src/daemon/metadata/
+                                hardlink_sources.rs:66-90)
 =============================  ==============================================
 
 All hashing runs on gfx950 through the library; there is no CPU fallback.
@@ -104,7 +112,7 @@ __all__ = [
     "block_extents", "ExtentsResult", "Extent",
     "block_repeats", "RepeatsResult",
     "index_digests", "IndexDigests", "file_sources", "file_copies", "check_links_at",
-    "fetch_plan", "PlanResult",
+    "fetch_plan", "PlanResult", "index_sketch", "sketch_rank", "sketch_key",
 ]
 
 DEFAULT_BLOCK_SIZE = 32768
@@ -397,6 +405,19 @@ class Context:
         _n.check(_n.lib.cir_index_digests_dev(self._h, d_text, length, body_off, body_end,
                                               block_size, d_digests, cap_blocks, d_runs,
                                               cap_runs, d_work, work_bytes, d_res, stream))
+
+    def sketch_digests_dev(self, d_digests, n, k, d_keys, d_work, work_bytes, d_res, stream=0):
+        """The content sketch of n device-resident digests
+        (cir_sketch_digests_dev): d_keys = room for k u64; d_res: 4 u64
+        {CIR_SKETCH_OK or CIR_SKETCH_DECLINED, keys written, n, candidates
+        sorted}; d_work: sketch_work_bytes(n, k) bytes.  All written by the
+        call, on `stream` alone."""
+        _n.check(_n.lib.cir_sketch_digests_dev(self._h, d_digests, n, k, d_keys, d_work,
+                                               work_bytes, d_res, stream))
+
+    @staticmethod
+    def sketch_work_bytes(n, k=_n.CIR_SKETCH_DEFAULT_K):
+        return _n.lib.cir_sketch_work_bytes(n, k)
 
     def index_files_dev(self, d_text, length, body_off, body_end, block_size, d_files,
                         cap_files, d_work, work_bytes, d_res, off_bias=0, block_bias=0,
@@ -1269,6 +1290,66 @@ def index_digests(index, ctx=None):
         st["declined_at"] = None
     return IndexDigests(ht.value, bs.value, digests.reshape(-1, 32), runs.reshape(-1, 4),
                         nfiles.value, st)
+
+
+SKETCH_STATS_FIELDS = ("on_device", "why_host", "blocks", "keys", "uploaded", "downloaded")
+
+
+def index_sketch(index, context=None, k=_n.CIR_SKETCH_DEFAULT_K, stats=None):
+    """The content sketch of an index (cir_index_sketch): the k smallest
+    distinct 64-bit keys of its block digests in a blob of 40 + 8 count bytes,
+    to keep beside the index and hand to sketch_rank.  With a context the text
+    is parsed and sketched on its first GPU and only the keys come down;
+    without one (or for a text or a sketch the device declines) the host rule
+    answers and no GPU is needed.  Both give identical bytes and raise the
+    same errors as index_digests.  stats: a dict that receives the call's
+    SKETCH_STATS_FIELDS."""
+    if len(index):
+        ptr, keep = _buf(index)
+    else:  # (an empty index is a parse error, not a null argument)
+        keep = ctypes.create_string_buffer(1)
+        ptr = ctypes.cast(keep, ctypes.c_void_p)
+    blob, blob_len = ctypes.c_void_p(), ctypes.c_size_t()
+    st = (ctypes.c_uint64 * _n.CIR_SKETCH_STATS_FIELDS)()
+    _n.check(_n.lib.cir_index_sketch(context.handle if context is not None else None, ptr,
+                                     len(index), k, ctypes.byref(blob), ctypes.byref(blob_len),
+                                     st))
+    del keep
+    if stats is not None:
+        stats.update(zip(SKETCH_STATS_FIELDS, list(st)))
+    return _n.take_buffer(blob.value, blob_len.value)
+
+
+def sketch_key(digest):
+    """The sketch key of one 32-byte digest (cir_sketch_key)."""
+    digest = bytes(digest)
+    if len(digest) != 32:
+        raise ValueError("a digest is 32 bytes")
+    return _n.lib.cir_sketch_key(digest)
+
+
+def sketch_rank(need, sources, skipped=None):
+    """Ranks source sketches against the sketch of a new image
+    (cir_sketch_rank): [(ordinal, shared, examined)], best first by shared /
+    examined, ties in the caller's order.  A source that is None, not a valid
+    sketch or of another hash type or block size is left out (skipped: a list
+    that receives their count).  Host-only, no GPU."""
+    need = bytes(need)
+    nsrc = len(sources)
+    bufs = [None if s is None else ctypes.create_string_buffer(bytes(s), max(len(s), 1))
+            for s in sources]
+    n = max(nsrc, 1)
+    sp = (ctypes.c_void_p * n)(*[None if b is None else ctypes.cast(b, ctypes.c_void_p)
+                                 for b in bufs])
+    sl = (ctypes.c_size_t * n)(*[0 if s is None else len(s) for s in sources])
+    order, shared, examined = ((ctypes.c_uint64 * n)() for _ in range(3))
+    nranked, nskipped = ctypes.c_size_t(), ctypes.c_size_t()
+    _n.check(_n.lib.cir_sketch_rank(ctypes.create_string_buffer(need, max(len(need), 1)),
+                                    len(need), sp, sl, nsrc, order, shared, examined,
+                                    ctypes.byref(nranked), ctypes.byref(nskipped)))
+    if skipped is not None:
+        skipped.append(nskipped.value)
+    return [(order[i], shared[i], examined[i]) for i in range(nranked.value)]
 
 
 _default = None

@@ -76,6 +76,16 @@ CIR_PLAN_WANT_RES_FIELDS = 3
 CIR_PLAN_STATS_FIELDS = 44
 CIR_PLAN_WHY_EMPTY = 5
 CIR_INDEX_STATS_FIELDS = 4
+CIR_SKETCH_MAX_K = 4096
+CIR_SKETCH_DEFAULT_K = 1024
+CIR_SKETCH_RES_FIELDS = 4
+CIR_SKETCH_OK = 0
+CIR_SKETCH_DECLINED = 1
+CIR_SKETCH_STATS_FIELDS = 6
+CIR_SKETCH_WHY_ENV = 1
+CIR_SKETCH_WHY_TEXT = 2
+CIR_SKETCH_WHY_DECLINED = 3
+CIR_SKETCH_WHY_SIZE = 4
 CIR_INDEX_OK = 0
 CIR_INDEX_CAPACITY = 1
 CIR_INDEX_DECLINED = 2
@@ -263,6 +273,15 @@ _SIGS = {
                                       ctypes.POINTER(c_vp), c_sizep,
                                       ctypes.POINTER(c_vp), c_sizep, ctypes.POINTER(c_vp), c_sizep,
                                       ctypes.POINTER(c_vp), c_u64p, c_sizep, c_u64p]),
+    "cir_sketch_key": (ctypes.c_uint64, [c_vp]),
+    "cir_sketch_rank": (ctypes.c_int, [c_vp, ctypes.c_size_t, ctypes.POINTER(c_vp), c_sizep,
+                                       ctypes.c_size_t, c_u64p, c_u64p, c_u64p, c_sizep,
+                                       c_sizep]),
+    "cir_sketch_work_bytes": (ctypes.c_uint64, [ctypes.c_uint64, ctypes.c_uint32]),
+    "cir_sketch_digests_dev": (ctypes.c_int, [c_vp, c_vp, ctypes.c_uint64, ctypes.c_uint32, c_vp,
+                                              c_vp, ctypes.c_uint64, c_vp, c_vp]),
+    "cir_index_sketch": (ctypes.c_int, [c_vp, c_vp, ctypes.c_size_t, ctypes.c_uint32,
+                                        ctypes.POINTER(c_vp), c_sizep, c_u64p]),
     "cir_debug_compress_only_dev": (ctypes.c_int, [ctypes.c_uint64, ctypes.c_uint32, c_vp, c_vp]),
     "cir_debug_relay_blocks": (ctypes.c_uint64, [ctypes.c_uint64, ctypes.c_uint64]),
     "cir_debug_device_identity": (ctypes.c_int, [ctypes.c_int, ctypes.c_char_p, ctypes.c_size_t,

@@ -81,6 +81,19 @@
 //       blocks, repeats, extents, bytes, left to fetch -- and one line per
 //       extent, `PATH OFFSET LENGTH CLASS SRCPATH SRCOFFSET` (CLASS 1: the
 //       source block is one of those fetched).  --host opens no device.
+//   ciruela-index sketch INDEX [-k N] [-o FILE] [--host]
+//       the content sketch of INDEX (cir_index_sketch): the N (default 1024)
+//       smallest distinct keys of its block digests, a blob of at most 40 + 8 N
+//       bytes to keep beside the index, written to FILE (default: standard
+//       output).  --host passes no context and opens no device.
+//   ciruela-index rank NEED SRC [SRC ...] [-k N] [--host]
+//       which older images are worth handing to `plan` (cir_sketch_rank): the
+//       sources ordered by how much of NEED each holds, one line `ORDINAL SHARED
+//       EXAMINED PATH` per ranked source, best first; a source of another hash
+//       type or block size, or one that is neither a sketch nor an index, is
+//       left out and counted on stderr.  Each argument is a sketch file or an
+//       index file, told apart by its first bytes; an index is sketched on the
+//       spot (size N).  A device is opened only when an index is among them.
 #include <dirent.h>
 #include <errno.h>
 #include <fcntl.h>
@@ -111,7 +124,9 @@ static void usage() {
           "       ciruela-index blocks DIR INDEX_FILE [--list] [--disk-threads N]\n"
           "       ciruela-index sources INDEX SRCINDEX [SRCINDEX ...] [--list] [--host]"
           " [--extents]\n"
-          "       ciruela-index repeats INDEX [--host]\n");
+          "       ciruela-index repeats INDEX [--host]\n"
+          "       ciruela-index sketch INDEX [-k N] [-o FILE] [--host]\n"
+          "       ciruela-index rank NEED SRC [SRC ...] [-k N] [--host]\n");
 }
 
 static std::string hex(const uint8_t* p, size_t n) {
@@ -278,6 +293,11 @@ static std::vector<std::string> index_file_paths(const std::vector<uint8_t>& ind
   return out;
 }
 
+// Does a file hold a sketch blob (cir_index_sketch's magic) rather than an index?
+static bool is_sketch(const std::vector<uint8_t>& data) {
+  return data.size() >= 8 && memcmp(data.data(), "CIRSKv1", 8) == 0;
+}
+
 // split "source:/dir/dest" (src/client/sync/uploads.rs:25-33)
 static bool split(const std::string& cli, std::string* src, std::string* dest) {
   const size_t c = cli.find(':');
@@ -305,6 +325,9 @@ int main(int argc, char** argv) {
   std::string index_dir;
   bool list_blocks = false, host_only = false, extents = false, host_candidates = false;
   bool unlinked = false, any_path = false;
+  const bool sketching = cmd == "sketch" || cmd == "rank";
+  uint32_t sketch_k = CIR_SKETCH_DEFAULT_K;
+  std::string out_path;
   std::vector<Job> jobs;
   std::vector<std::string> files;
   for (int i = 2; i < argc; ++i) {
@@ -334,6 +357,18 @@ int main(int argc, char** argv) {
         bs = n;
     }
     else if (a == "--index-dir") index_dir = val();
+    else if (a == "-k" && sketching) {
+      const std::string v = val();
+      char* end = nullptr;
+      const unsigned long long n = strtoull(v.c_str(), &end, 10);
+      if (v.empty() || v[0] == '-' || *end || n < 1 || n > CIR_SKETCH_MAX_K) {
+        fprintf(stderr, "invalid value for -k: %s (1 .. %d)\n", v.c_str(), CIR_SKETCH_MAX_K);
+        return 2;
+      }
+      sketch_k = (uint32_t)n;
+    }
+    else if (a == "-o" && cmd == "sketch") out_path = val();
+    else if (a == "--host" && sketching) host_only = true;
     else if (a == "--list" && (cmd == "blocks" || cmd == "sources")) list_blocks = true;
     else if (a == "--host" &&
              (cmd == "sources" || cmd == "repeats" || cmd == "candidates" || cmd == "copies" ||
@@ -353,7 +388,7 @@ int main(int argc, char** argv) {
       jobs.push_back(j);
     } else if ((cmd == "hash" || cmd == "check" || cmd == "links" || cmd == "blocks" ||
                 cmd == "sources" || cmd == "repeats" || cmd == "candidates" || cmd == "copies" ||
-       cmd == "plan") &&
+       cmd == "plan" || sketching) &&
                a.size() &&
                a[0] != '-') {
       files.push_back(a);
@@ -396,18 +431,32 @@ int main(int argc, char** argv) {
       if (!read_file(files[i], &link_indexes.back())) return 2;
     }
   }
-  if (cmd == "repeats" && files.size() != 1) {
+  if ((cmd == "repeats" || cmd == "sketch") && files.size() != 1) {
     usage();
     return 2;
   }
+  if (cmd == "rank") {
+    // every argument is read before any device is opened; sketches alone need none
+    if (files.size() < 2) {
+      usage();
+      return 2;
+    }
+    bool any_index = false;
+    for (const std::string& f : files) {
+      link_indexes.emplace_back();
+      if (!read_file(f, &link_indexes.back())) return 2;
+      any_index = any_index || !is_sketch(link_indexes.back());
+    }
+    if (!any_index) host_only = true;
+  }
   std::vector<std::string> inputs = cmd == "links" ? link_dirs : files;
   if (cmd == "sources" || cmd == "repeats" || cmd == "candidates" || cmd == "copies" ||
-       cmd == "plan")
+       cmd == "plan" || sketching)
     inputs.clear();  // (indexes only: nothing is staged)
   std::vector<uint8_t> check_index;
   // (read, and a missing one reported, before any device is opened)
   if ((cmd == "sources" || cmd == "repeats" || cmd == "candidates" || cmd == "copies" ||
-       cmd == "plan") &&
+       cmd == "plan" || cmd == "sketch") &&
       !read_file(files[0], &check_index))
     return 2;
   if (cmd == "links" && !read_file(files[0], &check_index)) return 2;
@@ -906,6 +955,77 @@ int main(int argc, char** argv) {
     fflush(stdout);
     cir_free(ext);
     cir_free(fetch);
+  } else if (cmd == "sketch") {
+    static const uint8_t none = 0;
+    uint8_t* blob = nullptr;
+    size_t blob_len = 0;
+    uint64_t st[CIR_SKETCH_STATS_FIELDS];
+    rc = cir_index_sketch(ctx, check_index.empty() ? &none : check_index.data(),
+                          check_index.size(), sketch_k, &blob, &blob_len, st);
+    if (rc) {
+      die(rc, files[0].c_str());
+      return 2;
+    }
+    FILE* out = out_path.empty() ? stdout : fopen(out_path.c_str(), "wb");
+    if (!out) {
+      perror(out_path.c_str());
+      return 1;
+    }
+    const bool bad = fwrite(blob, 1, blob_len, out) != blob_len || fflush(out) != 0;
+    if (out != stdout && fclose(out) != 0) {
+      perror(out_path.c_str());
+      return 1;
+    }
+    if (bad) {
+      perror(out_path.empty() ? "stdout" : out_path.c_str());
+      return 1;
+    }
+    cir_free(blob);
+    fprintf(stderr, "sketch: %llu keys of %llu blocks, %zu bytes, sketched on the %s\n",
+            (unsigned long long)st[3], (unsigned long long)st[2], blob_len,
+            st[0] ? "device" : "host");
+  } else if (cmd == "rank") {
+    // an index among the arguments is replaced by its sketch
+    for (size_t i = 0; i < link_indexes.size(); ++i) {
+      std::vector<uint8_t>& data = link_indexes[i];
+      if (is_sketch(data)) continue;
+      uint8_t* blob = nullptr;
+      size_t blob_len = 0;
+      uint64_t st[CIR_SKETCH_STATS_FIELDS];
+      static const uint8_t none = 0;
+      rc = cir_index_sketch(ctx, data.empty() ? &none : data.data(), data.size(), sketch_k, &blob,
+                            &blob_len, st);
+      if (rc && i == 0) {
+        die(rc, files[0].c_str());
+        return 2;
+      }
+      if (rc) {  // (a source that does not parse is left out, as the planning calls leave it)
+        data.clear();
+        continue;
+      }
+      data.assign(blob, blob + blob_len);
+      cir_free(blob);
+    }
+    const size_t nsrc = link_indexes.size() - 1;
+    std::vector<const uint8_t*> sp(nsrc);
+    std::vector<size_t> sl(nsrc);
+    for (size_t i = 0; i < nsrc; ++i) {
+      sp[i] = link_indexes[i + 1].empty() ? nullptr : link_indexes[i + 1].data();
+      sl[i] = link_indexes[i + 1].size();
+    }
+    std::vector<uint64_t> order(nsrc), shared(nsrc), examined(nsrc);
+    size_t nranked = 0, nskipped = 0;
+    rc = cir_sketch_rank(link_indexes[0].data(), link_indexes[0].size(), sp.data(), sl.data(), nsrc,
+                         order.data(), shared.data(), examined.data(), &nranked, &nskipped);
+    if (rc) {
+      die(rc, files[0].c_str());
+      return 2;
+    }
+    for (size_t i = 0; i < nranked; ++i)
+      printf("%llu %llu %llu %s\n", (unsigned long long)order[i], (unsigned long long)shared[i],
+             (unsigned long long)examined[i], files[order[i] + 1].c_str());
+    fflush(stdout);
+    fprintf(stderr, "rank: %zu source(s) ranked, %zu left out\n", nranked, nskipped);
   } else if (cmd == "sync") {
     if (jobs.empty()) {
       usage();

@@ -365,6 +365,42 @@ hipError_t launch_plan_want(const uint64_t* runs, uint64_t n_runs, uint64_t n_bl
                             uint64_t n_files, const uint32_t* cand_a, const uint32_t* cand_b,
                             const uint64_t* have, uint64_t* want, uint64_t* res, hipStream_t s);
 
+// The content sketch of a digest list (sketch.hip; cir_sketch_digests_dev; the
+// rule is sketch.hpp): keys[0 .. res[1]) = the k smallest distinct keys of the
+// n digests (16-B aligned), ascending, all on `s`.  work:
+// sketch_work_bytes(n) bytes of scratch, initialised here; res:
+// kSketchResFields u64 {status, keys written, n, candidates sorted}, all
+// written here.  kSketchDeclined: the answer did not fit the scratch (more
+// distinct keys than kSketchCands at or below the k-th key's histogram bin, or
+// a probe walk past kSketchWalk slots); the keys then mean nothing.
+// Unchecked: 1 <= k <= sketch::kMaxK, n < 2^32.  tev (nullable, a traced
+// cir_index_sketch): 2 events around the whole of it.
+constexpr int kSketchResFields = 4;
+constexpr uint64_t kSketchOk = 0, kSketchDeclined = 1;
+constexpr uint32_t kSketchCands = 8192;  // u64 keys the last kernel sorts in LDS (64 KiB)
+constexpr uint32_t kSketchWalk = 1024;   // probed slots per key before the call declines
+constexpr int kSketchHeadWords = 8;
+constexpr uint64_t kSketchEmpty = ~0ull;  // (the key 2^64 - 1 is kept in a flag of its own)
+inline uint64_t sketch_table_slots(uint64_t n) {
+  uint64_t s = 1024;
+  while (s < 2 * n) s <<= 1;
+  return s;
+}
+// Histogram bins over the keys' top bits: about 64 distinct keys per bin when
+// every digest is distinct, at least 2^10 and at most 2^26 bins.
+inline uint32_t sketch_hist_bits(uint64_t n) {
+  uint32_t b = 10;
+  while (b < 26 && (64ull << b) < n) ++b;
+  return b;
+}
+inline uint64_t sketch_work_bytes(uint64_t n) {
+  return 8 * (kSketchHeadWords + (uint64_t)kSketchCands) + (4ull << sketch_hist_bits(n)) +
+         8 * sketch_table_slots(n);
+}
+hipError_t launch_sketch(const uint8_t* digests, uint64_t n, uint32_t k, uint64_t* keys,
+                         uint64_t* work, uint64_t* res, hipStream_t s,
+                         const hipEvent_t* tev = nullptr);
+
 // nlanes x `lines` register-only compressions (diagnostic VALU ceiling).
 hipError_t launch_compress_only(uint64_t nlanes, uint32_t lines, uint8_t* out, hipStream_t s);
 

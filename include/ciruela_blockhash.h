@@ -56,6 +56,8 @@
  *       CIR_PLAN=host          cir_fetch_plan with a context answers with the host
  *                              composition of the four calls it is defined by (A/B
  *                              measurement; read per call);
+ *       CIR_SKETCH=host        cir_index_sketch with a context answers with the host
+ *                              rule (A/B measurement; read per call);
  *       CIR_DEBUG_SPLIT=k      (tests) every opened GPU appears k times.
  *       CIR_DEBUG_STRIPE_BLOCKS=n  (tests) a scan over several devices deals
  *                              stripes of n blocks (default: one staging
@@ -1273,6 +1275,110 @@ int cir_fetch_plan(cir_ctx* ctx, const uint8_t* index, size_t len,
                    uint64_t** extents_out, size_t* nextents_out, uint64_t** repeat_extents_out,
                    size_t* nrepeats_out, uint64_t** fetch_out, uint64_t* nblk_out,
                    size_t* nskipped_out, uint64_t stats[CIR_PLAN_STATS_FIELDS]);
+
+/* ---- content sketches: which older images are worth a plan ------------- */
+
+/* Every planning call above takes the older images' full index texts, and those texts are its
+ * cost (cir_fetch_plan with 16 sources uploads 1.77 GB).  The reference chooses its sources by
+ * timestamp, the 37 most recent images of the base directory whatever they hold
+ * (src/daemon/metadata/hardlink_sources.rs:66-90, "TODO make tweakable", "TODO look in cache").
+ * A sketch is a fixed-size summary of an index's block digests, made once when the index is
+ * registered and kept beside it (at most 40 + 8 k bytes); cir_sketch_rank orders any number of
+ * candidate sources by how much of the new image each one holds, from sketches alone, so no text
+ * is uploaded for an image that will not be used.  The plan stays exact: the ranking only
+ * decides which texts it is given.  Nothing lives on the device between calls.
+ *
+ * The rule (ciruela_amd/csrc/sketch.hpp).  Key of a digest: x = 0x243F6A8885A308D3; for the four
+ * little-endian u64 words w of the 32 bytes, in order: x = (x ^ w) * 0x9E3779B97F4A7C15, x ^= x >>
+ * 32; the key is the full x.  Sketch of size k (1 <= k <= CIR_SKETCH_MAX_K): the k smallest
+ * distinct keys of the digests of all blocks of all file entries (cir_index_digests' block list),
+ * ascending; all of them when there are fewer.  The seed is fixed because sketches are stored
+ * and compared across calls, and every step of the mix is invertible: an index's author can
+ * choose the keys of their own digests.  That can only mislead the ranking, never the plan.
+ *
+ * Blob, little-endian: 8 bytes "CIRSKv1\0", u32 hash_type, u32 k, u64 block_size, u64 n_blocks,
+ * u64 count, count u64 keys.  Valid iff the magic matches, 1 <= k <= 4096, count <= k, count <=
+ * n_blocks, the length is exactly 40 + 8 count and the keys are strictly ascending; everything
+ * that reads a blob validates it first. */
+#define CIR_SKETCH_MAX_K 4096
+#define CIR_SKETCH_DEFAULT_K 1024
+
+/* The key of one 32-byte digest (0 for a null pointer).  Pure, host-only. */
+uint64_t cir_sketch_key(const uint8_t* digest);
+
+/* Ranks nsrc source sketches against the sketch of a new image.  Overlap of the need sketch N
+ * and a source sketch S: t(X) = X's last key if X is full (count == k), else 2^64 - 1; tau =
+ * min(t(N), t(S)); both sketches are complete below tau, so examined = the number of N's keys <=
+ * tau and shared = how many of those S holds are exact over that range, and shared / examined
+ * estimates the fraction of the new image's distinct blocks the source holds (it is that
+ * fraction when neither sketch is full).  Sources are ordered by shared / examined descending
+ * (compared by cross-multiplying in integers; examined == 0 counts as 0), ties to the lower
+ * ordinal: the caller's order is kept.  order_out[0 .. *nranked_out) = the ranked source
+ * ordinals, shared_out and examined_out indexed like order_out; all three hold nsrc entries.  A
+ * source that is NULL, not a valid blob, or of another hash type or block size than the need is
+ * left out and counted in *nskipped_out (may be NULL), as cir_link_candidates treats its
+ * sources.  The sketches' k may differ.  Pure, host-only, no GPU.
+ * CIR_EINVAL: a null need, nranked_out, or (with nsrc > 0) array; CIR_EPARSE: the need blob is
+ * not valid. */
+int cir_sketch_rank(const uint8_t* need, size_t need_len, const uint8_t* const* src,
+                    const size_t* src_len, size_t nsrc, uint64_t* order_out, uint64_t* shared_out,
+                    uint64_t* examined_out, size_t* nranked_out, size_t* nskipped_out);
+
+/* Bytes of device scratch cir_sketch_digests_dev needs for n digests.  Pure. */
+uint64_t cir_sketch_work_bytes(uint64_t n, uint32_t k);
+
+/* The sketch of a digest list in device memory: d_digests = n digests of 32 bytes as
+ * cir_index_digests_dev leaves them, d_keys = room for k u64.
+ *
+ * d_res (device, CIR_SKETCH_RES_FIELDS u64, every word written by the call): [0] CIR_SKETCH_OK
+ * or CIR_SKETCH_DECLINED, [1] keys written = min(k, distinct keys), [2] n, [3] candidates the
+ * selection sorted (diagnostic).  On CIR_SKETCH_OK d_keys[0 .. [1]) holds exactly the rule's
+ * keys, ascending.  CIR_SKETCH_DECLINED: the device could not answer exactly inside its scratch
+ * -- more than 8192 distinct keys share the k-th key's top bits (for uniformly spread keys a
+ * histogram bin holds about 64), or a key's probe walk in the set passed 1024 slots; both take a
+ * crafted index -- and the keys then mean nothing; the host rule answers (cir_index_sketch does
+ * that).  The device never returns a wrong or short sketch with CIR_SKETCH_OK.  The keys 0 and
+ * 2^64 - 1 are ordinary keys.  n == 0 is CIR_SKETCH_OK with no key.  Nothing is written past
+ * d_keys[k), d_work[work_bytes) or d_res[4).
+ *
+ * Like every *_dev call it allocates nothing, synchronises nothing and runs on `stream` alone
+ * (two memsets and four launches: insert into a set of keys with a histogram of their top bits,
+ * scan the histogram, compact the candidates, sort them in LDS; no workgroup waits for another
+ * and every probe walk is bounded); ctx may be NULL and is not used.
+ *
+ * CIR_EINVAL, decided before any HIP call: a null d_digests (with n > 0), d_keys, d_work or
+ * d_res; d_digests not 16-byte aligned; d_keys, d_work or d_res not 8-byte aligned; k outside
+ * [1, 4096]; n > 2^32 - 1; work_bytes < cir_sketch_work_bytes(n, k). */
+#define CIR_SKETCH_RES_FIELDS 4
+#define CIR_SKETCH_OK 0
+#define CIR_SKETCH_DECLINED 1
+int cir_sketch_digests_dev(cir_ctx* ctx, const uint8_t* d_digests, uint64_t n, uint32_t k,
+                           uint64_t* d_keys, void* d_work, uint64_t work_bytes, uint64_t* d_res,
+                           void* stream);
+
+/* The sketch of an index in host memory: *blob_out = the malloc'd blob (cir_free), *blob_len its
+ * length (40 bytes for an index without blocks).  With a context: cir_index_frame, one upload,
+ * cir_index_digests_dev's kernels and cir_sketch_digests_dev's behind them on the context's first
+ * device, and a download of the result words and at most 8 k bytes of keys -- the digests never
+ * come down (cir_index_digests with a context downloads 32 bytes per block); the current device
+ * is restored.  The host rule alone (the host parser, the keys, a partial sort) answers when ctx
+ * == NULL, with CIR_SKETCH=host, for a text the device declines, for a declined sketch and for a
+ * length the device parse does not take.  None of these is an error, and the blob is
+ * byte-identical on both paths.  Error codes are cir_index_digests' (CIR_EPARSE, CIR_EHASHSIZE,
+ * CIR_EINVAL -- also k outside [1, 4096] --, CIR_ENOMEM); on error *blob_out is NULL, *blob_len 0
+ * and the stats are zero.
+ *
+ * stats: [0] 1 if the device answered, [1] why not: 0 (it did, or ctx == NULL) or a
+ * CIR_SKETCH_WHY_* value, [2] blocks, [3] keys in the blob, [4] text bytes uploaded, [5] bytes
+ * downloaded. */
+#define CIR_SKETCH_STATS_FIELDS 6
+#define CIR_SKETCH_WHY_ENV 1      /* CIR_SKETCH=host */
+#define CIR_SKETCH_WHY_TEXT 2     /* the device parse declined the text */
+#define CIR_SKETCH_WHY_DECLINED 3 /* CIR_SKETCH_DECLINED */
+#define CIR_SKETCH_WHY_SIZE 4     /* a text longer than the device parse takes */
+int cir_index_sketch(cir_ctx* ctx, const uint8_t* index, size_t len, uint32_t k,
+                     uint8_t** blob_out, size_t* blob_len,
+                     uint64_t stats[CIR_SKETCH_STATS_FIELDS]);
 
 /* ---- index (DIRSIGNATURE.v1) ----------------------------------------- */
 
