@@ -3,6 +3,7 @@
 #                      load drivers under build/, oracle
 #   make oracle     -> oracle/build/liboracle_blake2b.so (test infrastructure)
 #   make sketch_fuzz -> build/sketch_fuzz (the sketch rule under ASan + UBSan; not in `all`)
+#   make emit_fuzz  -> build/emit_fuzz (the emit rule under ASan + UBSan; not in `all`)
 #   make asan/tsan  -> build/host_{asan,tsan}_driver (host code under the
 #                      sanitizers; `make sanitizers` = both; not in `all`)
 HIPCC ?= /opt/rocm/bin/hipcc
@@ -21,10 +22,10 @@ CLI := bin/ciruela-index
 
 SRCS_HIP := $(CSRC)/kernels.hip $(CSRC)/order.hip $(CSRC)/join.hip \
             $(CSRC)/idxscan.hip $(CSRC)/extents.hip $(CSRC)/repeats.hip \
-            $(CSRC)/files.hip $(CSRC)/plan.hip $(CSRC)/sketch.hip
+            $(CSRC)/files.hip $(CSRC)/plan.hip $(CSRC)/sketch.hip $(CSRC)/emit.hip
 SRCS_CPP := $(CSRC)/runtime.cpp $(CSRC)/dirsig.cpp $(CSRC)/scan.cpp $(CSRC)/check.cpp \
             $(CSRC)/links.cpp $(CSRC)/sources.cpp $(CSRC)/repeats.cpp $(CSRC)/idxscan.cpp \
-            $(CSRC)/files.cpp $(CSRC)/copies.cpp $(CSRC)/plan.cpp $(CSRC)/sketch.cpp $(CSRC)/devcall.cpp $(CSRC)/registry.cpp $(CSRC)/blake2b_host.cpp \
+            $(CSRC)/files.cpp $(CSRC)/copies.cpp $(CSRC)/plan.cpp $(CSRC)/sketch.cpp $(CSRC)/memindex.cpp $(CSRC)/devcall.cpp $(CSRC)/registry.cpp $(CSRC)/blake2b_host.cpp \
             $(CSRC)/sha512_host.cpp
 OBJS := $(patsubst $(CSRC)/%.hip,$(OBJDIR)/%.hip.o,$(SRCS_HIP)) \
         $(patsubst $(CSRC)/%.cpp,$(OBJDIR)/%.o,$(SRCS_CPP))
@@ -103,6 +104,14 @@ build/sketch_fuzz: tools/sketch_fuzz.cpp $(CSRC)/sketch.hpp $(CSRC)/dirsig.hpp $
 	    -I$(CSRC) tools/sketch_fuzz.cpp $(CSRC)/dirsig.cpp -o $@
 sketch_fuzz: build/sketch_fuzz
 
+# the emit rule (emit.hpp) under ASan + UBSan: a stand-alone host program
+# (tools/emit_fuzz.cpp), no device code
+build/emit_fuzz: tools/emit_fuzz.cpp $(CSRC)/emit.hpp $(CSRC)/dirsig.hpp $(CSRC)/dirsig.cpp
+	@mkdir -p build
+	$(CXX) -std=c++17 -O1 -g -fsanitize=address,undefined -fno-sanitize-recover=all \
+	    -I$(CSRC) tools/emit_fuzz.cpp $(CSRC)/dirsig.cpp -o $@
+emit_fuzz: build/emit_fuzz
+
 oracle:
 	$(MAKE) -C oracle
 
@@ -110,4 +119,4 @@ clean:
 	rm -rf build $(LIB) $(CLI)
 	$(MAKE) -C oracle clean
 
-.PHONY: all oracle clean asan tsan sanitizers sketch_fuzz
+.PHONY: all oracle clean asan tsan sanitizers sketch_fuzz emit_fuzz

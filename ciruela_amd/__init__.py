@@ -91,6 +91,12 @@ index_sketch, sketch_rank,      the question before the plan: which older images
                                 alone; the reference takes the 37 most recent images
                                 by timestamp (src/daemon/metadata/
                                 hardlink_sources.rs:66-90)
+index_memory, index_emit,       the index and ImageId of files that no directory holds:
+  index_emit_layout,            bytes in device memory (tensors, checkpoints) hashed
+  Context.index_emit_dev        where they lie and the text written by the device, the
+                                inverse of index_digests; equal to v1.scan of a
+                                directory holding the same files (the reference indexes
+                                directories only: src/client/sync/uploads.rs:49-59)
 =============================  ==============================================
 
 All hashing runs on gfx950 through the library; there is no CPU fallback.
@@ -113,6 +119,7 @@ __all__ = [
     "block_repeats", "RepeatsResult",
     "index_digests", "IndexDigests", "file_sources", "file_copies", "check_links_at",
     "fetch_plan", "PlanResult", "index_sketch", "sketch_rank", "sketch_key",
+    "index_memory", "index_emit", "index_emit_layout", "index_emit_tables",
 ]
 
 DEFAULT_BLOCK_SIZE = 32768
@@ -418,6 +425,16 @@ class Context:
     @staticmethod
     def sketch_work_bytes(n, k=_n.CIR_SKETCH_DEFAULT_K):
         return _n.lib.cir_sketch_work_bytes(n, k)
+
+    def index_emit_dev(self, d_digests, ndigests, d_pieces, npieces, d_lits, lits_len, d_body,
+                       body_len, d_res, stream=0):
+        """The body text of an index from device-resident digests, pieces and
+        literals (cir_index_emit_dev; index_emit_layout gives the tables):
+        every byte of d_body[0, body_len rounded up to 16) and d_res[0] (the
+        count of pieces whose ranges lie outside the arrays; their bytes are 0)
+        is written, nothing else, on `stream` alone."""
+        _n.check(_n.lib.cir_index_emit_dev(self._h, d_digests, ndigests, d_pieces, npieces, d_lits,
+                                           lits_len, d_body, body_len, d_res, stream))
 
     def index_files_dev(self, d_text, length, body_off, body_end, block_size, d_files,
                         cap_files, d_work, work_bytes, d_res, off_bias=0, block_bias=0,
@@ -1350,6 +1367,144 @@ def sketch_rank(need, sources, skipped=None):
     if skipped is not None:
         skipped.append(nskipped.value)
     return [(order[i], shared[i], examined[i]) for i in range(nranked.value)]
+
+
+MEMINDEX_STATS_FIELDS = ("blocks", "device_emit", "files", "body_bytes", "uploaded", "downloaded")
+
+
+def _emit_files(files):
+    """The parallel arrays of a file list [(path, x[, exe])]: (paths buffer,
+    path_off, sizes or None, exe, the x column)."""
+    paths, offs, exe, col = [], [0], [], []
+    for f in files:
+        path = os.fsencode(f[0]) if isinstance(f[0], str) else bytes(f[0])
+        paths.append(path)
+        offs.append(offs[-1] + len(path))
+        col.append(f[1])
+        exe.append(1 if len(f) > 2 and f[2] else 0)
+    n = len(files)
+    blob = b"".join(paths)
+    return (ctypes.create_string_buffer(blob, max(len(blob), 1)), (ctypes.c_uint64 * (n + 1))(*offs),
+            ctypes.create_string_buffer(bytes(exe), max(n, 1)), col)
+
+
+def _sizes(values):
+    return (ctypes.c_uint64 * max(len(values), 1))(*values)
+
+
+def index_emit_layout(files, block_size=DEFAULT_BLOCK_SIZE):
+    """The layout of a file list [(path, size[, exe])]
+    (cir_index_emit_layout): (pieces: numpy u64 (npieces, 5) {out_off, lit_off,
+    lit_len, first_block, nblk} in emission order, lits: bytes, first_block:
+    numpy u64 per file in the caller's order, nblocks, body_len).  What
+    Context.index_emit_dev takes once uploaded.  Host-only, no GPU."""
+    import numpy as np
+    paths, offs, exe, sizes = _emit_files(files)
+    n = len(files)
+    pp, lp = ctypes.c_void_p(), ctypes.c_void_p()
+    npieces, nlits = ctypes.c_size_t(), ctypes.c_size_t()
+    first = (ctypes.c_uint64 * max(n, 1))()
+    nblk, body = ctypes.c_uint64(), ctypes.c_uint64()
+    _n.check(_n.lib.cir_index_emit_layout(block_size, paths, offs, _sizes(sizes), exe, n,
+                                          ctypes.byref(pp), ctypes.byref(npieces),
+                                          ctypes.byref(lp), ctypes.byref(nlits), first,
+                                          ctypes.byref(nblk), ctypes.byref(body)))
+    pieces = np.frombuffer(_n.take_buffer(pp.value, 8 * _n.CIR_EMIT_PIECE_WORDS * npieces.value),
+                           dtype=np.uint64).reshape(-1, _n.CIR_EMIT_PIECE_WORDS)
+    lits = _n.take_buffer(lp.value, nlits.value)
+    return pieces, lits, np.array(first[:n], dtype=np.uint64), nblk.value, body.value
+
+
+def index_emit_tables(pieces, lits, digests, body_len):
+    """The body of an index from its tables on the host
+    (cir_index_emit_tables): pieces as index_emit_layout gives them (any
+    buffer of 5 u64 per piece), lits and digests bytes-like.  Returns (the
+    body_len rounded up to 16 bytes, padding included, the count of pieces
+    whose ranges lie outside the arrays).  Host-only, no GPU."""
+    pieces, lits, digests = bytes(pieces), bytes(lits), bytes(digests)
+    if len(pieces) % (8 * _n.CIR_EMIT_PIECE_WORDS) or len(digests) % 32:
+        raise ValueError("pieces are 40 bytes each, digests 32")
+    cap = (body_len + 15) // 16 * 16
+    body = ctypes.create_string_buffer(max(cap, 1))
+    res = (ctypes.c_uint64 * _n.CIR_EMIT_RES_FIELDS)()
+    _n.check(_n.lib.cir_index_emit_tables(
+        ctypes.create_string_buffer(digests, max(len(digests), 1)), len(digests) // 32,
+        ctypes.create_string_buffer(pieces, max(len(pieces), 1)),
+        len(pieces) // (8 * _n.CIR_EMIT_PIECE_WORDS),
+        ctypes.create_string_buffer(lits, max(len(lits), 1)), len(lits), body, body_len, res))
+    return body.raw[:cap], res[0]
+
+
+def index_emit(files, digests, block_size=DEFAULT_BLOCK_SIZE, hash_type=None, image_id=None):
+    """The index of a flat list of regular files from host digests
+    (cir_index_emit): files = [(path, size[, exe])] in any order, path bytes or
+    str, absolute; digests = one bytes-like of 32 bytes per block, file i's
+    behind file i-1's in the files' order.  The text is what v1.scan gives for
+    a directory holding these files.  image_id: a list that receives the
+    ImageId.  Host-only, no GPU."""
+    ht = (hash_type or HashType.blake2b_256()).code
+    digests = bytes(digests)
+    if len(digests) % 32:
+        raise ValueError("a digest is 32 bytes")
+    paths, offs, exe, sizes = _emit_files(files)
+    out, out_len = ctypes.c_void_p(), ctypes.c_size_t()
+    iid = ctypes.create_string_buffer(32)
+    _n.check(_n.lib.cir_index_emit(ht, block_size, paths, offs, _sizes(sizes), exe, len(files),
+                                   ctypes.create_string_buffer(digests, max(len(digests), 1)),
+                                   len(digests) // 32, ctypes.byref(out), ctypes.byref(out_len),
+                                   iid))
+    if image_id is not None:
+        image_id.append(ImageId(iid.raw))
+    return _n.take_buffer(out.value, out_len.value)
+
+
+def _device_span(obj):
+    """(device pointer, bytes) of a (ptr, nbytes) pair or of anything with
+    data_ptr() and a byte count (a torch tensor: element_size() x numel(), or
+    nbytes); nothing is imported for it."""
+    if isinstance(obj, (tuple, list)) and len(obj) == 2:
+        return int(obj[0]), int(obj[1])
+    if not hasattr(obj, "data_ptr"):
+        raise TypeError("expected (ptr, nbytes) or an object with data_ptr(), got %r" % type(obj))
+    is_contiguous = getattr(obj, "is_contiguous", None)
+    if is_contiguous is not None and not is_contiguous():
+        raise ValueError("device data must be contiguous")
+    if hasattr(obj, "element_size") and hasattr(obj, "numel"):
+        nbytes = obj.element_size() * obj.numel()
+    elif hasattr(obj, "nbytes"):
+        nbytes = obj.nbytes
+    else:
+        raise TypeError("%r has data_ptr() but no byte count" % type(obj))
+    return int(obj.data_ptr()), int(nbytes)
+
+
+def index_memory(files, block_size=DEFAULT_BLOCK_SIZE, hash_type=None, context=None, stream=0,
+                 image_id=None, stats=None):
+    """The index of files held in device memory (cir_index_memory_dev): files
+    = [(path, obj[, exe])], obj a (ptr, nbytes) pair or anything with
+    data_ptr() and a byte count (a torch tensor), contiguous.  Hashing and the
+    text both run on the GPU of `stream`, queued behind whatever that stream
+    already holds; only the text comes down.  Returns the index bytes, equal to
+    v1.scan of a directory holding the same files.  image_id: a list that
+    receives the ImageId; stats: a dict that receives MEMINDEX_STATS_FIELDS."""
+    ht = (hash_type or HashType.blake2b_256()).code
+    ctx = context or default_context()
+    paths, offs, exe, objs = _emit_files(files)
+    spans = [_device_span(o) for o in objs]
+    n = len(files)
+    ptrs = (ctypes.c_void_p * max(n, 1))(*[p or None for p, _ in spans])
+    out, out_len = ctypes.c_void_p(), ctypes.c_size_t()
+    iid = ctypes.create_string_buffer(32)
+    st = (ctypes.c_uint64 * _n.CIR_MEMINDEX_STATS_FIELDS)()
+    _n.check(_n.lib.cir_index_memory_dev(ctx.handle, ht, block_size, paths, offs,
+                                         _sizes([b for _, b in spans]), exe, n, ptrs, stream,
+                                         ctypes.byref(out), ctypes.byref(out_len), iid, st))
+    del objs
+    if image_id is not None:
+        image_id.append(ImageId(iid.raw))
+    if stats is not None:
+        stats.update(zip(MEMINDEX_STATS_FIELDS, list(st)))
+    return _n.take_buffer(out.value, out_len.value)
 
 
 _default = None

@@ -86,6 +86,9 @@ CIR_SKETCH_WHY_ENV = 1
 CIR_SKETCH_WHY_TEXT = 2
 CIR_SKETCH_WHY_DECLINED = 3
 CIR_SKETCH_WHY_SIZE = 4
+CIR_EMIT_PIECE_WORDS = 5
+CIR_EMIT_RES_FIELDS = 1
+CIR_MEMINDEX_STATS_FIELDS = 6
 CIR_INDEX_OK = 0
 CIR_INDEX_CAPACITY = 1
 CIR_INDEX_DECLINED = 2
@@ -282,6 +285,20 @@ _SIGS = {
                                               c_vp, ctypes.c_uint64, c_vp, c_vp]),
     "cir_index_sketch": (ctypes.c_int, [c_vp, c_vp, ctypes.c_size_t, ctypes.c_uint32,
                                         ctypes.POINTER(c_vp), c_sizep, c_u64p]),
+    "cir_index_emit_layout": (ctypes.c_int, [ctypes.c_uint64, c_vp, c_u64p, c_u64p, c_vp,
+                                             ctypes.c_size_t, ctypes.POINTER(c_vp), c_sizep,
+                                             ctypes.POINTER(c_vp), c_sizep, c_u64p, c_u64p,
+                                             c_u64p]),
+    "cir_index_emit_tables": (ctypes.c_int, [c_vp, ctypes.c_uint64, c_vp, ctypes.c_uint64, c_vp,
+                                             ctypes.c_uint64, c_vp, ctypes.c_uint64, c_u64p]),
+    "cir_index_emit": (ctypes.c_int, [ctypes.c_int, ctypes.c_uint64, c_vp, c_u64p, c_u64p, c_vp,
+                                      ctypes.c_size_t, c_vp, ctypes.c_size_t,
+                                      ctypes.POINTER(c_vp), c_sizep, c_vp]),
+    "cir_index_emit_dev": (ctypes.c_int, [c_vp, c_vp, ctypes.c_uint64, c_vp, ctypes.c_uint64, c_vp,
+                                          ctypes.c_uint64, c_vp, ctypes.c_uint64, c_vp, c_vp]),
+    "cir_index_memory_dev": (ctypes.c_int, [c_vp, ctypes.c_int, ctypes.c_uint64, c_vp, c_u64p,
+                                            c_u64p, c_vp, ctypes.c_size_t, ctypes.POINTER(c_vp),
+                                            c_vp, ctypes.POINTER(c_vp), c_sizep, c_vp, c_u64p]),
     "cir_debug_compress_only_dev": (ctypes.c_int, [ctypes.c_uint64, ctypes.c_uint32, c_vp, c_vp]),
     "cir_debug_relay_blocks": (ctypes.c_uint64, [ctypes.c_uint64, ctypes.c_uint64]),
     "cir_debug_device_identity": (ctypes.c_int, [ctypes.c_int, ctypes.c_char_p, ctypes.c_size_t,

@@ -4,6 +4,9 @@
 #include <stdint.h>
 
 namespace cir {
+namespace emit {
+struct Tables;  // emit.hpp
+}
 namespace dev {
 
 constexpr int kThreads = 256;  // 4 waves per workgroup (every kernel but the two below)
@@ -400,6 +403,24 @@ inline uint64_t sketch_work_bytes(uint64_t n) {
 hipError_t launch_sketch(const uint8_t* digests, uint64_t n, uint32_t k, uint64_t* keys,
                          uint64_t* work, uint64_t* res, hipStream_t s,
                          const hipEvent_t* tev = nullptr);
+
+// The body text of an index from digests in device memory (emit.hip;
+// cir_index_emit_dev; the rule is emit.hpp): every byte of body[0,
+// round_up(t.body_len, 16)) is written and nothing else (body 16-B aligned);
+// res: kEmitResFields u64 {pieces whose literal or block range lies outside the
+// arrays: their bytes are 0}, zeroed here, all on `s`.  Unchecked: t.npieces <=
+// emit::kMaxPieces, t.body_len <= kEmitMaxBody, t.ndigests <= kEmitMaxDigests.
+constexpr int kEmitResFields = 1;
+constexpr uint64_t kEmitMaxBody = 1ull << 40;     // the grid: 2^36 lanes of 16 bytes
+constexpr uint64_t kEmitMaxDigests = 1ull << 40;  // 65 x and 32 x a block ordinal stay in u64
+hipError_t launch_emit_text(const emit::Tables& t, uint8_t* body, uint64_t* res, hipStream_t s);
+// The descriptors of the blocks of files in device memory (emit.hip;
+// cir_index_memory_dev): off[g], len[g] for every g < nblocks from the table of
+// non-empty files (emit::kFileWords u64 each {first_block, base offset, size},
+// first_block ascending), on `s`.  Unchecked: bs != 0 and below 2^32, nblocks <
+// 2^32.
+hipError_t launch_mem_desc(const uint64_t* files, uint64_t nfiles, uint64_t bs, uint64_t nblocks,
+                           uint64_t* off, uint32_t* len, hipStream_t s);
 
 // nlanes x `lines` register-only compressions (diagnostic VALU ceiling).
 hipError_t launch_compress_only(uint64_t nlanes, uint32_t lines, uint8_t* out, hipStream_t s);

@@ -1420,6 +1420,111 @@ int cir_index_get_hash(const uint8_t* index, size_t len, uint8_t* id_out, size_t
  * alike; CIR_FOOTER_GPU as one descriptor on the GPU. */
 int cir_index_rewrite(cir_ctx* ctx, const uint8_t* in, size_t len, uint8_t** out, size_t* out_len);
 
+/* ---- an index of files that are not in a file system ------------------- */
+
+/* The index of a flat list of regular files, for bytes that no directory holds: tensors,
+ * checkpoints, generated data.  The reference has no counterpart: its indexes come from a
+ * directory scan (src/client/sync/uploads.rs:49-59) or from a parsed index re-emitted
+ * (src/cluster/download.rs:266-319).  The rule is ciruela_amd/csrc/emit.hpp.
+ *
+ * Input, as parallel arrays in the caller's order: file i's path is paths[path_off[i] ..
+ * path_off[i + 1]) (raw bytes, nfiles + 1 offsets, no terminators), its size sizes[i], its
+ * executable flag exe[i] != 0 (exe == NULL: none).  Digests are one flat list of 32 bytes each,
+ * file i's behind file i - 1's in that same order -- not in emission order --, sizes[i] /
+ * block_size + (sizes[i] % block_size != 0) per file.
+ *
+ * Tree: a path is '/' followed by components separated by single '/'; no component is empty, "."
+ * or ".."; no NUL byte; no path twice; no path that is both a file and a directory (the checks of
+ * cir_index_rewrite's tree: InvalidPath, PathConflict).  The directories are those the paths
+ * imply, plus "/".  A violation is CIR_EINVAL with the path in cir_last_error, decided before
+ * anything is allocated on or sent to a device.
+ *
+ * Text: exactly what cir_scan_v1 emits for a directory that holds these files: the header line;
+ * per directory its line, its files in bytewise name order, then its subdirectories in bytewise
+ * name order, recursively; a size-0 file carries no token; the footer line is H(body).  No file
+ * at all gives the body "/\n".  Symlinks and empty directories cannot be expressed.
+ *
+ * Layout: the body is a sequence of pieces, one per file in emission order (one piece with the
+ * literal "/" when there is no file).  A piece is CIR_EMIT_PIECE_WORDS u64 {out_off, lit_off,
+ * lit_len, first_block, nblk}: at body offset out_off stand lit_len bytes of the literal arena
+ * from lit_off (the directory lines since the previous file, then the file line's head through
+ * the size digits), then nblk tokens (' ' + 64 lower-case hex digits) of the digests first_block
+ * .. first_block + nblk - 1, then '\n'. */
+#define CIR_EMIT_PIECE_WORDS 5
+#define CIR_EMIT_RES_FIELDS 1
+
+/* The layout of a file list: *pieces_out (malloc'd, cir_free; *npieces pieces), *lits_out
+ * (malloc'd; *lits_len bytes), first_block_out (nullable; nfiles u64: where file i's digests
+ * start in the flat list), *nblocks and *body_len.  What a caller of cir_index_emit_dev uploads.
+ * Pure, host-only.  CIR_EINVAL: as above, a block_size outside 1 .. 2^32-1, more than 2^31-1
+ * blocks. */
+int cir_index_emit_layout(uint64_t block_size, const uint8_t* paths, const uint64_t* path_off,
+                          const uint64_t* sizes, const uint8_t* exe, size_t nfiles,
+                          uint64_t** pieces_out, size_t* npieces, uint8_t** lits_out,
+                          size_t* lits_len, uint64_t* first_block_out, uint64_t* nblocks,
+                          uint64_t* body_len);
+
+/* The body from its tables on the host: the function the kernel of cir_index_emit_dev runs, 16
+ * bytes at a time, with the same guards.  body holds body_len rounded up to 16 bytes; every one
+ * of them is written, the padding as 0.  res[0] = pieces whose literal range lies outside [0,
+ * lits_len) or whose block range lies outside [0, ndigests): every byte of such a piece is 0 and
+ * nothing is read through it (exact for tables whose out_off strictly ascends); bytes that no
+ * piece covers are 0.  Pure, host-only.  CIR_EINVAL: a null array of non-zero length, npieces >
+ * 2^32-1, body_len or ndigests > 2^40. */
+int cir_index_emit_tables(const uint8_t* digests, uint64_t ndigests, const uint64_t* pieces,
+                          uint64_t npieces, const uint8_t* lits, uint64_t lits_len, uint8_t* body,
+                          uint64_t body_len, uint64_t res[CIR_EMIT_RES_FIELDS]);
+
+/* The host form: *index_out = the malloc'd index (cir_free), *len_out its length, image_id
+ * (nullable, 32 bytes) = the footer digest.  Needs no context and no device.  CIR_EINVAL: as
+ * above, an unknown hash type, ndigests other than the sizes ask for. */
+int cir_index_emit(int hash_type, uint64_t block_size, const uint8_t* paths,
+                   const uint64_t* path_off, const uint64_t* sizes, const uint8_t* exe,
+                   size_t nfiles, const uint8_t* digests, size_t ndigests, uint8_t** index_out,
+                   size_t* len_out, uint8_t image_id[CIR_DIGEST_BYTES]);
+
+/* cir_index_emit_tables on the device: digests, pieces and literals in device memory to the body
+ * in device memory (d_body: 16-byte aligned, body_len rounded up to 16 bytes; d_pieces and d_res
+ * 8-byte aligned).  One lane owns 16 aligned bytes of the body and stores only those, so the
+ * call writes every byte of d_body[0, round_up(body_len, 16)) and d_res[0], and nothing else,
+ * whatever the tables hold; d_res[0] as res[0] above (a memset and one launch).  Like every *_dev
+ * call it allocates nothing, synchronises nothing and runs on `stream` alone; ctx may be NULL and
+ * is not used.  CIR_EINVAL, decided before any HIP call: as cir_index_emit_tables, or a
+ * misaligned pointer. */
+int cir_index_emit_dev(cir_ctx* ctx, const uint8_t* d_digests, uint64_t ndigests,
+                       const uint64_t* d_pieces, uint64_t npieces, const uint8_t* d_lits,
+                       uint64_t lits_len, uint8_t* d_body, uint64_t body_len, uint64_t* d_res,
+                       void* stream);
+
+/* The index of files held in device memory: file i's bytes are d_data[i][0 .. sizes[i]) on the
+ * device of `stream` (any alignment; ignored for a size-0 file), which must be one of ctx's.
+ * The host validates the list and lays the body out; the file table (24 bytes per non-empty
+ * file), the pieces and the literals go up; on `stream` a kernel writes one descriptor per block,
+ * the blocks are hashed as one batch by cir_hash_blocks_dev_ht's routing over the lowest pointer
+ * as the arena, and cir_index_emit_dev's kernel writes the body, which comes down; the footer is
+ * hashed on the calling thread.  All of it is queued behind whatever the caller queued on
+ * `stream` before: data still being produced there needs no synchronise first.  The call
+ * returns after its own synchronise; its device buffers are allocated and freed inside the call
+ * and nothing stays on the device; the caller's current device is restored.
+ *
+ * CIR_EMIT=host (read per call) hashes on the device, downloads the digests and emits with
+ * cir_index_emit's code; the index is byte-identical.  CIR_TRACE=1: one "cir index_memory:" line
+ * with the laps hash, emit, download, footer.
+ *
+ * CIR_EINVAL: as cir_index_emit, a null ctx, a device that is not ctx's, a null pointer of a
+ * non-empty file, more than 2^31-1 blocks (one descriptor batch).  CIR_EIO: the emit kernel
+ * counted a piece outside its arrays (the tables are the call's own: a defect).
+ *
+ * stats: [0] blocks, [1] 1 if the device emitted the text, 0 if the host did, [2] files, [3]
+ * body bytes, [4] bytes uploaded, [5] bytes downloaded. */
+#define CIR_MEMINDEX_STATS_FIELDS 6
+int cir_index_memory_dev(cir_ctx* ctx, int hash_type, uint64_t block_size, const uint8_t* paths,
+                         const uint64_t* path_off, const uint64_t* sizes, const uint8_t* exe,
+                         size_t nfiles, const void* const* d_data, void* stream,
+                         uint8_t** index_out, size_t* len_out,
+                         uint8_t image_id[CIR_DIGEST_BYTES],
+                         uint64_t stats[CIR_MEMINDEX_STATS_FIELDS]);
+
 /* ---- consumers of the index (host bookkeeping) ------------------------ */
 
 /* InMemoryIndexes (src/index.rs:53-124): ImageId -> index bytes. */
