@@ -4,6 +4,7 @@
 #   make oracle     -> oracle/build/liboracle_blake2b.so (test infrastructure)
 #   make sketch_fuzz -> build/sketch_fuzz (the sketch rule under ASan + UBSan; not in `all`)
 #   make emit_fuzz  -> build/emit_fuzz (the emit rule under ASan + UBSan; not in `all`)
+#   make scatter_fuzz -> build/scatter_fuzz (the scatter rule under ASan + UBSan; not in `all`)
 #   make asan/tsan  -> build/host_{asan,tsan}_driver (host code under the
 #                      sanitizers; `make sanitizers` = both; not in `all`)
 HIPCC ?= /opt/rocm/bin/hipcc
@@ -22,7 +23,8 @@ CLI := bin/ciruela-index
 
 SRCS_HIP := $(CSRC)/kernels.hip $(CSRC)/order.hip $(CSRC)/join.hip \
             $(CSRC)/idxscan.hip $(CSRC)/extents.hip $(CSRC)/repeats.hip \
-            $(CSRC)/files.hip $(CSRC)/plan.hip $(CSRC)/sketch.hip $(CSRC)/emit.hip
+            $(CSRC)/files.hip $(CSRC)/plan.hip $(CSRC)/sketch.hip $(CSRC)/emit.hip \
+            $(CSRC)/scatter.hip
 SRCS_CPP := $(CSRC)/runtime.cpp $(CSRC)/dirsig.cpp $(CSRC)/scan.cpp $(CSRC)/check.cpp \
             $(CSRC)/links.cpp $(CSRC)/sources.cpp $(CSRC)/repeats.cpp $(CSRC)/idxscan.cpp \
             $(CSRC)/files.cpp $(CSRC)/copies.cpp $(CSRC)/plan.cpp $(CSRC)/sketch.cpp $(CSRC)/memindex.cpp $(CSRC)/devcall.cpp $(CSRC)/registry.cpp $(CSRC)/blake2b_host.cpp \
@@ -112,6 +114,14 @@ build/emit_fuzz: tools/emit_fuzz.cpp $(CSRC)/emit.hpp $(CSRC)/dirsig.hpp $(CSRC)
 	    -I$(CSRC) tools/emit_fuzz.cpp $(CSRC)/dirsig.cpp -o $@
 emit_fuzz: build/emit_fuzz
 
+# the scatter rule (scatter.hpp) over pack.hpp's runs under ASan + UBSan: a
+# stand-alone host program (tools/scatter_fuzz.cpp), no device code
+build/scatter_fuzz: tools/scatter_fuzz.cpp $(CSRC)/scatter.hpp $(CSRC)/pack.hpp
+	@mkdir -p build
+	$(CXX) -std=c++17 -O1 -g -fsanitize=address,undefined -fno-sanitize-recover=all \
+	    -I$(CSRC) tools/scatter_fuzz.cpp -o $@
+scatter_fuzz: build/scatter_fuzz
+
 oracle:
 	$(MAKE) -C oracle
 
@@ -119,4 +129,4 @@ clean:
 	rm -rf build $(LIB) $(CLI)
 	$(MAKE) -C oracle clean
 
-.PHONY: all oracle clean asan tsan sanitizers sketch_fuzz emit_fuzz
+.PHONY: all oracle clean asan tsan sanitizers sketch_fuzz emit_fuzz scatter_fuzz

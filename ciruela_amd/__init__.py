@@ -97,6 +97,10 @@ index_memory, index_emit,       the index and ImageId of files that no directory
                                 inverse of index_digests; equal to v1.scan of a
                                 directory holding the same files (the reference indexes
                                 directories only: src/client/sync/uploads.rs:49-59)
+load_image,                     the way back: an image directory read into device
+  Context.load_blocks           buffers and verified there, check_blocks that keeps
+                                what it read (the reference's consumers read committed
+                                files unchecked: src/daemon/disk/commit.rs:51-117)
 =============================  ==============================================
 
 All hashing runs on gfx950 through the library; there is no CPU fallback.
@@ -119,7 +123,7 @@ __all__ = [
     "block_repeats", "RepeatsResult",
     "index_digests", "IndexDigests", "file_sources", "file_copies", "check_links_at",
     "fetch_plan", "PlanResult", "index_sketch", "sketch_rank", "sketch_key",
-    "index_memory", "index_emit", "index_emit_layout", "index_emit_tables",
+    "index_memory", "index_emit", "index_emit_layout", "index_emit_tables", "load_image",
 ]
 
 DEFAULT_BLOCK_SIZE = 32768
@@ -692,6 +696,62 @@ class Context:
         return BlocksResult(index, nblk.value, bits, list(states), errnos,
                             dict(zip(self.BLOCKS_STATS_FIELDS, list(stats))))
 
+    LOAD_STATS_FIELDS = BLOCKS_STATS_FIELDS + ("scattered_bytes", "skipped")
+
+    def load_blocks(self, root, index, buffers, threads=0, dir_fd=None, stream=0):
+        """check_blocks that keeps what it read (cir_load_blocks): the bytes of
+        every block it read stand in the caller's device buffers afterwards,
+        and the BlocksResult says which of them are the index's.  buffers: per
+        file entry, in index order, None (a non-empty file is then "skipped":
+        not opened, not read), a device pointer as int, or a (ptr, nbytes) pair
+        or anything with data_ptr() and a byte count (a torch tensor); a span
+        shorter than its entry is a ValueError.  The buffers live on the device
+        of `stream`, behind whose earlier work the first byte lands; the call
+        returns when the buffers are filled."""
+        if len(index):
+            ptr, keep = _buf(index)
+        else:  # (an empty index is a parse error, not a null argument)
+            keep = ctypes.create_string_buffer(1)
+            ptr = ctypes.cast(keep, ctypes.c_void_p)
+        if root is None and dir_fd is None:
+            raise ValueError("load_blocks needs a root path or a directory fd")
+        fd = -100 if dir_fd is None else dir_fd  # AT_FDCWD
+        buffers = list(buffers)
+        ptrs = []
+        sizes = None
+        for i, b in enumerate(buffers):
+            if b is None:
+                ptrs.append(None)
+            elif isinstance(b, int):
+                ptrs.append(b or None)
+            else:
+                p, nbytes = _device_span(b)
+                if sizes is None:
+                    sizes = [size for _, size, _ in _file_blocks(index)[0]]
+                if i < len(sizes) and nbytes < sizes[i]:
+                    raise ValueError("buffer %d holds %d bytes, its entry %d" % (i, nbytes, sizes[i]))
+                ptrs.append(p or None)
+        n = len(ptrs)
+        d_data = (ctypes.c_void_p * max(n, 1))(*ptrs)
+        have = ctypes.c_void_p()
+        nblk = ctypes.c_uint64()
+        state = ctypes.c_void_p()
+        errs = ctypes.c_void_p()
+        nfiles = ctypes.c_size_t()
+        stats = (ctypes.c_uint64 * _n.CIR_LOAD_STATS_FIELDS)()
+        _n.check(_n.lib.cir_load_blocks(self._h, fd, None if root is None else os.fsencode(root),
+                                        ptr, len(index), threads, d_data, n, stream,
+                                        ctypes.byref(have), ctypes.byref(nblk), ctypes.byref(state),
+                                        ctypes.byref(errs), ctypes.byref(nfiles), stats))
+        del keep, buffers
+        nf = nfiles.value
+        bits = _n.take_buffer(have.value, 8 * ((nblk.value + 63) // 64))
+        states = _n.take_buffer(state.value, nf)
+        raw = _n.take_buffer(errs.value, 4 * nf)
+        errnos = list((ctypes.c_int32 * nf).from_buffer_copy(raw)) if nf else []
+        return BlocksResult(index, nblk.value, bits, list(states), errnos,
+                            dict(zip(self.LOAD_STATS_FIELDS, list(stats))))
+
     def scan(self, config):
         dirs = [os.fsencode(d) for d, _ in config._dirs]
         pres = [p.encode() for _, p in config._dirs]
@@ -881,9 +941,10 @@ class BlocksResult:
     """Verdict of check_blocks.  nblk: the index's blocks, numbered in index
     order over its file entries; have: their bitmap as bytes (bit g & 7 of
     byte g >> 3), has(g) one bit of it.  Per file entry, in index order:
-    states ("complete", "absent", "partial" or "blocked"), long (the file is
-    longer than its entry and is to be truncated before commit), errnos (of a
-    "blocked", else 0).  complete: every file is complete.  missing(): the
+    states ("complete", "absent", "partial" or "blocked"; from load_blocks
+    also "skipped": a non-empty file that was given no buffer), long (the file
+    is longer than its entry and is to be truncated before commit), errnos (of
+    a "blocked", else 0).  complete: every file is complete.  missing(): the
     (path as raw bytes, byte offset) of every block that is not there, in
     index order -- what fill_blocks would queue
     (src/daemon/tracking/progress.rs:136-151)."""
@@ -891,12 +952,14 @@ class BlocksResult:
     __slots__ = ("nblk", "have", "states", "long", "errnos", "stats", "_index")
     STATES = {_n.CIR_FILE_COMPLETE: "complete", _n.CIR_FILE_ABSENT: "absent",
               _n.CIR_FILE_PARTIAL: "partial", _n.CIR_FILE_BLOCKED: "blocked"}
+    SKIPPED = "skipped"
 
     def __init__(self, index, nblk, have, states, errnos, stats):
         self._index = index  # (split into lines only when missing() is asked for)
         self.nblk = nblk
         self.have = bytes(have)  # (little-endian u64 words: byte order is bit order)
-        self.states = [self.STATES[s & 3] for s in states]
+        self.states = [self.SKIPPED if s & 0x7f == _n.CIR_FILE_SKIPPED else self.STATES[s & 3]
+                       for s in states]
         self.long = [bool(s & _n.CIR_FILE_LONG) for s in states]
         self.errnos = list(errnos)
         self.stats = stats
@@ -1509,6 +1572,33 @@ def index_memory(files, block_size=DEFAULT_BLOCK_SIZE, hash_type=None, context=N
 
 _default = None
 _default_lock = threading.Lock()
+
+
+def load_image(root, index, context=None, only=None, threads=0):
+    """An image directory read into device memory, verified (cir_load_blocks):
+    one torch.uint8 tensor per non-empty file entry of `index` -- with `only`
+    (paths as raw bytes or str) for those entries alone --, on the context's
+    first device, filled from the directory `root`.  Returns ({path as raw
+    bytes: tensor}, BlocksResult): a "complete" file's tensor is the file, the
+    result's bits say which blocks of the others are the index's."""
+    import torch
+    ctx = context or default_context()
+    dev = torch.device("cuda", ctx.devices()[0])
+    files, _ = _file_blocks(index)
+    keep = None if only is None else {os.fsencode(p) if isinstance(p, str) else bytes(p)
+                                      for p in only}
+    tensors = {}
+    buffers = []
+    for path, size, _ in files:
+        if size and (keep is None or path in keep):
+            tensors[path] = torch.empty(size, dtype=torch.uint8, device=dev)
+            buffers.append(tensors[path])
+        else:
+            buffers.append(None)
+    with torch.cuda.device(dev):
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        res = ctx.load_blocks(root, index, buffers, threads=threads, stream=stream)
+    return tensors, res
 
 
 def default_context():

@@ -1,7 +1,9 @@
 // cir_check_index: the re-hash loop of commit_image over a whole image
 // (and, below it, cir_check_links: the same pipeline with a verdict per file
-// for the hardlink candidates of check_and_hardlink, and cir_check_blocks: the
-// same pipeline with a verdict per block, for the resume of a partial image).
+// for the hardlink candidates of check_and_hardlink, cir_check_blocks: the
+// same pipeline with a verdict per block, for the resume of a partial image,
+// and cir_load_blocks: cir_check_blocks that keeps the bytes it read, in
+// device buffers of the caller's).
 //
 // Reference: commit_image (src/daemon/disk/commit.rs:51-117) walks the
 // index's entries in order, re-hashes every non-empty file
@@ -64,6 +66,7 @@
 #include "linkpath.hpp"
 #include "pack.hpp"
 #include "runtime.hpp"
+#include "scatter.hpp"
 #include "stripes.hpp"
 
 namespace cir {
@@ -1017,6 +1020,14 @@ int links_impl(cir_ctx* ctx, const uint8_t* index, size_t len, const int* src_di
 // run's bits into the device's bitmap (bits.hpp).  Several devices take
 // stripes of the global block order, each into a bitmap of its own; every
 // block has one owner, so the merge is an OR and does not depend on timing.
+//
+// cir_load_blocks is the same pipeline with a destination per file (Blocks::
+// dests): pack appends one scatter record (scatter.hpp) per packed run to the
+// slot's table, the table goes up with the descriptors and launch_scatter_runs
+// copies the batch's runs from the slot's device twin to the files' buffers
+// behind the compare, on the compute stream.  A non-empty file without a
+// destination is left out of the work list: nothing of it is looked at.  One
+// device takes the whole image, the one the caller's stream belongs to.
 
 // What the looks and the reads found of a file.
 constexpr uint8_t kLookAbsent = 1, kLookBlocked = 2, kLookShort = 4, kLookLong = 8;
@@ -1029,6 +1040,10 @@ struct Blocks : Layout {
   std::vector<uint8_t> look;
   std::vector<int32_t> err;
   std::atomic<uint64_t> n_bytes{0}, n_batches{0}, n_unread{0};
+  // cir_load_blocks: each file entry's device buffer (null: cir_check_blocks),
+  // the bytes and records scattered, and the records a scatter found bad
+  void* const* dests = nullptr;
+  std::atomic<uint64_t> n_scat_bytes{0}, n_scat_recs{0}, n_scat_bad{0};
 
   void report(size_t item, uint8_t bits, int e = 0) {
     std::lock_guard<std::mutex> lk(mu);
@@ -1106,10 +1121,12 @@ int blocks_range(cir_ctx* ctx, Device& d, Blocks& B, unsigned threads, const Blo
   std::vector<BitRun> runs[Device::kSlots];  // per slot in flight
   Batch b;
   uint64_t file_bytes = 0;
+  uint64_t nscat = 0, nunits = 0;  // the batch's scatter table (with B.dests)
   std::vector<ReadJob> jobs;
   auto retire = [&](int k, Slot& s) {
     const uint64_t* bits = reinterpret_cast<const uint64_t*>(s.h_bits + kBitsResHead);
     for (const BitRun& r : runs[k]) copy_bits(have, r.global, bits, r.at, r.count);
+    if (B.dests) B.n_scat_bad.fetch_add(s.h_scat[0]);
   };
   auto pack = [&](int k, Slot& s) {
     std::vector<BitRun>& rs = runs[k];
@@ -1117,6 +1134,7 @@ int blocks_range(cir_ctx* ctx, Device& d, Blocks& B, unsigned threads, const Blo
     jobs.clear();
     b = Batch();
     file_bytes = 0;
+    nscat = nunits = 0;
     while (cur.here() && b.n < sz.cap_blk) {
       const size_t item = work[cur.ui];
       const Item& it = B.items[item];
@@ -1150,6 +1168,10 @@ int blocks_range(cir_ctx* ctx, Device& d, Blocks& B, unsigned threads, const Blo
         rs.back().count += r.take;  // (neighbouring files, both complete: one run)
       else
         rs.push_back({r.at, it.first_blk + fblk, r.take});
+      if (B.dests)  // (at most one record per block: <= cap_blk)
+        nunits = scatter::record_of(r, (uint64_t)reinterpret_cast<uintptr_t>(B.dests[item]), fblk,
+                                    bs, nunits,
+                                    s.h_scat + kScatHead + scatter::kRunWords * nscat++);
       file_bytes += r.bytes;
       cur.advance(r.take);
     }
@@ -1159,27 +1181,51 @@ int blocks_range(cir_ctx* ctx, Device& d, Blocks& B, unsigned threads, const Blo
     run_reads(B, jobs, threads, [&](size_t i, int e) { B.report(jobs[i].tag, kLookBlocked, e); });
   };
   auto submit = [&](int, Slot& s) -> int {
-    const int rc = slot_submit_blocks(d, s, std::max<uint64_t>(b.used, 16), b.n, B.ht);
+    const uint64_t used = std::max<uint64_t>(b.used, 16);
+    const int rc = B.dests ? slot_submit_load(d, s, used, b.n, B.ht, nscat, nunits)
+                           : slot_submit_blocks(d, s, used, b.n, B.ht);
     if (rc) return rc;
+    if (B.dests) {
+      B.n_scat_bytes.fetch_add(file_bytes);
+      B.n_scat_recs.fetch_add(nscat);
+    }
     B.n_bytes.fetch_add(file_bytes);
     B.n_batches.fetch_add(1);
     return CIR_OK;
   };
   Laps laps(trace_enabled());
   const int rc = rotate_slots(
-      d, sz, &Device::ensure_blocks, laps, [&] { return cur.more(); }, retire, pack, read, submit);
+      d, sz, B.dests ? &Device::ensure_load : &Device::ensure_blocks, laps,
+      [&] { return cur.more(); }, retire, pack, read, submit);
   if (rc) return rc;
-  if (laps.on)
+  if (laps.on) {
     fprintf(stderr,
-            "cir check_blocks dev %d: %llu batches; packer's look and run table %.2f ms, "
+            "cir %s dev %d: %llu batches; packer's look and run table %.2f ms, "
             "reads %.2f ms, submit %.2f ms, waiting for results and bit runs %.2f ms\n",
-            d.id, (unsigned long long)laps.batches, laps.pack, laps.read, laps.submit, laps.wait);
+            B.dests ? "load_blocks" : "check_blocks", d.id, (unsigned long long)laps.batches,
+            laps.pack, laps.read, laps.submit, laps.wait);
+    if (B.dests)
+      fprintf(stderr, "cir load_blocks dev %d: %llu scatter records, %.1f per batch, %llu bytes\n",
+              d.id, (unsigned long long)B.n_scat_recs.load(),
+              laps.batches ? (double)B.n_scat_recs.load() / (double)laps.batches : 0.0,
+              (unsigned long long)B.n_scat_bytes.load());
+  }
   return CIR_OK;
 }
 
+// cir_load_blocks' own arguments: a device buffer per file entry, and the
+// caller's stream.
+struct LoadArgs {
+  void* const* d_data;
+  size_t ndata;
+  void* stream;
+};
+
+// load == nullptr: cir_check_blocks.
 int blocks_impl(cir_ctx* ctx, int dirfd, const char* dir, const uint8_t* index, size_t len,
                 uint32_t threads, uint64_t** have_out, uint64_t* nblk_out, uint8_t** state_out,
-                int32_t** errno_out, size_t* nfiles_out, uint64_t* stats) {
+                int32_t** errno_out, size_t* nfiles_out, uint64_t* stats,
+                const LoadArgs* load = nullptr) {
   if (!ctx || !index || !have_out || !nblk_out || !state_out || !nfiles_out || !stats)
     return fail(CIR_EINVAL, "null pointer");
   *have_out = nullptr;
@@ -1187,7 +1233,7 @@ int blocks_impl(cir_ctx* ctx, int dirfd, const char* dir, const uint8_t* index, 
   *state_out = nullptr;
   if (errno_out) *errno_out = nullptr;
   *nfiles_out = 0;
-  for (int i = 0; i < CIR_BLOCKS_STATS_FIELDS; ++i) stats[i] = 0;
+  for (int i = 0; i < (load ? CIR_LOAD_STATS_FIELDS : CIR_BLOCKS_STATS_FIELDS); ++i) stats[i] = 0;
   const auto t_start = std::chrono::steady_clock::now();
   auto ms_since = [](std::chrono::steady_clock::time_point t) {
     return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t).count();
@@ -1196,9 +1242,27 @@ int blocks_impl(cir_ctx* ctx, int dirfd, const char* dir, const uint8_t* index, 
   int rc = load_index(index, len, &B);
   if (rc) return rc;
   const size_t nfiles = B.items.size();
+  uint64_t n_skipped = 0;
+  Device* load_dev = nullptr;
+  if (load) {
+    if (load->ndata != nfiles)
+      return fail(CIR_EINVAL, "ndata is " + std::to_string(load->ndata) + ", the index has " +
+                                  std::to_string(nfiles) + " file entries");
+    if (nfiles && !load->d_data) return fail(CIR_EINVAL, "null pointer");
+    load_dev = stream_device(ctx, (hipStream_t)load->stream);
+    if (!load_dev) return fail(CIR_EINVAL, "stream device is not part of the context");
+    B.dests = load->d_data;
+  }
+  // (a non-empty file without a destination is no work: it is not looked at)
   for (size_t i = 0; i < nfiles; ++i)
-    if (B.items[i].nblk) B.work.push_back(i);
-  // ---- nothing above touched a file or a device
+    if (B.items[i].nblk) {
+      if (!load || load->d_data[i])
+        B.work.push_back(i);
+      else
+        ++n_skipped;
+    }
+  // ---- nothing above touched a file or a device (a load asked which device
+  // its stream belongs to)
   const double ms_parse = ms_since(t_start);
   const auto t_empty = std::chrono::steady_clock::now();
   rc = open_image(B, dirfd, dir);
@@ -1232,19 +1296,40 @@ int blocks_impl(cir_ctx* ctx, int dirfd, const char* dir, const uint8_t* index, 
   // a bitmap per device (stripes do not end on word boundaries); device 0
   // writes into the result itself
   std::vector<std::vector<uint64_t>> part(ctx->devs.size());
-  rc = run_striped(ctx, B.nblk_total, B.bs, threads,
-                   [&](size_t i, Device& d, unsigned per, const BlockRanges& ranges) {
-                     if (i) part[i].assign(nwords, 0);
-                     return blocks_range(ctx, d, B, per, ranges, i ? part[i].data() : outs.have);
-                   });
-  for (const std::vector<uint64_t>& p : part)
-    for (size_t w = 0; w < p.size(); ++w) outs.have[w] |= p[w];
+  if (!load) {
+    rc = run_striped(ctx, B.nblk_total, B.bs, threads,
+                     [&](size_t i, Device& d, unsigned per, const BlockRanges& ranges) {
+                       if (i) part[i].assign(nwords, 0);
+                       return blocks_range(ctx, d, B, per, ranges, i ? part[i].data() : outs.have);
+                     });
+    for (const std::vector<uint64_t>& p : part)
+      for (size_t w = 0; w < p.size(); ++w) outs.have[w] |= p[w];
+  } else if (!B.work.empty()) {
+    // One device, the stream's.  Its compute stream -- the scatters run there
+    // -- first waits for what the caller queued on `stream`: a producer or an
+    // earlier user of the buffers is done before the first byte lands.
+    rc = [&]() -> int {
+      DeviceGuard guard;
+      CIR_HIP(hipSetDevice(load_dev->id));
+      hipEvent_t ev = nullptr;
+      CIR_HIP(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
+      hipError_t e = hipEventRecord(ev, (hipStream_t)load->stream);
+      if (e == hipSuccess) e = hipStreamWaitEvent(load_dev->compute, ev, 0);
+      (void)hipEventDestroy(ev);  // (released once it has completed)
+      if (e != hipSuccess) return hip_fail(e, "ordering the compute stream behind the caller's");
+      return blocks_range(ctx, *load_dev, B, threads ? threads : host_copy_threads((size_t)1),
+                          BlockRanges{{0, B.nblk_total}}, outs.have);
+    }();
+    if (!rc && B.n_scat_bad.load())
+      rc = fail(CIR_EIO, "the scatter kernel met a record outside its slot");
+  }
   stats[8] = B.fds.peak.load();
   if (trace_enabled())
     fprintf(stderr,
-            "cir check_blocks: %zu files, %llu blocks; index parse %.2f ms, root and size-0 "
+            "cir %s: %zu files, %llu blocks; index parse %.2f ms, root and size-0 "
             "entries %.2f ms, pipeline %.2f ms\n",
-            nfiles, (unsigned long long)B.nblk_total, ms_parse, ms_empty, ms_since(t_pipe));
+            load ? "load_blocks" : "check_blocks", nfiles, (unsigned long long)B.nblk_total,
+            ms_parse, ms_empty, ms_since(t_pipe));
   if (rc) return rc;
   // the files' states.  A file that is absent or blocked has none of its
   // blocks: whatever a range packed of it before it went is cleared.
@@ -1252,6 +1337,10 @@ int blocks_impl(cir_ctx* ctx, int dirfd, const char* dir, const uint8_t* index, 
     const Item& it = B.items[i];
     const uint8_t lk = B.look[i];
     uint8_t st;
+    if (load && it.nblk && !load->d_data[i]) {  // (no bit of it was ever set)
+      outs.state[i] = CIR_FILE_SKIPPED;
+      continue;
+    }
     if (lk & kLookBlocked)
       st = CIR_FILE_BLOCKED;
     else if (lk & kLookAbsent)
@@ -1275,6 +1364,10 @@ int blocks_impl(cir_ctx* ctx, int dirfd, const char* dir, const uint8_t* index, 
   stats[6] = B.n_bytes.load();
   stats[7] = B.n_batches.load();
   stats[9] = B.n_unread.load();
+  if (load) {
+    stats[10] = B.n_scat_bytes.load();
+    stats[11] = n_skipped;
+  }
   *have_out = outs.have;
   *nblk_out = B.nblk_total;
   *state_out = outs.state;
@@ -1286,8 +1379,62 @@ int blocks_impl(cir_ctx* ctx, int dirfd, const char* dir, const uint8_t* index, 
   return CIR_OK;
 }
 
+// ---- cir_scatter_runs, cir_scatter_runs_dev: the scatter on its own ----------
+
+int check_scatter(const void* src, const void* runs, uint64_t nruns, uint64_t nunits,
+                  const void* res) {
+  if ((nunits && !src) || (nruns && !runs) || !res) return fail(CIR_EINVAL, "null pointer");
+  if (nruns > scatter::kMaxRuns) return fail(CIR_EINVAL, "more than 2^32-1 records");
+  if (nunits > scatter::kMaxUnits) return fail(CIR_EINVAL, "more than 2^32-1 units");
+  return CIR_OK;
+}
+
+int scatter_host_impl(const uint8_t* src, uint64_t src_bytes, const uint64_t* runs, uint64_t nruns,
+                      uint64_t nunits, uint64_t* res) {
+  const int rc = check_scatter(src, runs, nruns, nunits, res);
+  if (rc) return rc;
+  res[0] = scatter::apply_host(src, src_bytes, runs, nruns, nunits);
+  return CIR_OK;
+}
+
+int scatter_dev_impl(const uint8_t* d_src, uint64_t src_bytes, const uint64_t* d_runs,
+                     uint64_t nruns, uint64_t nunits, uint64_t* d_res, void* stream) {
+  const int rc = check_scatter(d_src, d_runs, nruns, nunits, d_res);
+  if (rc) return rc;
+  if (reinterpret_cast<uintptr_t>(d_src) & 15u)
+    return fail(CIR_EINVAL, "d_src must be 16-byte aligned");
+  if ((reinterpret_cast<uintptr_t>(d_runs) | reinterpret_cast<uintptr_t>(d_res)) & 7u)
+    return fail(CIR_EINVAL, "d_runs and d_res must be 8-byte aligned");
+  CIR_HIP(dev::launch_scatter_runs(d_src, src_bytes, d_runs, nruns, nunits, d_res,
+                                   (hipStream_t)stream));
+  return CIR_OK;
+}
+
 }  // namespace
 }  // namespace cir
+
+extern "C" int cir_scatter_runs(const uint8_t* src, uint64_t src_bytes, const uint64_t* runs,
+                                uint64_t nruns, uint64_t nunits,
+                                uint64_t res[CIR_SCATTER_RES_FIELDS]) try {
+  return cir::scatter_host_impl(src, src_bytes, runs, nruns, nunits, res);
+} CIR_CATCH_BOUNDARY
+
+extern "C" int cir_scatter_runs_dev(cir_ctx* ctx, const uint8_t* d_src, uint64_t src_bytes,
+                                    const uint64_t* d_runs, uint64_t nruns, uint64_t nunits,
+                                    uint64_t* d_res, void* stream) try {
+  (void)ctx;  // no scratch of the context's, no side streams
+  return cir::scatter_dev_impl(d_src, src_bytes, d_runs, nruns, nunits, d_res, stream);
+} CIR_CATCH_BOUNDARY
+
+extern "C" int cir_load_blocks(cir_ctx* ctx, int dirfd, const char* dir, const uint8_t* index,
+                               size_t len, uint32_t threads, void* const* d_data, size_t ndata,
+                               void* stream, uint64_t** have_out, uint64_t* nblk_out,
+                               uint8_t** state_out, int32_t** errno_out, size_t* nfiles_out,
+                               uint64_t stats[CIR_LOAD_STATS_FIELDS]) try {
+  const cir::LoadArgs load{d_data, ndata, stream};
+  return cir::blocks_impl(ctx, dirfd, dir, index, len, threads, have_out, nblk_out, state_out,
+                          errno_out, nfiles_out, stats, &load);
+} CIR_CATCH_BOUNDARY
 
 extern "C" int cir_check_blocks(cir_ctx* ctx, int dirfd, const char* dir, const uint8_t* index,
                                 size_t len, uint32_t threads, uint64_t** have_out,

@@ -422,6 +422,18 @@ hipError_t launch_emit_text(const emit::Tables& t, uint8_t* body, uint64_t* res,
 hipError_t launch_mem_desc(const uint64_t* files, uint64_t nfiles, uint64_t bs, uint64_t nblocks,
                            uint64_t* off, uint32_t* len, hipStream_t s);
 
+// The packed runs of a staging slot copied to their places (scatter.hip;
+// cir_scatter_runs_dev, cir_load_blocks; the rule is scatter.hpp): for every
+// sound record {unit_first, src_pos, dst, bytes} of `runs` (scatter::kRunWords
+// u64 each) the bytes src[src_pos, src_pos + bytes) stand at dst afterwards and
+// no other byte is written; res: kScatterResFields u64 {bad records: written
+// nowhere, read nowhere}, zeroed here, all on `s`.  src 16-byte aligned.  No
+// launch when there is neither a unit nor a record.  Unchecked: nruns <=
+// scatter::kMaxRuns, nunits <= scatter::kMaxUnits.
+constexpr int kScatterResFields = 1;
+hipError_t launch_scatter_runs(const uint8_t* src, uint64_t src_bytes, const uint64_t* runs,
+                               uint64_t nruns, uint64_t nunits, uint64_t* res, hipStream_t s);
+
 // nlanes x `lines` register-only compressions (diagnostic VALU ceiling).
 hipError_t launch_compress_only(uint64_t nlanes, uint32_t lines, uint8_t* out, hipStream_t s);
 

@@ -5,6 +5,7 @@
 #include "runtime.hpp"
 
 #include "pool.hpp"
+#include "scatter.hpp"
 
 #include <emmintrin.h>
 #include <errno.h>
@@ -89,6 +90,8 @@ Device::~Device() {
     (void)hipFree(s.d_seg_res);
     (void)hipHostFree(s.h_bits);
     (void)hipFree(s.d_bits);
+    (void)hipHostFree(s.h_scat);
+    (void)hipFree(s.d_scat);
     if (s.copied) (void)hipEventDestroy(s.copied);
     if (s.done) (void)hipEventDestroy(s.done);
     for (hipEvent_t e : {s.t_copy0, s.t_copy1, s.t_hash0, s.t_done})
@@ -380,6 +383,22 @@ int Device::ensure_blocks(Slot& s) {
   return CIR_OK;
 }
 
+int Device::ensure_load(Slot& s) {
+  int rc = ensure_blocks(s);
+  if (rc) return rc;
+  if (s.scat_cap < s.cap_blk) {
+    (void)hipHostFree(s.h_scat);
+    (void)hipFree(s.d_scat);
+    s.h_scat = s.d_scat = nullptr;
+    s.scat_cap = 0;
+    const size_t bytes = 8 * (kScatHead + scatter::kRunWords * s.cap_blk);
+    CIR_HIP(hipHostMalloc((void**)&s.h_scat, bytes, hipHostMallocDefault));
+    CIR_HIP(hipMalloc((void**)&s.d_scat, bytes));
+    s.scat_cap = s.cap_blk;
+  }
+  return CIR_OK;
+}
+
 int Device::ensure_timing(Slot& s) {
   for (hipEvent_t* e : {&s.t_copy0, &s.t_copy1, &s.t_hash0, &s.t_done})
     if (!*e) CIR_HIP(hipEventCreate(e));
@@ -509,7 +528,8 @@ int hash_desc_ordered(Device& d, const uint8_t* arena, const uint64_t* off, cons
 // bytes of one file split into chunk_bs blocks (nblk = ceil(bytes / bs)).
 static int slot_submit_impl(Device& d, Slot& s, uint64_t bytes, uint64_t nblk,
                             uint64_t chunk_bs, int ht, const uint64_t* check_base = nullptr,
-                            uint64_t nseg = 0, bool bits = false) {
+                            uint64_t nseg = 0, bool bits = false, uint64_t nscat = 0,
+                            uint64_t nunits = 0) {
   s.timed = d.record_times || trace_enabled();
   if (s.timed) {
     int rc = d.ensure_timing(s);
@@ -526,6 +546,9 @@ static int slot_submit_impl(Device& d, Slot& s, uint64_t bytes, uint64_t nblk,
     CIR_HIP(hipMemcpyAsync(s.d_want, s.h_out, nblk * 32, hipMemcpyHostToDevice, d.copy));
   if (nseg)
     CIR_HIP(hipMemcpyAsync(s.d_seg_end, s.h_seg_end, nseg * 4, hipMemcpyHostToDevice, d.copy));
+  if (nscat)
+    CIR_HIP(hipMemcpyAsync(s.d_scat + kScatHead, s.h_scat + kScatHead,
+                           8 * scatter::kRunWords * nscat, hipMemcpyHostToDevice, d.copy));
   if (s.timed) CIR_HIP(hipEventRecord(s.t_copy1, d.copy));
   CIR_HIP(hipEventRecord(s.copied, d.copy));
   CIR_HIP(hipStreamWaitEvent(d.compute, s.copied, 0));
@@ -551,6 +574,12 @@ static int slot_submit_impl(Device& d, Slot& s, uint64_t bytes, uint64_t nblk,
                                    reinterpret_cast<uint32_t*>(s.d_bits), d.compute));
     CIR_HIP(hipMemcpyAsync(s.h_bits, s.d_bits, kBitsResHead + 8 * ((nblk + 63) / 64),
                            hipMemcpyDeviceToHost, d.compute));
+    if (nscat) {
+      CIR_HIP(dev::launch_scatter_runs(src, bytes, s.d_scat + kScatHead, nscat, nunits, s.d_scat,
+                                       d.compute));
+      CIR_HIP(hipMemcpyAsync(s.h_scat, s.d_scat, 8 * dev::kScatterResFields,
+                             hipMemcpyDeviceToHost, d.compute));
+    }
   } else {
     CIR_HIP(hipMemcpyAsync(s.h_out, s.d_out, nblk * 32, hipMemcpyDeviceToHost, d.compute));
   }
@@ -581,6 +610,14 @@ int slot_submit_blocks(Device& d, Slot& s, uint64_t bytes, uint64_t nblk, int ht
   if (!s.d_bits || !s.h_bits || s.want_blk < nblk || s.bits_cap < nblk || nblk == 0)
     return fail(CIR_EINVAL, "blocks-mode submit without ensure_blocks");
   return slot_submit_impl(d, s, bytes, nblk, 0, ht, nullptr, 0, true);
+}
+
+int slot_submit_load(Device& d, Slot& s, uint64_t bytes, uint64_t nblk, int ht, uint64_t nscat,
+                     uint64_t nunits) {
+  if (!s.d_bits || !s.h_bits || s.want_blk < nblk || s.bits_cap < nblk || nblk == 0 ||
+      !s.d_scat || !s.h_scat || s.scat_cap < nscat || nscat == 0)
+    return fail(CIR_EINVAL, "load-mode submit without ensure_load");
+  return slot_submit_impl(d, s, bytes, nblk, 0, ht, nullptr, 0, true, nscat, nunits);
 }
 
 int slot_wait(Device& d, Slot& s) {

@@ -98,6 +98,14 @@ struct Slot {
   uint8_t* h_bits = nullptr;
   uint8_t* d_bits = nullptr;
   uint64_t bits_cap = 0;
+  // load mode (cir_load_blocks): the batch's scatter table (scatter.hpp: one
+  // record of 4 u64 per packed run) behind a head of kScatHead u64 whose first
+  // word is the scatter's result {bad records}; pinned host twin, the table
+  // going up and the result coming down; room for scat_cap records, allocated
+  // on the first load
+  uint64_t* h_scat = nullptr;
+  uint64_t* d_scat = nullptr;
+  uint64_t scat_cap = 0;
   hipEvent_t copied = nullptr;  // H2D of this slot finished (copy stream)
   hipEvent_t done = nullptr;    // digests of this slot are back in h_out
   // timing events (created on first use, recorded only while the device's
@@ -226,6 +234,7 @@ struct Device {
   int ensure_check(Slot& s);  // the check-mode buffers, sized to s.cap_blk
   int ensure_links(Slot& s);  // those and the links-mode buffers, sized to s.cap_blk
   int ensure_blocks(Slot& s);  // the check-mode and the blocks-mode buffers, sized to s.cap_blk
+  int ensure_load(Slot& s);    // those and the load-mode table, sized to s.cap_blk
 };
 
 // Every slot a staged loop submitted is waited for before the loop lets go
@@ -271,6 +280,15 @@ int slot_submit_links(Device& d, Slot& s, uint64_t bytes, uint64_t nblk, int ht,
 // the batch matches (the last word's bits at and past nblk are 0).
 constexpr uint64_t kBitsResHead = 16;
 int slot_submit_blocks(Device& d, Slot& s, uint64_t bytes, uint64_t nblk, int ht);
+// Load mode: blocks mode, and the batch's bytes are kept: the nscat records at
+// s.h_scat + kScatHead (nunits units in all) go up with the descriptors, and
+// behind launch_block_bits, in front of the done event, launch_scatter_runs
+// copies the slot's runs to the records' destinations on the compute stream;
+// after slot_wait, s.h_scat[0] = the records the scatter found bad (0 for a
+// table the packer built).
+constexpr uint64_t kScatHead = 2;
+int slot_submit_load(Device& d, Slot& s, uint64_t bytes, uint64_t nblk, int ht, uint64_t nscat,
+                     uint64_t nunits);
 int hash_desc_ordered(Device& d, const uint8_t* arena, const uint64_t* off, const uint32_t* len,
                       uint64_t n, uint8_t* out, hipStream_t s, int ht = CIR_HASH_BLAKE2B_256,
                       bool warm_only = false);

@@ -565,11 +565,94 @@ enum cir_file_state {
   CIR_FILE_BLOCKED = 3
 };
 #define CIR_FILE_LONG 0x80 /* or'ed in: on-disk length exceeds the entry's */
+#define CIR_FILE_SKIPPED 4 /* cir_load_blocks only: a non-empty entry without a destination */
 #define CIR_BLOCKS_STATS_FIELDS 10
 int cir_check_blocks(cir_ctx* ctx, int dirfd, const char* dir, const uint8_t* index, size_t len,
                      uint32_t threads, uint64_t** have_out, uint64_t* nblk_out,
                      uint8_t** state_out, int32_t** errno_out, size_t* nfiles_out,
                      uint64_t stats[CIR_BLOCKS_STATS_FIELDS]);
+
+/* The scatter of cir_load_blocks on its own: packed runs of one source buffer copied to their
+ * places.  The reference has no counterpart.  The rule is ciruela_amd/csrc/scatter.hpp.
+ *
+ * Table: nruns records of CIR_SCATTER_RUN_WORDS u64 {unit_first, src_pos, dst, bytes}: `bytes`
+ * (> 0) bytes at byte src_pos of the source (a multiple of 16) go to the address dst (any
+ * alignment).  A record has ceil(bytes / 16) units of 16 bytes; unit_first is the unit count of
+ * all earlier records and nunits that of the whole table.  For every sound record the bytes
+ * src[src_pos, src_pos + bytes) stand at dst afterwards, and no other byte is written: a unit
+ * stores only its own bytes, so the destinations of different records must not overlap and need
+ * no padding.
+ *
+ * res[0] = the bad records: src_pos not a multiple of 16, bytes 0, a source range outside [0,
+ * src_bytes), or a unit_first that is not the previous record's plus its units (0 for the first
+ * record; the last record must end at nunits).  A bad record is written nowhere and read nowhere;
+ * the count is exact whatever the table holds.
+ *
+ * cir_scatter_runs is the host form (dst: host addresses; pure, host-only).  CIR_EINVAL: a null
+ * pointer with a non-zero count, a null res, nruns or nunits above 2^32 - 1. */
+#define CIR_SCATTER_RUN_WORDS 4
+#define CIR_SCATTER_RES_FIELDS 1
+int cir_scatter_runs(const uint8_t* src, uint64_t src_bytes, const uint64_t* runs, uint64_t nruns,
+                     uint64_t nunits, uint64_t res[CIR_SCATTER_RES_FIELDS]);
+
+/* The same on the device: source, table and destinations in device memory (d_src 16-byte
+ * aligned, d_runs and d_res 8-byte aligned).  One lane per unit: one 16-byte load from the source
+ * (a unit that reaches past src_bytes loads its bytes singly), one 16-byte store where the unit
+ * is whole and its destination 16-byte aligned, narrower stores otherwise; no atomic touches a
+ * destination.  Every word of d_res[CIR_SCATTER_RES_FIELDS] is written (a memset and one launch;
+ * no launch for an empty table).  Like every *_dev call it allocates nothing, synchronises
+ * nothing and runs on `stream` alone; ctx may be NULL and is not used.  CIR_EINVAL, decided
+ * before any HIP call: as cir_scatter_runs, or a misaligned pointer. */
+int cir_scatter_runs_dev(cir_ctx* ctx, const uint8_t* d_src, uint64_t src_bytes,
+                         const uint64_t* d_runs, uint64_t nruns, uint64_t nunits, uint64_t* d_res,
+                         void* stream);
+
+/* cir_check_blocks that keeps what it read: an image directory read into device memory,
+ * verified.  The way back from cir_index_memory_dev; the reference has no counterpart (its
+ * consumers read committed files from disk unchecked: commit_image, src/daemon/disk/commit.rs:
+ * 51-117, is the last look at the bytes).
+ *
+ * Root, hash type, block size, threads, block numbering, file ordinals, *have_out, *state_out and
+ * *errno_out are exactly cir_check_blocks'.
+ *
+ * Destinations: d_data[i] belongs to file ordinal i; ndata must be the index's file entries,
+ * else CIR_EINVAL after the parse and before any I/O.  Each is at least the entry's size, of any
+ * alignment, on the device of `stream`, which must be one of ctx's.  For a size-0 entry d_data[i]
+ * is ignored (the host judges the entry as in cir_check_blocks).  A non-empty entry with
+ * d_data[i] == NULL is not looked at, not opened and not read: its bits are 0 and its state is
+ * CIR_FILE_SKIPPED (each rank of a job loads its own shard files).
+ *
+ * Afterwards the bytes of every block that was read -- exactly the blocks cir_check_blocks would
+ * have read -- stand at d_data[file] + j * block_size, and the block's bit says whether those
+ * bytes are the index's: a COMPLETE file's buffer is the file.  Bytes of blocks that were not
+ * read are untouched; a file that is not COMPLETE has unspecified content in the positions of
+ * the blocks that were read.  Nothing is written outside [d_data[i], d_data[i] + size_i).
+ *
+ * Stream order: before the first batch the device's compute stream waits for an event recorded
+ * on `stream`, so whatever the caller queued there before the call -- a producer or an earlier
+ * user of the buffers -- is finished before the first byte lands.  The call returns after all
+ * its batches are done: the caller needs no synchronise afterwards.  The caller's current device
+ * is restored.
+ *
+ * One device: the whole image goes through the device state that owns `stream`'s device (no
+ * striping: the destinations live on one device).  The pipeline is cir_check_blocks' with one
+ * scatter record per packed run added to each batch: the packed slot stays the unit of upload,
+ * and behind the compare cir_scatter_runs_dev's kernel moves the batch's runs from the slot's
+ * device twin to the destinations, inside device memory, while the next batch uploads.
+ * CIR_TRACE=1 prints cir_check_blocks' laps and the scatter records per batch.
+ *
+ * CIR_EINVAL / CIR_EPARSE / CIR_EHASHSIZE / CIR_EIO as cir_check_blocks, and CIR_EINVAL for a
+ * wrong ndata, a null d_data, a device that is not ctx's; CIR_EIO when the scatter counted a bad
+ * record (the table is the call's own: a defect).
+ *
+ * stats: [0..9] as cir_check_blocks (SKIPPED files are in none of [2..5], their blocks count as
+ * not have and not in [9]), [10] bytes scattered, [11] files SKIPPED. */
+#define CIR_LOAD_STATS_FIELDS 12
+int cir_load_blocks(cir_ctx* ctx, int dirfd, const char* dir, const uint8_t* index, size_t len,
+                    uint32_t threads, void* const* d_data, size_t ndata, void* stream,
+                    uint64_t** have_out, uint64_t* nblk_out, uint8_t** state_out,
+                    int32_t** errno_out, size_t* nfiles_out,
+                    uint64_t stats[CIR_LOAD_STATS_FIELDS]);
 
 /* Slots the table of cir_match_digests_dev needs for n_pool digests: the smallest power of two
  * >= max(64, 2 * n_pool), so the table is never more than half full (0 when no u64 holds it:
