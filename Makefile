@@ -5,6 +5,7 @@
 #   make sketch_fuzz -> build/sketch_fuzz (the sketch rule under ASan + UBSan; not in `all`)
 #   make emit_fuzz  -> build/emit_fuzz (the emit rule under ASan + UBSan; not in `all`)
 #   make scatter_fuzz -> build/scatter_fuzz (the scatter rule under ASan + UBSan; not in `all`)
+#   make gather_fuzz -> build/gather_fuzz (the gather rule under ASan + UBSan; not in `all`)
 #   make asan/tsan  -> build/host_{asan,tsan}_driver (host code under the
 #                      sanitizers; `make sanitizers` = both; not in `all`)
 HIPCC ?= /opt/rocm/bin/hipcc
@@ -24,10 +25,10 @@ CLI := bin/ciruela-index
 SRCS_HIP := $(CSRC)/kernels.hip $(CSRC)/order.hip $(CSRC)/join.hip \
             $(CSRC)/idxscan.hip $(CSRC)/extents.hip $(CSRC)/repeats.hip \
             $(CSRC)/files.hip $(CSRC)/plan.hip $(CSRC)/sketch.hip $(CSRC)/emit.hip \
-            $(CSRC)/scatter.hip
+            $(CSRC)/scatter.hip $(CSRC)/gather.hip
 SRCS_CPP := $(CSRC)/runtime.cpp $(CSRC)/dirsig.cpp $(CSRC)/scan.cpp $(CSRC)/check.cpp \
             $(CSRC)/links.cpp $(CSRC)/sources.cpp $(CSRC)/repeats.cpp $(CSRC)/idxscan.cpp \
-            $(CSRC)/files.cpp $(CSRC)/copies.cpp $(CSRC)/plan.cpp $(CSRC)/sketch.cpp $(CSRC)/memindex.cpp $(CSRC)/devcall.cpp $(CSRC)/registry.cpp $(CSRC)/blake2b_host.cpp \
+            $(CSRC)/files.cpp $(CSRC)/copies.cpp $(CSRC)/plan.cpp $(CSRC)/sketch.cpp $(CSRC)/memindex.cpp $(CSRC)/store.cpp $(CSRC)/devcall.cpp $(CSRC)/registry.cpp $(CSRC)/blake2b_host.cpp \
             $(CSRC)/sha512_host.cpp
 OBJS := $(patsubst $(CSRC)/%.hip,$(OBJDIR)/%.hip.o,$(SRCS_HIP)) \
         $(patsubst $(CSRC)/%.cpp,$(OBJDIR)/%.o,$(SRCS_CPP))
@@ -122,6 +123,14 @@ build/scatter_fuzz: tools/scatter_fuzz.cpp $(CSRC)/scatter.hpp $(CSRC)/pack.hpp
 	    -I$(CSRC) tools/scatter_fuzz.cpp -o $@
 scatter_fuzz: build/scatter_fuzz
 
+# the gather rule (gather.hpp; the kernel is gather.hip) over pack.hpp's runs under
+# ASan + UBSan: a stand-alone host program (tools/gather_fuzz.cpp), no device code
+build/gather_fuzz: tools/gather_fuzz.cpp $(CSRC)/gather.hpp $(CSRC)/scatter.hpp $(CSRC)/pack.hpp
+	@mkdir -p build
+	$(CXX) -std=c++17 -O1 -g -fsanitize=address,undefined -fno-sanitize-recover=all \
+	    -I$(CSRC) tools/gather_fuzz.cpp -o $@
+gather_fuzz: build/gather_fuzz
+
 oracle:
 	$(MAKE) -C oracle
 
@@ -129,4 +138,4 @@ clean:
 	rm -rf build $(LIB) $(CLI)
 	$(MAKE) -C oracle clean
 
-.PHONY: all oracle clean asan tsan sanitizers sketch_fuzz emit_fuzz scatter_fuzz
+.PHONY: all oracle clean asan tsan sanitizers sketch_fuzz emit_fuzz scatter_fuzz gather_fuzz

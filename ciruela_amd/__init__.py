@@ -124,6 +124,7 @@ __all__ = [
     "index_digests", "IndexDigests", "file_sources", "file_copies", "check_links_at",
     "fetch_plan", "PlanResult", "index_sketch", "sketch_rank", "sketch_key",
     "index_memory", "index_emit", "index_emit_layout", "index_emit_tables", "load_image",
+    "store_image",
 ]
 
 DEFAULT_BLOCK_SIZE = 32768
@@ -751,6 +752,42 @@ class Context:
         errnos = list((ctypes.c_int32 * nf).from_buffer_copy(raw)) if nf else []
         return BlocksResult(index, nblk.value, bits, list(states), errnos,
                             dict(zip(self.LOAD_STATS_FIELDS, list(stats))))
+
+    STORE_STATS_FIELDS = ("blocks", "files", "dirs_made", "bytes", "batches", "body_bytes")
+
+    def store_blocks(self, root, files, block_size, hash_type, threads=0, dir_fd=None, stream=0,
+                     image_id=None, stats=None):
+        """load_blocks mirrored (cir_store_blocks): files held in device
+        memory written out below the existing directory `root` (relative to
+        dir_fd when given; root=None: dir_fd itself), and the tree's index.
+        files = [(path, obj[, exe])] as index_memory takes them, on the device
+        of `stream`, behind whose earlier work the first byte is read.
+        Directories are made as needed; a file that exists, a symlink at any
+        component or a write error raises CiruelaError (CIR_EIO) and leaves
+        what was written.  Returns the index bytes: index_memory's of the same
+        list and v1.scan's of the written tree.  image_id: a list that receives
+        the ImageId; stats: a dict that receives STORE_STATS_FIELDS."""
+        if root is None and dir_fd is None:
+            raise ValueError("store_blocks needs a root path or a directory fd")
+        fd = -100 if dir_fd is None else dir_fd  # AT_FDCWD
+        paths, offs, exe, objs = _emit_files(files)
+        spans = [_device_span(o) for o in objs]
+        n = len(spans)
+        ptrs = (ctypes.c_void_p * max(n, 1))(*[p or None for p, _ in spans])
+        out, out_len = ctypes.c_void_p(), ctypes.c_size_t()
+        iid = ctypes.create_string_buffer(32)
+        st = (ctypes.c_uint64 * _n.CIR_STORE_STATS_FIELDS)()
+        _n.check(_n.lib.cir_store_blocks(self._h, fd, None if root is None else os.fsencode(root),
+                                         hash_type.code, block_size, paths, offs,
+                                         _sizes([b for _, b in spans]), exe, n, ptrs, stream,
+                                         threads, ctypes.byref(out), ctypes.byref(out_len), iid,
+                                         st))
+        del objs
+        if image_id is not None:
+            image_id.append(ImageId(iid.raw))
+        if stats is not None:
+            stats.update(zip(self.STORE_STATS_FIELDS, list(st)))
+        return _n.take_buffer(out.value, out_len.value)
 
     def scan(self, config):
         dirs = [os.fsencode(d) for d, _ in config._dirs]
@@ -1599,6 +1636,27 @@ def load_image(root, index, context=None, only=None, threads=0):
         stream = torch.cuda.current_stream(dev).cuda_stream
         res = ctx.load_blocks(root, index, buffers, threads=threads, stream=stream)
     return tensors, res
+
+
+def store_image(root, files, block_size=DEFAULT_BLOCK_SIZE, hash_type=None, context=None,
+                threads=0):
+    """load_image mirrored (cir_store_blocks): files = [(path, obj[, exe])] as
+    index_memory takes them -- obj a torch tensor or anything with data_ptr()
+    and a byte count, or a (ptr, nbytes) pair -- written out below the existing
+    directory `root`, on the current torch stream.  Returns the index bytes of
+    the written tree: check_index(root, store_image(root, files)) passes, and
+    load_image(root, ...) of it gives the files back."""
+    import torch
+    ctx = context or default_context()
+    dev = torch.device("cuda", ctx.devices()[0])
+    for f in files:
+        if getattr(f[1], "is_cuda", False):
+            dev = f[1].device
+            break
+    with torch.cuda.device(dev):
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        return ctx.store_blocks(root, files, block_size, hash_type or HashType.blake2b_256(),
+                                threads=threads, stream=stream)
 
 
 def default_context():

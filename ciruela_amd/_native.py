@@ -55,6 +55,9 @@ CIR_BLOCKS_STATS_FIELDS = 10
 CIR_LOAD_STATS_FIELDS = 12
 CIR_SCATTER_RUN_WORDS = 4
 CIR_SCATTER_RES_FIELDS = 1
+CIR_GATHER_RUN_WORDS = 4
+CIR_GATHER_RES_FIELDS = 1
+CIR_STORE_STATS_FIELDS = 6
 CIR_SOURCES_STATS_FIELDS = 8
 CIR_EXTENTS_STATS_FIELDS = 10
 CIR_EXTENTS_RES_FIELDS = 6
@@ -211,6 +214,15 @@ _SIGS = {
                                         ctypes.c_uint64, c_u64p]),
     "cir_scatter_runs_dev": (ctypes.c_int, [c_vp, c_vp, ctypes.c_uint64, c_vp, ctypes.c_uint64,
                                             ctypes.c_uint64, c_vp, c_vp]),
+    "cir_gather_runs": (ctypes.c_int, [c_vp, ctypes.c_uint64, c_vp, ctypes.c_uint64,
+                                       ctypes.c_uint64, c_u64p]),
+    "cir_gather_runs_dev": (ctypes.c_int, [c_vp, c_vp, ctypes.c_uint64, c_vp, ctypes.c_uint64,
+                                           ctypes.c_uint64, c_vp, c_vp]),
+    "cir_store_blocks": (ctypes.c_int, [c_vp, ctypes.c_int, ctypes.c_char_p, ctypes.c_int,
+                                        ctypes.c_uint64, c_vp, c_u64p, c_u64p, c_vp,
+                                        ctypes.c_size_t, ctypes.POINTER(c_vp), c_vp,
+                                        ctypes.c_uint32, ctypes.POINTER(c_vp), c_sizep, c_vp,
+                                        c_u64p]),
     "cir_load_blocks": (ctypes.c_int, [c_vp, ctypes.c_int, ctypes.c_char_p, c_vp, ctypes.c_size_t,
                                        ctypes.c_uint32, ctypes.POINTER(c_vp), ctypes.c_size_t,
                                        c_vp, ctypes.POINTER(c_vp), c_u64p, ctypes.POINTER(c_vp),

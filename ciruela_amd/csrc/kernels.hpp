@@ -434,6 +434,19 @@ constexpr int kScatterResFields = 1;
 hipError_t launch_scatter_runs(const uint8_t* src, uint64_t src_bytes, const uint64_t* runs,
                                uint64_t nruns, uint64_t nunits, uint64_t* res, hipStream_t s);
 
+// Bytes anywhere in device memory copied into the packed runs of a staging
+// slot (gather.hip; cir_gather_runs_dev, cir_store_blocks; the rule is
+// gather.hpp): for every sound record {unit_first, dst_pos, src, bytes} of
+// `runs` (gather::kRunWords u64 each) the bytes at src stand at dst[dst_pos,
+// dst_pos + bytes) afterwards, zeros behind them up to the next multiple of 16,
+// and no other byte is written; res: kGatherResFields u64 {bad records: written
+// nowhere, read nowhere}, zeroed here, all on `s`.  dst 16-byte aligned and not
+// overlapping any source.  No launch when there is neither a unit nor a record.
+// Unchecked: nruns <= gather::kMaxRuns, nunits <= gather::kMaxUnits.
+constexpr int kGatherResFields = 1;
+hipError_t launch_gather_runs(uint8_t* dst, uint64_t dst_bytes, const uint64_t* runs,
+                              uint64_t nruns, uint64_t nunits, uint64_t* res, hipStream_t s);
+
 // nlanes x `lines` register-only compressions (diagnostic VALU ceiling).
 hipError_t launch_compress_only(uint64_t nlanes, uint32_t lines, uint8_t* out, hipStream_t s);
 

@@ -19,6 +19,7 @@
 #include "devcall.hpp"
 #include "dirsig.hpp"
 #include "emit.hpp"
+#include "memindex.hpp"
 #include "runtime.hpp"
 #include "sha512_host.hpp"
 
@@ -35,24 +36,9 @@ bool emit_on_host() {
   return v && strcmp(v, "host") == 0;
 }
 
-bool header_of(int hash_type, uint64_t bs, dirsig::Header* h) {
-  if (bs == 0 || bs > 0xffffffffull) return false;
-  h->block_size = bs;
-  h->hash = hash_type == CIR_HASH_SHA512_256 ? dirsig::HashType::kSha512_256
-                                             : dirsig::HashType::kBlake2b256;
-  return true;
-}
-
 std::string header_line(const dirsig::Header& h) {
   return std::string("DIRSIGNATURE.v1 ") + dirsig::hash_type_name(h.hash) +
          " block_size=" + std::to_string(h.block_size) + "\n";
-}
-
-int check_files(const uint8_t* paths, const uint64_t* path_off, const uint64_t* sizes,
-                size_t nfiles) {
-  if (nfiles && (!path_off || !sizes || (!paths && path_off[nfiles] != path_off[0])))
-    return fail(CIR_EINVAL, "null pointer");
-  return CIR_OK;
 }
 
 // The index buffer of a body of body_len bytes: header, room for the body in
@@ -182,14 +168,7 @@ int index_emit_impl(int hash_type, uint64_t bs, const uint8_t* paths, const uint
                                 std::to_string(ndigests) + " given, " +
                                 std::to_string(lay.nblocks) + " needed");
   if (lay.body_len > dev::kEmitMaxBody) return fail(CIR_EINVAL, "body longer than 2^40 bytes");
-  const std::string header = header_line(h);
-  size_t cap = 0;
-  uint8_t* buf = index_buffer(header, lay.body_len, &cap);
-  if (!buf) return fail(CIR_ENOMEM, "malloc");
-  emit::emit_host(lay.tables(digests), buf + header.size());
-  *len_out = finish_index(buf, header.size(), lay.body_len, h, image_id);
-  *index_out = buf;
-  return CIR_OK;
+  return emit_index_host(lay, h, digests, index_out, len_out, image_id);
 }
 
 struct HostBuf {
@@ -341,6 +320,36 @@ int index_memory_impl(cir_ctx* ctx, int hash_type, uint64_t bs, const uint8_t* p
 }
 
 }  // namespace
+
+// ---- shared with cir_store_blocks (memindex.hpp) -----------------------------
+
+int check_files(const uint8_t* paths, const uint64_t* path_off, const uint64_t* sizes,
+                size_t nfiles) {
+  if (nfiles && (!path_off || !sizes || (!paths && path_off[nfiles] != path_off[0])))
+    return fail(CIR_EINVAL, "null pointer");
+  return CIR_OK;
+}
+
+bool header_of(int hash_type, uint64_t bs, dirsig::Header* h) {
+  if (bs == 0 || bs > 0xffffffffull) return false;
+  h->block_size = bs;
+  h->hash = hash_type == CIR_HASH_SHA512_256 ? dirsig::HashType::kSha512_256
+                                             : dirsig::HashType::kBlake2b256;
+  return true;
+}
+
+int emit_index_host(const emit::Layout& lay, const dirsig::Header& h, const uint8_t* digests,
+                    uint8_t** index_out, size_t* len_out, uint8_t* image_id) {
+  const std::string header = header_line(h);
+  size_t cap = 0;
+  uint8_t* buf = index_buffer(header, lay.body_len, &cap);
+  if (!buf) return fail(CIR_ENOMEM, "malloc");
+  emit::emit_host(lay.tables(digests), buf + header.size());
+  *len_out = finish_index(buf, header.size(), lay.body_len, h, image_id);
+  *index_out = buf;
+  return CIR_OK;
+}
+
 }  // namespace cir
 
 extern "C" int cir_index_emit_layout(uint64_t block_size, const uint8_t* paths,

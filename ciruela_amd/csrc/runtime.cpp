@@ -5,6 +5,8 @@
 #include "runtime.hpp"
 
 #include "pool.hpp"
+#include "gather.hpp"
+#include "pack.hpp"
 #include "scatter.hpp"
 
 #include <emmintrin.h>
@@ -383,9 +385,9 @@ int Device::ensure_blocks(Slot& s) {
   return CIR_OK;
 }
 
-int Device::ensure_load(Slot& s) {
-  int rc = ensure_blocks(s);
-  if (rc) return rc;
+// The run table of the load and the store mode (one record per packed run, at
+// most one per block), sized to s.cap_blk.
+static int ensure_run_table(Slot& s) {
   if (s.scat_cap < s.cap_blk) {
     (void)hipHostFree(s.h_scat);
     (void)hipFree(s.d_scat);
@@ -398,6 +400,13 @@ int Device::ensure_load(Slot& s) {
   }
   return CIR_OK;
 }
+
+int Device::ensure_load(Slot& s) {
+  const int rc = ensure_blocks(s);
+  return rc ? rc : ensure_run_table(s);
+}
+
+int Device::ensure_store(Slot& s) { return ensure_run_table(s); }
 
 int Device::ensure_timing(Slot& s) {
   for (hipEvent_t* e : {&s.t_copy0, &s.t_copy1, &s.t_hash0, &s.t_done})
@@ -618,6 +627,31 @@ int slot_submit_load(Device& d, Slot& s, uint64_t bytes, uint64_t nblk, int ht, 
       !s.d_scat || !s.h_scat || s.scat_cap < nscat || nscat == 0)
     return fail(CIR_EINVAL, "load-mode submit without ensure_load");
   return slot_submit_impl(d, s, bytes, nblk, 0, ht, nullptr, 0, true, nscat, nunits);
+}
+
+int slot_submit_store(Device& d, Slot& s, uint64_t bytes, uint64_t nblk, int ht, uint64_t ngath,
+                      uint64_t nunits) {
+  if (!s.d_scat || !s.h_scat || s.scat_cap < ngath || ngath == 0 || nblk == 0 || bytes == 0 ||
+      align16(bytes) > s.cap)
+    return fail(CIR_EINVAL, "store-mode submit without ensure_store");
+  s.timed = false;
+  CIR_HIP(hipMemcpyAsync(s.d_off, s.h_off, nblk * 8, hipMemcpyHostToDevice, d.copy));
+  CIR_HIP(hipMemcpyAsync(s.d_len, s.h_len, nblk * 4, hipMemcpyHostToDevice, d.copy));
+  CIR_HIP(hipMemcpyAsync(s.d_scat + kScatHead, s.h_scat + kScatHead,
+                         8 * gather::kRunWords * ngath, hipMemcpyHostToDevice, d.copy));
+  CIR_HIP(hipEventRecord(s.copied, d.copy));
+  CIR_HIP(hipStreamWaitEvent(d.compute, s.copied, 0));
+  CIR_HIP(dev::launch_gather_runs(s.d_data, align16(bytes), s.d_scat + kScatHead, ngath, nunits,
+                                  s.d_scat, d.compute));
+  const int rc = hash_desc_ordered(d, s.d_data, s.d_off, s.d_len, nblk, s.d_out, d.compute, ht);
+  if (rc) return rc;
+  CIR_HIP(hipMemcpyAsync(s.h_data, s.d_data, bytes, hipMemcpyDeviceToHost, d.compute));
+  CIR_HIP(hipMemcpyAsync(s.h_out, s.d_out, nblk * 32, hipMemcpyDeviceToHost, d.compute));
+  CIR_HIP(hipMemcpyAsync(s.h_scat, s.d_scat, 8 * dev::kGatherResFields, hipMemcpyDeviceToHost,
+                         d.compute));
+  CIR_HIP(hipEventRecord(s.done, d.compute));
+  s.busy = true;
+  return CIR_OK;
 }
 
 int slot_wait(Device& d, Slot& s) {

@@ -102,7 +102,8 @@ struct Slot {
   // record of 4 u64 per packed run) behind a head of kScatHead u64 whose first
   // word is the scatter's result {bad records}; pinned host twin, the table
   // going up and the result coming down; room for scat_cap records, allocated
-  // on the first load
+  // on the first load.  Store mode (cir_store_blocks) keeps its gather table
+  // (gather.hpp: the same shape) and the gather's result in the same pair
   uint64_t* h_scat = nullptr;
   uint64_t* d_scat = nullptr;
   uint64_t scat_cap = 0;
@@ -235,6 +236,7 @@ struct Device {
   int ensure_links(Slot& s);  // those and the links-mode buffers, sized to s.cap_blk
   int ensure_blocks(Slot& s);  // the check-mode and the blocks-mode buffers, sized to s.cap_blk
   int ensure_load(Slot& s);    // those and the load-mode table, sized to s.cap_blk
+  int ensure_store(Slot& s);   // the store mode's table (the load mode's buffers), sized to s.cap_blk
 };
 
 // Every slot a staged loop submitted is waited for before the loop lets go
@@ -289,6 +291,16 @@ int slot_submit_blocks(Device& d, Slot& s, uint64_t bytes, uint64_t nblk, int ht
 constexpr uint64_t kScatHead = 2;
 int slot_submit_load(Device& d, Slot& s, uint64_t bytes, uint64_t nblk, int ht, uint64_t nscat,
                      uint64_t nunits);
+// Store mode (cir_store_blocks): nothing goes up but the descriptors and the
+// ngath gather records at s.h_scat + kScatHead (gather.hpp; nunits units in
+// all).  On the compute stream launch_gather_runs fills the slot's device twin
+// from the records' sources, the batch is hashed there, and the slot's `bytes`
+// bytes, the digests and the gather's result come down: after slot_wait,
+// s.h_data holds the packed runs, s.h_out the digests of exactly those bytes
+// and s.h_scat[0] the records the gather found bad (0 for a table the packer
+// built).
+int slot_submit_store(Device& d, Slot& s, uint64_t bytes, uint64_t nblk, int ht, uint64_t ngath,
+                      uint64_t nunits);
 int hash_desc_ordered(Device& d, const uint8_t* arena, const uint64_t* off, const uint32_t* len,
                       uint64_t n, uint8_t* out, hipStream_t s, int ht = CIR_HASH_BLAKE2B_256,
                       bool warm_only = false);

@@ -654,6 +654,87 @@ int cir_load_blocks(cir_ctx* ctx, int dirfd, const char* dir, const uint8_t* ind
                     int32_t** errno_out, size_t* nfiles_out,
                     uint64_t stats[CIR_LOAD_STATS_FIELDS]);
 
+/* The gather of cir_store_blocks on its own: bytes that lie anywhere copied into the packed runs
+ * of one destination buffer.  cir_scatter_runs turned round; the reference has no counterpart.
+ * The rule is ciruela_amd/csrc/gather.hpp.
+ *
+ * Table: nruns records of CIR_GATHER_RUN_WORDS u64 {unit_first, dst_pos, src, bytes}: `bytes`
+ * (> 0) bytes at the address src (any alignment) go to byte dst_pos of the destination (a
+ * multiple of 16).  A record has ceil(bytes / 16) units of 16 bytes; unit_first is the unit count
+ * of all earlier records and nunits that of the whole table.  A unit owns its 16 aligned
+ * destination bytes and writes all of them: for every sound record the bytes at src stand at
+ * dst[dst_pos, dst_pos + bytes) afterwards, zeros behind them up to the next multiple of 16, and
+ * no other byte is written.  Nothing is read outside [src, src + bytes).  The sources must not
+ * overlap the destination.
+ *
+ * res[0] = the bad records: dst_pos not a multiple of 16, bytes 0, a range [dst_pos, dst_pos +
+ * 16 * ceil(bytes / 16)) that does not lie inside [0, dst_bytes], or a unit_first that is not the
+ * previous record's plus its units (0 for the first record; the last record must end at nunits).
+ * A bad record is written nowhere and read nowhere; the count is exact whatever the table holds.
+ *
+ * cir_gather_runs is the host form (src: host addresses; pure, host-only).  CIR_EINVAL: a null
+ * pointer with a non-zero count, a null res, nruns or nunits above 2^32 - 1. */
+#define CIR_GATHER_RUN_WORDS 4
+#define CIR_GATHER_RES_FIELDS 1
+int cir_gather_runs(uint8_t* dst, uint64_t dst_bytes, const uint64_t* runs, uint64_t nruns,
+                    uint64_t nunits, uint64_t res[CIR_GATHER_RES_FIELDS]);
+
+/* The same on the device: destination, table and sources in device memory (d_dst 16-byte
+ * aligned, d_runs and d_res 8-byte aligned).  One lane per unit: always one 16-byte store; a whole
+ * unit is loaded with one 16-byte load where its source is 16-byte aligned and with the widest
+ * loads the source's alignment allows otherwise, a short last unit byte by byte.  Every word of
+ * d_res[CIR_GATHER_RES_FIELDS] is written (a memset and one launch; no launch for an empty
+ * table).  Like every *_dev call it allocates nothing, synchronises nothing and runs on `stream`
+ * alone; ctx may be NULL and is not used.  CIR_EINVAL, decided before any HIP call: as
+ * cir_gather_runs, or a misaligned pointer. */
+int cir_gather_runs_dev(cir_ctx* ctx, uint8_t* d_dst, uint64_t dst_bytes, const uint64_t* d_runs,
+                        uint64_t nruns, uint64_t nunits, uint64_t* d_res, void* stream);
+
+/* cir_load_blocks mirrored: files held in device memory written out as an image directory, and
+ * the directory's index.  The reference has no counterpart (an image directory is filled block by
+ * block from the network, src/daemon/disk/public.rs write_block; its index comes from a scan).
+ *
+ * The file list -- paths, path_off, sizes, exe, nfiles, d_data --, the path rules and every
+ * CIR_EINVAL case are cir_index_memory_dev's (a null ctx, a device that is not ctx's, a null
+ * pointer of a non-empty file, an invalid path or a path conflict, a bad block size or hash
+ * type); all of them are decided before anything is created on disk and before any device work.
+ * The root is dirfd + dir as in cir_check_blocks and must exist.
+ *
+ * The tree: the directories the paths imply are made with mkdirat below their parent's fd (an
+ * existing directory is accepted) and opened with O_DIRECTORY | O_NOFOLLOW; every file is created
+ * with openat(O_WRONLY | O_CREAT | O_EXCL | O_NOFOLLOW) and fchmod'ed to exactly 0644, or 0755
+ * where exe is set; a size-0 file is created empty.  Nothing is fsync'ed, and renaming a
+ * temporary root into place stays the caller's.  CIR_EIO with the path and errno in
+ * cir_last_error: a root that cannot be opened, a file that exists, a symlink at any component, a
+ * write error.  The first such failure ends the call; what was written is left for the caller to
+ * remove.  Nothing is ever written through a symlink or outside the root.
+ *
+ * Pipeline: cir_load_blocks' the other way, on the device of `stream`.  The files' runs are laid
+ * out in a staging slot in the caller's file order, one gather record per run; cir_gather_runs_dev's
+ * kernel fills the slot's device twin from d_data, the slot is hashed there, and its bytes and
+ * digests come down as one copy each per batch; `threads` writers (0: chosen by the library)
+ * pwrite the runs from the pinned slot while the next slots gather and download.  Before the
+ * first batch the device's compute stream waits for an event recorded on `stream`, so whatever the
+ * caller queued there to produce the data is finished before the first byte is read.  The call
+ * returns after its last write; the caller's current device is restored.  CIR_TRACE=1 prints one
+ * `cir store_blocks:` line with the laps.
+ *
+ * The index: made by cir_index_emit's emitter from the digests of the slots' bytes, the bytes
+ * that were written.  *index_out (cir_free) and image_id are byte-identical to
+ * cir_index_memory_dev's of the same list and so to cir_scan_v1's of the written tree:
+ * cir_check_index(root, *index_out) passes by construction.
+ *
+ * CIR_EIO also when the gather counted a bad record (the table is the call's own: a defect).
+ *
+ * stats (all written as 0 first): [0] blocks, [1] files written, [2] directories made, [3] bytes
+ * written, [4] batches, [5] body bytes. */
+#define CIR_STORE_STATS_FIELDS 6
+int cir_store_blocks(cir_ctx* ctx, int dirfd, const char* dir, int hash_type, uint64_t block_size,
+                     const uint8_t* paths, const uint64_t* path_off, const uint64_t* sizes,
+                     const uint8_t* exe, size_t nfiles, const void* const* d_data, void* stream,
+                     uint32_t threads, uint8_t** index_out, size_t* len_out,
+                     uint8_t image_id[CIR_DIGEST_BYTES], uint64_t stats[CIR_STORE_STATS_FIELDS]);
+
 /* Slots the table of cir_match_digests_dev needs for n_pool digests: the smallest power of two
  * >= max(64, 2 * n_pool), so the table is never more than half full (0 when no u64 holds it:
  * n_pool > 2^62).  Pure: no HIP call. */
