@@ -724,8 +724,9 @@ def test_sha512_256_single_and_batches(gpu, ctx, oracle):
         offs.append(pos)
         pos += ln
     got = ctx.hash_blocks(arena, offs, lens, hash_type=sha)
-    for i in range(0, len(lens), 7):
-        assert got[32 * i:32 * i + 32] == oracle_sha(oracle, arena[offs[i]:offs[i] + lens[i]]), i
+    want = b"".join(oracle_sha(oracle, arena[o:o + ln]) for o, ln in zip(offs, lens))
+    for i in range(len(lens)):
+        assert got[32 * i:32 * i + 32] == want[32 * i:32 * i + 32], (i, lens[i])
     # device-resident descriptors
     t = torch.tensor(bytearray(arena), dtype=torch.uint8, device="cuda:0")
     d_off = torch.tensor(offs, dtype=torch.int64, device="cuda:0")
@@ -734,7 +735,10 @@ def test_sha512_256_single_and_batches(gpu, ctx, oracle):
     ctx.hash_blocks_dev(t.data_ptr(), d_off.data_ptr(), d_len.data_ptr(), len(lens),
                         out.data_ptr(), 0, hash_type=sha)
     torch.cuda.synchronize()
-    assert out.cpu().numpy().tobytes() == got
+    dev = out.cpu().numpy().tobytes()
+    for i in range(len(lens)):
+        assert dev[32 * i:32 * i + 32] == want[32 * i:32 * i + 32], (i, lens[i])
+    assert dev == got
     data = os.urandom(5 * 32768 + 17)
     assert ctx.hash_memory(data, 32768, hash_type=sha) == b"".join(
         oracle_sha(oracle, data[i:i + 32768]) for i in range(0, len(data), 32768))
