@@ -101,6 +101,9 @@ load_image,                     the way back: an image directory read into devic
   Context.load_blocks           buffers and verified there, check_blocks that keeps
                                 what it read (the reference's consumers read committed
                                 files unchecked: src/daemon/disk/commit.rs:51-117)
+reload_image,                   load_image for a process that holds the previous
+  Context.reload_blocks         version in device memory: the blocks its buffers
+                                already hold are copied on the device, the rest read
 =============================  ==============================================
 
 All hashing runs on gfx950 through the library; there is no CPU fallback.
@@ -124,6 +127,7 @@ __all__ = [
     "index_digests", "IndexDigests", "file_sources", "file_copies", "check_links_at",
     "fetch_plan", "PlanResult", "index_sketch", "sketch_rank", "sketch_key",
     "index_memory", "index_emit", "index_emit_layout", "index_emit_tables", "load_image",
+    "reload_image",
     "store_image",
 ]
 
@@ -709,49 +713,22 @@ class Context:
         shorter than its entry is a ValueError.  The buffers live on the device
         of `stream`, behind whose earlier work the first byte lands; the call
         returns when the buffers are filled."""
-        if len(index):
-            ptr, keep = _buf(index)
-        else:  # (an empty index is a parse error, not a null argument)
-            keep = ctypes.create_string_buffer(1)
-            ptr = ctypes.cast(keep, ctypes.c_void_p)
-        if root is None and dir_fd is None:
-            raise ValueError("load_blocks needs a root path or a directory fd")
-        fd = -100 if dir_fd is None else dir_fd  # AT_FDCWD
-        buffers = list(buffers)
-        ptrs = []
-        sizes = None
-        for i, b in enumerate(buffers):
-            if b is None:
-                ptrs.append(None)
-            elif isinstance(b, int):
-                ptrs.append(b or None)
-            else:
-                p, nbytes = _device_span(b)
-                if sizes is None:
-                    sizes = [size for _, size, _ in _file_blocks(index)[0]]
-                if i < len(sizes) and nbytes < sizes[i]:
-                    raise ValueError("buffer %d holds %d bytes, its entry %d" % (i, nbytes, sizes[i]))
-                ptrs.append(p or None)
-        n = len(ptrs)
-        d_data = (ctypes.c_void_p * max(n, 1))(*ptrs)
-        have = ctypes.c_void_p()
-        nblk = ctypes.c_uint64()
-        state = ctypes.c_void_p()
-        errs = ctypes.c_void_p()
-        nfiles = ctypes.c_size_t()
-        stats = (ctypes.c_uint64 * _n.CIR_LOAD_STATS_FIELDS)()
-        _n.check(_n.lib.cir_load_blocks(self._h, fd, None if root is None else os.fsencode(root),
-                                        ptr, len(index), threads, d_data, n, stream,
-                                        ctypes.byref(have), ctypes.byref(nblk), ctypes.byref(state),
-                                        ctypes.byref(errs), ctypes.byref(nfiles), stats))
-        del keep, buffers
-        nf = nfiles.value
-        bits = _n.take_buffer(have.value, 8 * ((nblk.value + 63) // 64))
-        states = _n.take_buffer(state.value, nf)
-        raw = _n.take_buffer(errs.value, 4 * nf)
-        errnos = list((ctypes.c_int32 * nf).from_buffer_copy(raw)) if nf else []
-        return BlocksResult(index, nblk.value, bits, list(states), errnos,
-                            dict(zip(self.LOAD_STATS_FIELDS, list(stats))))
+        return _load_blocks(self, root, index, buffers, None, threads, dir_fd, stream)
+
+    RELOAD_STATS_FIELDS = LOAD_STATS_FIELDS + ("copied_blocks", "copied_bytes", "resident_blocks",
+                                               "resident_files", "dropped_length")
+
+    def reload_blocks(self, root, index, buffers, resident, threads=0, dir_fd=None, stream=0):
+        """load_blocks for a process that holds the previous version in device
+        memory (cir_reload_blocks).  resident: the previous version's buffers,
+        in any order -- (ptr, nbytes) pairs or anything with data_ptr() and a
+        byte count, None and empty ones ignored --, on the same device, none of
+        them overlapping a destination.  They are hashed where they lie; a
+        block of `index` whose digest and length one of their blocks has is
+        copied inside device memory, the rest is read from `root` as
+        load_blocks reads it.  A file all of whose blocks came from memory is
+        not opened: it is "complete" and its `resident` flag is set."""
+        return _load_blocks(self, root, index, buffers, list(resident), threads, dir_fd, stream)
 
     STORE_STATS_FIELDS = ("blocks", "files", "dirs_made", "bytes", "batches", "body_bytes")
 
@@ -980,13 +957,14 @@ class BlocksResult:
     byte g >> 3), has(g) one bit of it.  Per file entry, in index order:
     states ("complete", "absent", "partial" or "blocked"; from load_blocks
     also "skipped": a non-empty file that was given no buffer), long (the file
-    is longer than its entry and is to be truncated before commit), errnos (of
-    a "blocked", else 0).  complete: every file is complete.  missing(): the
+    is longer than its entry and is to be truncated before commit), resident
+    (reload_blocks took every block of the file from device memory and did not
+    open it), errnos (of a "blocked", else 0).  complete: every file is complete.  missing(): the
     (path as raw bytes, byte offset) of every block that is not there, in
     index order -- what fill_blocks would queue
     (src/daemon/tracking/progress.rs:136-151)."""
 
-    __slots__ = ("nblk", "have", "states", "long", "errnos", "stats", "_index")
+    __slots__ = ("nblk", "have", "states", "long", "resident", "errnos", "stats", "_index")
     STATES = {_n.CIR_FILE_COMPLETE: "complete", _n.CIR_FILE_ABSENT: "absent",
               _n.CIR_FILE_PARTIAL: "partial", _n.CIR_FILE_BLOCKED: "blocked"}
     SKIPPED = "skipped"
@@ -998,6 +976,7 @@ class BlocksResult:
         self.states = [self.SKIPPED if s & 0x7f == _n.CIR_FILE_SKIPPED else self.STATES[s & 3]
                        for s in states]
         self.long = [bool(s & _n.CIR_FILE_LONG) for s in states]
+        self.resident = [bool(s & _n.CIR_FILE_RESIDENT) for s in states]
         self.errnos = list(errnos)
         self.stats = stats
 
@@ -1558,6 +1537,65 @@ def index_emit(files, digests, block_size=DEFAULT_BLOCK_SIZE, hash_type=None, im
     return _n.take_buffer(out.value, out_len.value)
 
 
+def _load_blocks(ctx, root, index, buffers, resident, threads, dir_fd, stream):
+    """Context.load_blocks (resident is None) and Context.reload_blocks: the
+    arguments are checked before the context is touched."""
+    if len(index):
+        ptr, keep = _buf(index)
+    else:  # (an empty index is a parse error, not a null argument)
+        keep = ctypes.create_string_buffer(1)
+        ptr = ctypes.cast(keep, ctypes.c_void_p)
+    if root is None and dir_fd is None:
+        raise ValueError("load_blocks needs a root path or a directory fd")
+    fd = -100 if dir_fd is None else dir_fd  # AT_FDCWD
+    buffers = list(buffers)
+    ptrs = []
+    sizes = None
+    for i, b in enumerate(buffers):
+        if b is None:
+            ptrs.append(None)
+        elif isinstance(b, int):
+            ptrs.append(b or None)
+        else:
+            p, nbytes = _device_span(b)
+            if sizes is None:
+                sizes = [size for _, size, _ in _file_blocks(index)[0]]
+            if i < len(sizes) and nbytes < sizes[i]:
+                raise ValueError("buffer %d holds %d bytes, its entry %d" % (i, nbytes, sizes[i]))
+            ptrs.append(p or None)
+    n = len(ptrs)
+    d_data = (ctypes.c_void_p * max(n, 1))(*ptrs)
+    have = ctypes.c_void_p()
+    nblk = ctypes.c_uint64()
+    state = ctypes.c_void_p()
+    errs = ctypes.c_void_p()
+    nfiles = ctypes.c_size_t()
+    outs = (ctypes.byref(have), ctypes.byref(nblk), ctypes.byref(state), ctypes.byref(errs),
+            ctypes.byref(nfiles))
+    path = None if root is None else os.fsencode(root)
+    if resident is None:
+        fields = Context.LOAD_STATS_FIELDS
+        stats = (ctypes.c_uint64 * _n.CIR_LOAD_STATS_FIELDS)()
+        _n.check(_n.lib.cir_load_blocks(ctx._h, fd, path, ptr, len(index), threads, d_data, n,
+                                        stream, *outs, stats))
+    else:
+        fields = Context.RELOAD_STATS_FIELDS
+        spans = [_device_span(r) for r in resident if r is not None]
+        d_have = (ctypes.c_void_p * max(len(spans), 1))(*[p or None for p, _ in spans])
+        stats = (ctypes.c_uint64 * _n.CIR_RELOAD_STATS_FIELDS)()
+        _n.check(_n.lib.cir_reload_blocks(ctx._h, fd, path, ptr, len(index), threads, d_data,
+                                          n, d_have, _sizes([b for _, b in spans]), len(spans),
+                                          stream, *outs, stats))
+    del keep, buffers, resident
+    nf = nfiles.value
+    bits = _n.take_buffer(have.value, 8 * ((nblk.value + 63) // 64))
+    states = _n.take_buffer(state.value, nf)
+    raw = _n.take_buffer(errs.value, 4 * nf)
+    errnos = list((ctypes.c_int32 * nf).from_buffer_copy(raw)) if nf else []
+    return BlocksResult(index, nblk.value, bits, list(states), errnos,
+                        dict(zip(fields, list(stats))))
+
+
 def _device_span(obj):
     """(device pointer, bytes) of a (ptr, nbytes) pair or of anything with
     data_ptr() and a byte count (a torch tensor: element_size() x numel(), or
@@ -1618,6 +1656,10 @@ def load_image(root, index, context=None, only=None, threads=0):
     first device, filled from the directory `root`.  Returns ({path as raw
     bytes: tensor}, BlocksResult): a "complete" file's tensor is the file, the
     result's bits say which blocks of the others are the index's."""
+    return _load_image(root, index, context, only, threads, None)
+
+
+def _load_image(root, index, context, only, threads, resident):
     import torch
     ctx = context or default_context()
     dev = torch.device("cuda", ctx.devices()[0])
@@ -1634,8 +1676,21 @@ def load_image(root, index, context=None, only=None, threads=0):
             buffers.append(None)
     with torch.cuda.device(dev):
         stream = torch.cuda.current_stream(dev).cuda_stream
-        res = ctx.load_blocks(root, index, buffers, threads=threads, stream=stream)
+        if resident is None:
+            res = ctx.load_blocks(root, index, buffers, threads=threads, stream=stream)
+        else:
+            res = ctx.reload_blocks(root, index, buffers, resident, threads=threads, stream=stream)
     return tensors, res
+
+
+def reload_image(root, index, resident, context=None, only=None, threads=0):
+    """load_image for a process that holds the previous version of the image in
+    device memory (cir_reload_blocks): resident is a dict or a list of tensors,
+    typically the dict the previous load_image returned.  New tensors are
+    allocated and the old ones left alone; what the old ones hold of the new
+    image is copied on the device, the rest is read from `root`."""
+    held = list(resident.values()) if isinstance(resident, dict) else list(resident)
+    return _load_image(root, index, context, only, threads, held)
 
 
 def store_image(root, files, block_size=DEFAULT_BLOCK_SIZE, hash_type=None, context=None,

@@ -57,6 +57,9 @@ CIR_SCATTER_RUN_WORDS = 4
 CIR_SCATTER_RES_FIELDS = 1
 CIR_GATHER_RUN_WORDS = 4
 CIR_GATHER_RES_FIELDS = 1
+CIR_COPY_RUN_WORDS = 4
+CIR_COPY_RES_FIELDS = 1
+CIR_RELOAD_STATS_FIELDS = 17
 CIR_STORE_STATS_FIELDS = 6
 CIR_SOURCES_STATS_FIELDS = 8
 CIR_EXTENTS_STATS_FIELDS = 10
@@ -104,6 +107,7 @@ CIR_FILE_PARTIAL = 2
 CIR_FILE_BLOCKED = 3
 CIR_FILE_SKIPPED = 4  # cir_load_blocks: a non-empty entry without a destination
 CIR_FILE_LONG = 0x80  # or'ed into a file's state: longer on disk than its entry
+CIR_FILE_RESIDENT = 0x40  # or'ed in by cir_reload_blocks: every block came from device memory
 CIR_INIT_ONE_SHOT = 1  # cir_init_n: one stream and one staging slot per device
 CIR_STAGING_LAZY = (1 << 64) - 1  # cir_init: no staging slots until a host path needs them
 
@@ -227,6 +231,13 @@ _SIGS = {
                                        ctypes.c_uint32, ctypes.POINTER(c_vp), ctypes.c_size_t,
                                        c_vp, ctypes.POINTER(c_vp), c_u64p, ctypes.POINTER(c_vp),
                                        ctypes.POINTER(c_vp), c_sizep, c_u64p]),
+    "cir_copy_runs": (ctypes.c_int, [c_vp, ctypes.c_uint64, ctypes.c_uint64, c_u64p]),
+    "cir_copy_runs_dev": (ctypes.c_int, [c_vp, c_vp, ctypes.c_uint64, ctypes.c_uint64, c_vp, c_vp]),
+    "cir_reload_blocks": (ctypes.c_int, [c_vp, ctypes.c_int, ctypes.c_char_p, c_vp, ctypes.c_size_t,
+                                         ctypes.c_uint32, ctypes.POINTER(c_vp), ctypes.c_size_t,
+                                         ctypes.POINTER(c_vp), c_u64p, ctypes.c_size_t, c_vp,
+                                         ctypes.POINTER(c_vp), c_u64p, ctypes.POINTER(c_vp),
+                                         ctypes.POINTER(c_vp), c_sizep, c_u64p]),
     "cir_match_table_slots": (ctypes.c_uint64, [ctypes.c_uint64]),
     "cir_match_digests_dev": (ctypes.c_int, [c_vp, c_vp, ctypes.c_size_t, c_vp, ctypes.c_size_t,
                                              c_vp, ctypes.c_uint64, ctypes.c_uint64, c_vp, c_vp,

@@ -47,6 +47,20 @@ inline uint64_t count_bits(const uint64_t* src, uint64_t bit, uint64_t count) {
   return n;
 }
 
+// How many bits from `bit` on, at most count, equal `value` in a row.
+inline uint64_t run_bits(const uint64_t* src, uint64_t bit, uint64_t count, bool value) {
+  uint64_t n = 0;
+  while (n < count) {
+    const unsigned k = (unsigned)(count - n < 64 ? count - n : 64);
+    uint64_t v = get_bits(src, bit + n, k);
+    if (value) v = ~v;  // (the first bit that differs is the lowest set one)
+    if (k < 64) v &= (1ull << k) - 1;
+    if (v) return n + (uint64_t)__builtin_ctzll(v);
+    n += k;
+  }
+  return count;
+}
+
 // Clear the bits [bit, bit + count).
 inline void clear_bits(uint64_t* dst, uint64_t bit, uint64_t count) {
   while (count > 0) {

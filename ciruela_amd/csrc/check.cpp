@@ -66,6 +66,7 @@
 #include "dirsig.hpp"
 #include "linkpath.hpp"
 #include "pack.hpp"
+#include "reload.hpp"
 #include "runtime.hpp"
 #include "scatter.hpp"
 #include "stage.hpp"
@@ -814,6 +815,13 @@ int links_impl(cir_ctx* ctx, const uint8_t* index, size_t len, const int* src_di
 // behind the compare, on the compute stream.  A non-empty file without a
 // destination is left out of the work list: nothing of it is looked at.  One
 // device takes the whole image, the one the caller's stream belongs to.
+//
+// cir_reload_blocks (reload.cpp) is cir_load_blocks with a bitmap of the blocks
+// still wanted (Blocks::want): the others already stand in the destinations,
+// copied there from buffers resident in device memory.  A run taken from a file
+// ends at the first unwanted block, unwanted blocks are passed over without
+// being read, and a file none of whose blocks in the range is wanted is not
+// looked at.
 
 // What the looks and the reads found of a file.
 constexpr uint8_t kLookAbsent = 1, kLookBlocked = 2, kLookShort = 4, kLookLong = 8;
@@ -830,6 +838,9 @@ struct Blocks : Layout {
   // the bytes and records scattered, and the records a scatter found bad
   void* const* dests = nullptr;
   std::atomic<uint64_t> n_scat_bytes{0}, n_scat_recs{0}, n_scat_bad{0};
+  // cir_reload_blocks: the blocks still to be read, over the global blocks
+  // (null: all of them)
+  const uint64_t* want = nullptr;
 
   void report(size_t item, uint8_t bits, int e = 0) {
     std::lock_guard<std::mutex> lk(mu);
@@ -925,6 +936,16 @@ int blocks_range(cir_ctx* ctx, Device& d, Blocks& B, unsigned threads, const Blo
       const size_t item = work[cur.ui];
       const Item& it = B.items[item];
       const uint64_t in_range = cur.left();
+      uint64_t wanted = in_range;  // the blocks at the cursor that a run may take
+      if (B.want) {
+        // unwanted blocks are passed over before any look at the file
+        const uint64_t pass = run_bits(B.want, cur.at(), in_range, false);
+        if (pass) {
+          cur.advance(pass);
+          continue;
+        }
+        wanted = run_bits(B.want, cur.at(), in_range, true);
+      }
       // the blocks that lie wholly inside the length the packer saw; the
       // others of this range are passed over (their bits stay 0), and so are
       // all of them when the look fails
@@ -936,12 +957,12 @@ int blocks_range(cir_ctx* ctx, Device& d, Blocks& B, unsigned threads, const Blo
       }
       const uint64_t fblk = cur.fblk;
       if (fblk >= avail) {
-        B.n_unread.fetch_add(in_range);
+        B.n_unread.fetch_add(B.want ? count_bits(B.want, cur.at(), in_range) : in_range);
         cur.advance(in_range);
         continue;
       }
       const Run r = pack_run(b, sz.fill, sz.cap_blk, bs, it.size, fblk,
-                             std::min<uint64_t>(avail - fblk, in_range), s.h_off, s.h_len);
+                             std::min<uint64_t>(avail - fblk, wanted), s.h_off, s.h_len);
       if (!r.take) break;
       // the entry's digests of these blocks travel up through h_out
       memcpy(s.h_out + 32 * r.at, B.digests(it, fblk), 32 * r.take);
@@ -1005,6 +1026,9 @@ struct LoadArgs {
   void* const* d_data;
   size_t ndata;
   void* stream;
+  // cir_reload_blocks: what fills the destinations from resident buffers and
+  // says which blocks it filled (reload.hpp); null: cir_load_blocks
+  const ResidentFn* resident = nullptr;
 };
 
 // load == nullptr: cir_check_blocks.
@@ -1050,10 +1074,22 @@ int blocks_impl(cir_ctx* ctx, int dirfd, const char* dir, const uint8_t* index, 
   // ---- nothing above touched a file or a device (a load asked which device
   // its stream belongs to)
   const double ms_parse = ms_since(t_start);
+  const size_t nwords = (size_t)((B.nblk_total + 63) / 64);
+  // cir_reload_blocks: the blocks taken from memory (empty: none were), and
+  // with them the blocks still wanted
+  std::vector<uint64_t> mem, want;
+  if (load && load->resident) {
+    rc = (*load->resident)(B, *load_dev, &mem);
+    if (rc) return rc;
+    if (!mem.empty()) {
+      want.resize(nwords);
+      for (size_t w = 0; w < nwords; ++w) want[w] = ~mem[w];
+      B.want = want.data();
+    }
+  }
   const auto t_empty = std::chrono::steady_clock::now();
   rc = open_image(B, dirfd, dir);
   if (rc) return rc;
-  const size_t nwords = (size_t)((B.nblk_total + 63) / 64);
   B.look.assign(nfiles, 0);
   B.err.assign(nfiles, 0);
   // the outputs (calloc: every bit starts as "not have")
@@ -1117,14 +1153,22 @@ int blocks_impl(cir_ctx* ctx, int dirfd, const char* dir, const uint8_t* index, 
             load ? "load_blocks" : "check_blocks", nfiles, (unsigned long long)B.nblk_total,
             ms_parse, ms_empty, ms_since(t_pipe));
   if (rc) return rc;
+  // (the pipeline read no block that memory gave: the two bitmaps are disjoint)
+  for (size_t w = 0; B.want && w < nwords; ++w) outs.have[w] |= mem[w];
   // the files' states.  A file that is absent or blocked has none of its
-  // blocks: whatever a range packed of it before it went is cleared.
+  // blocks: whatever a range packed of it before it went is cleared (what
+  // memory gave of it stays: those bytes stand in its destination).
   for (size_t i = 0; i < nfiles; ++i) {
     const Item& it = B.items[i];
     const uint8_t lk = B.look[i];
     uint8_t st;
     if (load && it.nblk && !load->d_data[i]) {  // (no bit of it was ever set)
       outs.state[i] = CIR_FILE_SKIPPED;
+      continue;
+    }
+    if (B.want && it.nblk && count_bits(mem.data(), it.first_blk, it.nblk) == it.nblk) {
+      outs.state[i] = CIR_FILE_COMPLETE | CIR_FILE_RESIDENT;  // (never looked at)
+      ++stats[2];
       continue;
     }
     if (lk & kLookBlocked)
@@ -1137,7 +1181,10 @@ int blocks_impl(cir_ctx* ctx, int dirfd, const char* dir, const uint8_t* index, 
     else
       st = CIR_FILE_PARTIAL;
     if (st == CIR_FILE_BLOCKED || st == CIR_FILE_ABSENT) {
-      clear_bits(outs.have, it.first_blk, it.nblk);
+      if (B.want)
+        copy_bits(outs.have, it.first_blk, mem.data(), it.first_blk, it.nblk);
+      else
+        clear_bits(outs.have, it.first_blk, it.nblk);
     } else if (lk & kLookLong) {
       st |= CIR_FILE_LONG;
     }
@@ -1197,6 +1244,17 @@ int scatter_dev_impl(const uint8_t* d_src, uint64_t src_bytes, const uint64_t* d
 }
 
 }  // namespace
+
+int load_blocks_resident(cir_ctx* ctx, int dirfd, const char* dir, const uint8_t* index, size_t len,
+                         uint32_t threads, void* const* d_data, size_t ndata, void* stream,
+                         const ResidentFn* resident, uint64_t** have_out, uint64_t* nblk_out,
+                         uint8_t** state_out, int32_t** errno_out, size_t* nfiles_out,
+                         uint64_t* stats) {
+  const LoadArgs load{d_data, ndata, stream, resident};
+  return blocks_impl(ctx, dirfd, dir, index, len, threads, have_out, nblk_out, state_out,
+                     errno_out, nfiles_out, stats, &load);
+}
+
 }  // namespace cir
 
 extern "C" int cir_scatter_runs(const uint8_t* src, uint64_t src_bytes, const uint64_t* runs,

@@ -7,6 +7,9 @@ namespace cir {
 namespace emit {
 struct Tables;  // emit.hpp
 }
+namespace copyblk {
+struct Plan;  // copyblk.hpp
+}
 namespace dev {
 
 constexpr int kThreads = 256;  // 4 waves per workgroup (every kernel but the two below)
@@ -446,6 +449,29 @@ hipError_t launch_scatter_runs(const uint8_t* src, uint64_t src_bytes, const uin
 constexpr int kGatherResFields = 1;
 hipError_t launch_gather_runs(uint8_t* dst, uint64_t dst_bytes, const uint64_t* runs,
                               uint64_t nruns, uint64_t nunits, uint64_t* res, hipStream_t s);
+
+// Runs of bytes copied between buffers of any alignment inside device memory
+// (copyblk.hip; cir_copy_runs_dev, cir_reload_blocks; the rule is copyblk.hpp):
+// for every sound record {unit_first, src, dst, bytes} of `runs`
+// (copyblk::kRunWords u64 each) the bytes at src stand at dst afterwards and no
+// other byte is written; res: kCopyResFields u64 {bad records: written nowhere,
+// read nowhere}, zeroed here, all on `s`.  Sources and destinations of one table
+// must not overlap.  No launch when there is neither a unit nor a record.
+// Unchecked: nruns <= copyblk::kMaxRuns, nunits <= copyblk::kMaxUnits.
+constexpr int kCopyResFields = 1;
+hipError_t launch_copy_runs(const uint64_t* runs, uint64_t nruns, uint64_t nunits, uint64_t* res,
+                            hipStream_t s);
+// The copy table of the blocks taken from resident buffers (copyblk.hip;
+// cir_reload_blocks; the rule is copyblk::take_of): have (ceil(n_need / 64) u64,
+// every word written) = the taken blocks, runs = their records in block order
+// (none at or past cap_runs is written), res: copyblk::kPlanResFields u64
+// {records, units, bytes, matches dropped for their length}, all written here,
+// all on `s`.  work: copy_plan_work_bytes(n_need) bytes of scratch.  Unchecked:
+// bs != 0, n_need < 2^32.
+inline uint64_t copy_plan_tiles(uint64_t n_need) { return (n_need + 63) / 64; }
+inline uint64_t copy_plan_work_bytes(uint64_t n_need) { return 16 * copy_plan_tiles(n_need) + 16; }
+hipError_t launch_copy_plan(const copyblk::Plan& p, uint64_t* have, uint64_t* runs,
+                            uint64_t cap_runs, uint64_t* work, uint64_t* res, hipStream_t s);
 
 // nlanes x `lines` register-only compressions (diagnostic VALU ceiling).
 hipError_t launch_compress_only(uint64_t nlanes, uint32_t lines, uint8_t* out, hipStream_t s);

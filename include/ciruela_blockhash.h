@@ -735,6 +735,99 @@ int cir_store_blocks(cir_ctx* ctx, int dirfd, const char* dir, int hash_type, ui
                      uint32_t threads, uint8_t** index_out, size_t* len_out,
                      uint8_t image_id[CIR_DIGEST_BYTES], uint64_t stats[CIR_STORE_STATS_FIELDS]);
 
+/* The copy of cir_reload_blocks on its own: runs of bytes copied between buffers of any
+ * alignment.  The reference has no counterpart.  The rule is ciruela_amd/csrc/copyblk.hpp.
+ *
+ * Table: nruns records of CIR_COPY_RUN_WORDS u64 {unit_first, src, dst, bytes}: `bytes` (> 0)
+ * bytes at the address src go to the address dst, both of any alignment.  A record has
+ * ceil(bytes / 16) units of 16 bytes; unit_first is the unit count of all earlier records and
+ * nunits that of the whole table.  Unit k of a record is the bytes [16 k, 16 k + n), n = min(16,
+ * bytes - 16 k), on both sides: it reads only its own n source bytes and stores only its own n
+ * destination bytes.  For every sound record the bytes at src stand at dst afterwards, and no
+ * other byte is written.  Sources and destinations of one table must not overlap, and neither
+ * may the destinations of different records.
+ *
+ * res[0] = the bad records: bytes 0, or a unit_first that is not the previous record's plus its
+ * units (0 for the first record; the last record must end at nunits).  A bad record is written
+ * nowhere and read nowhere; the count is exact whatever the table holds.
+ *
+ * cir_copy_runs is the host form (src, dst: host addresses; pure, host-only).  CIR_EINVAL: a null
+ * runs with a non-zero count, a null res, nruns above 2^32 - 1 or nunits above 2^60. */
+#define CIR_COPY_RUN_WORDS 4
+#define CIR_COPY_RES_FIELDS 1
+int cir_copy_runs(const uint64_t* runs, uint64_t nruns, uint64_t nunits,
+                  uint64_t res[CIR_COPY_RES_FIELDS]);
+
+/* The same on the device: table, sources and destinations in device memory (d_runs and d_res
+ * 8-byte aligned).  One lane per unit, striding when the table has more units than one grid
+ * holds: one 16-byte load and one 16-byte store where the unit is whole and both addresses are
+ * 16-byte aligned, otherwise the widest loads the source's and the widest stores the
+ * destination's alignment allow, down to single bytes; no atomic touches a destination.  Every
+ * word of d_res[CIR_COPY_RES_FIELDS] is written (a memset and one launch; no launch for an empty
+ * table).  Like every *_dev call it allocates nothing, synchronises nothing and runs on `stream`
+ * alone; ctx may be NULL and is not used.  CIR_EINVAL, decided before any HIP call: as
+ * cir_copy_runs, or a misaligned pointer. */
+int cir_copy_runs_dev(cir_ctx* ctx, const uint64_t* d_runs, uint64_t nruns, uint64_t nunits,
+                      uint64_t* d_res, void* stream);
+
+/* cir_load_blocks for a process that holds the previous version of the image in device memory:
+ * the blocks the resident buffers already hold are copied inside device memory, and only the
+ * rest is read from the image directory.  The reference has no counterpart (it holds no image in
+ * device memory); the observation is the one behind cir_block_sources: most blocks of version
+ * N + 1 are already present in version N.
+ *
+ * The root, index, d_data / ndata, threads, the block numbering, the file ordinals, the outputs
+ * and the stream contract are cir_load_blocks'.  d_have[i] / have_bytes[i] (nhave of them) is a
+ * flat list of resident buffers on the same device: the tensors of the previous version, in any
+ * order and of any alignment.  No path, no index and no claim about their content comes with
+ * them: each is cut into blocks of the new index's block size from its own offset 0, and those
+ * blocks are hashed where they lie, in this call, with the index's hash type.  An entry that is
+ * NULL or empty is ignored.
+ *
+ * Bit g is 1 exactly when d_data[file] + j * block_size now holds bytes whose digest is the
+ * index's: they were copied from a resident block with that digest and length (min(block_size,
+ * size - j * block_size) on either side), or read from the root and verified as in
+ * cir_load_blocks.  Bytes of blocks with neither are untouched.  Blocks taken from memory are
+ * not read, and a file none of whose blocks is left to read is not looked at: a non-empty file
+ * all of whose blocks came from memory is never opened, and its state is CIR_FILE_COMPLETE |
+ * CIR_FILE_RESIDENT whatever is on disk.  Every other file's state is cir_load_blocks', judged
+ * over the combined bitmap; of an ABSENT or BLOCKED file the bits that memory gave stay.  Size-0
+ * entries and CIR_FILE_SKIPPED are as in cir_load_blocks.
+ *
+ * Steps, on the device of `stream`: the memory half is queued on `stream` itself, behind
+ * whatever the caller queued there, and waited for: descriptors of the resident blocks
+ * (cir_index_memory_dev's kernel), their digests, the new index's digests uploaded (the host
+ * parser's: the load pipeline needs the parsed index anyway), cir_match_digests_dev's join with
+ * a seed drawn per call, a plan kernel that turns the matches into a copy table in block order
+ * and a bitmap, cir_copy_runs_dev's kernel.  Then cir_load_blocks' pipeline runs over the blocks
+ * the bitmap lacks.  Device scratch is allocated for the call and freed after it: 44 bytes per
+ * resident block plus the join's table (4 bytes per slot, cir_match_table_slots), 48 bytes per
+ * resident buffer (its record in two tables), 68.4 bytes per block of the new index, and 40 bytes
+ * per file entry of the new index (a run record and a destination).
+ *
+ * Updating an image in the buffers that hold it is out of scope: a block being overwritten may
+ * be another block's source.  CIR_EINVAL, decided before any I/O and any device work: whatever
+ * cir_load_blocks rejects; a null d_have or have_bytes with nhave > 0; more than 2^31 - 1
+ * resident blocks; any destination range [d_data[i], d_data[i] + size_i) that overlaps any
+ * resident range.
+ *
+ * CIR_RELOAD=disk (read per call) ignores the resident list: the call is then cir_load_blocks
+ * (A/B measurement).  CIR_TRACE=1 prints one `cir reload_blocks:` line with the tables, resident
+ * hash, digest upload, join, plan + copy, pipeline and whole-call laps and the blocks taken from
+ * memory, besides cir_load_blocks' own lines.
+ *
+ * stats: [0..11] as cir_load_blocks (blocks from memory count as have and are not in [9]; a
+ * RESIDENT file is in [2]), [12] blocks copied from memory, [13] bytes copied, [14] resident
+ * blocks hashed, [15] files RESIDENT, [16] matches dropped because the lengths differ. */
+#define CIR_FILE_RESIDENT 0x40 /* or'ed in: cir_reload_blocks took every block from memory */
+#define CIR_RELOAD_STATS_FIELDS 17
+int cir_reload_blocks(cir_ctx* ctx, int dirfd, const char* dir, const uint8_t* index, size_t len,
+                      uint32_t threads, void* const* d_data, size_t ndata,
+                      const void* const* d_have, const uint64_t* have_bytes, size_t nhave,
+                      void* stream, uint64_t** have_out, uint64_t* nblk_out, uint8_t** state_out,
+                      int32_t** errno_out, size_t* nfiles_out,
+                      uint64_t stats[CIR_RELOAD_STATS_FIELDS]);
+
 /* Slots the table of cir_match_digests_dev needs for n_pool digests: the smallest power of two
  * >= max(64, 2 * n_pool), so the table is never more than half full (0 when no u64 holds it:
  * n_pool > 2^62).  Pure: no HIP call. */
