@@ -7,6 +7,8 @@
 #   make scatter_fuzz -> build/scatter_fuzz (the scatter rule under ASan + UBSan; not in `all`)
 #   make gather_fuzz -> build/gather_fuzz (the gather rule under ASan + UBSan; not in `all`)
 #   make copyblk_fuzz -> build/copyblk_fuzz (the copy and plan rules under ASan + UBSan; not in `all`)
+#   make update_fuzz -> build/update_fuzz (the in-place update rule under ASan + UBSan; not in
+#                      `all`, built by `make sanitizers`)
 #   make asan/tsan  -> build/host_{asan,tsan}_driver (host code under the
 #                      sanitizers; `make sanitizers` = both; not in `all`)
 HIPCC ?= /opt/rocm/bin/hipcc
@@ -26,10 +28,10 @@ CLI := bin/ciruela-index
 SRCS_HIP := $(CSRC)/kernels.hip $(CSRC)/order.hip $(CSRC)/join.hip \
             $(CSRC)/idxscan.hip $(CSRC)/extents.hip $(CSRC)/repeats.hip \
             $(CSRC)/files.hip $(CSRC)/plan.hip $(CSRC)/sketch.hip $(CSRC)/emit.hip \
-            $(CSRC)/scatter.hip $(CSRC)/gather.hip $(CSRC)/copyblk.hip
+            $(CSRC)/scatter.hip $(CSRC)/gather.hip $(CSRC)/copyblk.hip $(CSRC)/update.hip
 SRCS_CPP := $(CSRC)/runtime.cpp $(CSRC)/dirsig.cpp $(CSRC)/scan.cpp $(CSRC)/check.cpp \
             $(CSRC)/links.cpp $(CSRC)/sources.cpp $(CSRC)/repeats.cpp $(CSRC)/idxscan.cpp \
-            $(CSRC)/files.cpp $(CSRC)/copies.cpp $(CSRC)/plan.cpp $(CSRC)/sketch.cpp $(CSRC)/memindex.cpp $(CSRC)/store.cpp $(CSRC)/reload.cpp $(CSRC)/devcall.cpp $(CSRC)/registry.cpp $(CSRC)/blake2b_host.cpp \
+            $(CSRC)/files.cpp $(CSRC)/copies.cpp $(CSRC)/plan.cpp $(CSRC)/sketch.cpp $(CSRC)/memindex.cpp $(CSRC)/store.cpp $(CSRC)/reload.cpp $(CSRC)/update.cpp $(CSRC)/devcall.cpp $(CSRC)/registry.cpp $(CSRC)/blake2b_host.cpp \
             $(CSRC)/sha512_host.cpp
 OBJS := $(patsubst $(CSRC)/%.hip,$(OBJDIR)/%.hip.o,$(SRCS_HIP)) \
         $(patsubst $(CSRC)/%.cpp,$(OBJDIR)/%.o,$(SRCS_CPP))
@@ -98,7 +100,7 @@ build/host_tsan_driver: $(TSAN_OBJS)
 	$(HIPCC) $(HIPFLAGS) $(TSAN_HOST) -o $@ $(TSAN_OBJS) -lpthread
 tsan: build/host_tsan_driver
 
-sanitizers: asan tsan
+sanitizers: asan tsan update_fuzz
 
 # the sketch rule (sketch.hpp) and the index parser under ASan + UBSan: a
 # stand-alone host program (tools/sketch_fuzz.cpp), no device code
@@ -140,6 +142,14 @@ build/copyblk_fuzz: tools/copyblk_fuzz.cpp $(CSRC)/copyblk.hpp $(CSRC)/scatter.h
 	    -I$(CSRC) tools/copyblk_fuzz.cpp -o $@
 copyblk_fuzz: build/copyblk_fuzz
 
+# the in-place update rule (update.hpp over copyblk.hpp; the kernels are update.hip) under
+# ASan + UBSan: a stand-alone host program (tools/update_fuzz.cpp), no device code
+build/update_fuzz: tools/update_fuzz.cpp $(CSRC)/update.hpp $(CSRC)/copyblk.hpp $(CSRC)/scatter.hpp $(CSRC)/pack.hpp
+	@mkdir -p build
+	$(CXX) -std=c++17 -O1 -g -fsanitize=address,undefined -fno-sanitize-recover=all \
+	    -I$(CSRC) tools/update_fuzz.cpp -o $@
+update_fuzz: build/update_fuzz
+
 oracle:
 	$(MAKE) -C oracle
 
@@ -147,4 +157,4 @@ clean:
 	rm -rf build $(LIB) $(CLI)
 	$(MAKE) -C oracle clean
 
-.PHONY: all oracle clean asan tsan sanitizers sketch_fuzz emit_fuzz scatter_fuzz gather_fuzz copyblk_fuzz
+.PHONY: all oracle clean asan tsan sanitizers sketch_fuzz emit_fuzz scatter_fuzz gather_fuzz copyblk_fuzz update_fuzz

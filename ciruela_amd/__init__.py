@@ -104,6 +104,9 @@ load_image,                     the way back: an image directory read into devic
 reload_image,                   load_image for a process that holds the previous
   Context.reload_blocks         version in device memory: the blocks its buffers
                                 already hold are copied on the device, the rest read
+update_image,                   the same in the tensors that hold the previous
+  Context.update_blocks         version: blocks already in place are left alone, the
+                                others move through a staging scratch where they must
 =============================  ==============================================
 
 All hashing runs on gfx950 through the library; there is no CPU fallback.
@@ -127,7 +130,7 @@ __all__ = [
     "index_digests", "IndexDigests", "file_sources", "file_copies", "check_links_at",
     "fetch_plan", "PlanResult", "index_sketch", "sketch_rank", "sketch_key",
     "index_memory", "index_emit", "index_emit_layout", "index_emit_tables", "load_image",
-    "reload_image",
+    "reload_image", "update_image",
     "store_image",
 ]
 
@@ -729,6 +732,28 @@ class Context:
         load_blocks reads it.  A file all of whose blocks came from memory is
         not opened: it is "complete" and its `resident` flag is set."""
         return _load_blocks(self, root, index, buffers, list(resident), threads, dir_fd, stream)
+
+    UPDATE_STATS_FIELDS = RELOAD_STATS_FIELDS + ("kept_blocks", "kept_bytes", "staged_blocks",
+                                                 "scratch_bytes", "demoted_blocks")
+
+    def update_blocks(self, root, index, buffers, resident, scratch_bytes=None, threads=0,
+                      dir_fd=None, stream=0):
+        """reload_blocks without the overlap restriction (cir_update_blocks):
+        the buffers may be the resident ones themselves, overlap them in any
+        way, or be fresh memory.  A block that already stands at its
+        destination with the index's digest is kept untouched; a block whose
+        destination lies clear of every resident buffer is copied directly;
+        any other block found in memory goes through a staging scratch of at
+        most scratch_bytes (None: whatever it takes; 0: none, such blocks are
+        read from `root`).  Resident buffers must not overlap one another, nor
+        may the destinations.  Until the scratch is allocated nothing is
+        written, so a CiruelaError(CIR_ENOMEM) leaves the old version whole;
+        after that the result's bits are the truth about the buffers."""
+        cap = (1 << 64) - 1 if scratch_bytes is None else int(scratch_bytes)
+        if not 0 <= cap < 1 << 64:
+            raise ValueError("scratch_bytes must fit 64 bits")
+        return _load_blocks(self, root, index, buffers, list(resident), threads, dir_fd, stream,
+                            scratch=cap)
 
     STORE_STATS_FIELDS = ("blocks", "files", "dirs_made", "bytes", "batches", "body_bytes")
 
@@ -1537,9 +1562,10 @@ def index_emit(files, digests, block_size=DEFAULT_BLOCK_SIZE, hash_type=None, im
     return _n.take_buffer(out.value, out_len.value)
 
 
-def _load_blocks(ctx, root, index, buffers, resident, threads, dir_fd, stream):
-    """Context.load_blocks (resident is None) and Context.reload_blocks: the
-    arguments are checked before the context is touched."""
+def _load_blocks(ctx, root, index, buffers, resident, threads, dir_fd, stream, scratch=None):
+    """Context.load_blocks (resident is None), Context.reload_blocks and
+    Context.update_blocks (scratch is its cap): the arguments are checked
+    before the context is touched."""
     if len(index):
         ptr, keep = _buf(index)
     else:  # (an empty index is a parse error, not a null argument)
@@ -1579,13 +1605,19 @@ def _load_blocks(ctx, root, index, buffers, resident, threads, dir_fd, stream):
         _n.check(_n.lib.cir_load_blocks(ctx._h, fd, path, ptr, len(index), threads, d_data, n,
                                         stream, *outs, stats))
     else:
-        fields = Context.RELOAD_STATS_FIELDS
         spans = [_device_span(r) for r in resident if r is not None]
         d_have = (ctypes.c_void_p * max(len(spans), 1))(*[p or None for p, _ in spans])
-        stats = (ctypes.c_uint64 * _n.CIR_RELOAD_STATS_FIELDS)()
-        _n.check(_n.lib.cir_reload_blocks(ctx._h, fd, path, ptr, len(index), threads, d_data,
-                                          n, d_have, _sizes([b for _, b in spans]), len(spans),
-                                          stream, *outs, stats))
+        held = (d_have, _sizes([b for _, b in spans]), len(spans))
+        if scratch is None:
+            fields = Context.RELOAD_STATS_FIELDS
+            stats = (ctypes.c_uint64 * _n.CIR_RELOAD_STATS_FIELDS)()
+            _n.check(_n.lib.cir_reload_blocks(ctx._h, fd, path, ptr, len(index), threads, d_data,
+                                              n, *held, stream, *outs, stats))
+        else:
+            fields = Context.UPDATE_STATS_FIELDS
+            stats = (ctypes.c_uint64 * _n.CIR_UPDATE_STATS_FIELDS)()
+            _n.check(_n.lib.cir_update_blocks(ctx._h, fd, path, ptr, len(index), threads, d_data,
+                                              n, *held, scratch, stream, *outs, stats))
     del keep, buffers, resident
     nf = nfiles.value
     bits = _n.take_buffer(have.value, 8 * ((nblk.value + 63) // 64))
@@ -1691,6 +1723,46 @@ def reload_image(root, index, resident, context=None, only=None, threads=0):
     image is copied on the device, the rest is read from `root`."""
     held = list(resident.values()) if isinstance(resident, dict) else list(resident)
     return _load_image(root, index, context, only, threads, held)
+
+
+def update_image(root, index, held, context=None, only=None, threads=0, scratch_bytes=None):
+    """reload_image in the tensors that hold the previous version
+    (cir_update_blocks): held is the {path: tensor} dict the previous
+    load_image (or update_image) returned.  An entry of `index` whose path is
+    in held with a tensor of exactly the entry's size gets that same tensor as
+    its destination; every other non-empty entry -- with `only`, of those named
+    -- gets a new tensor.  All of held is the resident list.  Blocks that
+    already stand where they belong are not touched, the others found in held
+    are copied on the device (through at most scratch_bytes of staging where
+    they land on old bytes; None: whatever it takes), the rest is read from
+    `root`.  Returns ({path: tensor}, BlocksResult); held itself is not
+    modified, and tensors of paths that vanished are simply not in the result
+    -- their bytes may have served as sources, but nothing is written to
+    them."""
+    import torch
+    ctx = context or default_context()
+    dev = torch.device("cuda", ctx.devices()[0])
+    files, _ = _file_blocks(index)
+    keep = None if only is None else {os.fsencode(p) if isinstance(p, str) else bytes(p)
+                                      for p in only}
+    held = {os.fsencode(p) if isinstance(p, str) else bytes(p): t for p, t in held.items()}
+    tensors = {}
+    buffers = []
+    for path, size, _ in files:
+        if size and (keep is None or path in keep):
+            old = held.get(path)
+            if old is not None and _device_span(old)[1] == size:
+                tensors[path] = old
+            else:
+                tensors[path] = torch.empty(size, dtype=torch.uint8, device=dev)
+            buffers.append(tensors[path])
+        else:
+            buffers.append(None)
+    with torch.cuda.device(dev):
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        res = ctx.update_blocks(root, index, buffers, list(held.values()),
+                                scratch_bytes=scratch_bytes, threads=threads, stream=stream)
+    return tensors, res
 
 
 def store_image(root, files, block_size=DEFAULT_BLOCK_SIZE, hash_type=None, context=None,

@@ -60,6 +60,7 @@ CIR_GATHER_RES_FIELDS = 1
 CIR_COPY_RUN_WORDS = 4
 CIR_COPY_RES_FIELDS = 1
 CIR_RELOAD_STATS_FIELDS = 17
+CIR_UPDATE_STATS_FIELDS = 22
 CIR_STORE_STATS_FIELDS = 6
 CIR_SOURCES_STATS_FIELDS = 8
 CIR_EXTENTS_STATS_FIELDS = 10
@@ -238,6 +239,12 @@ _SIGS = {
                                          ctypes.POINTER(c_vp), c_u64p, ctypes.c_size_t, c_vp,
                                          ctypes.POINTER(c_vp), c_u64p, ctypes.POINTER(c_vp),
                                          ctypes.POINTER(c_vp), c_sizep, c_u64p]),
+    "cir_update_blocks": (ctypes.c_int, [c_vp, ctypes.c_int, ctypes.c_char_p, c_vp, ctypes.c_size_t,
+                                         ctypes.c_uint32, ctypes.POINTER(c_vp), ctypes.c_size_t,
+                                         ctypes.POINTER(c_vp), c_u64p, ctypes.c_size_t,
+                                         ctypes.c_uint64, c_vp, ctypes.POINTER(c_vp), c_u64p,
+                                         ctypes.POINTER(c_vp), ctypes.POINTER(c_vp), c_sizep,
+                                         c_u64p]),
     "cir_match_table_slots": (ctypes.c_uint64, [ctypes.c_uint64]),
     "cir_match_digests_dev": (ctypes.c_int, [c_vp, c_vp, ctypes.c_size_t, c_vp, ctypes.c_size_t,
                                              c_vp, ctypes.c_uint64, ctypes.c_uint64, c_vp, c_vp,

@@ -7,6 +7,9 @@ namespace cir {
 namespace emit {
 struct Tables;  // emit.hpp
 }
+namespace update {
+struct Plan;
+}
 namespace copyblk {
 struct Plan;  // copyblk.hpp
 }
@@ -472,6 +475,25 @@ inline uint64_t copy_plan_tiles(uint64_t n_need) { return (n_need + 63) / 64; }
 inline uint64_t copy_plan_work_bytes(uint64_t n_need) { return 16 * copy_plan_tiles(n_need) + 16; }
 hipError_t launch_copy_plan(const copyblk::Plan& p, uint64_t* have, uint64_t* runs,
                             uint64_t cap_runs, uint64_t* work, uint64_t* res, hipStream_t s);
+
+// The two copy tables and the bitmap of an image updated in the buffers that
+// hold it (update.hip; cir_update_blocks; the rule is update.hpp), in two steps
+// with the host's look at the counts between them.  launch_update_count:
+// k_update_plan and k_update_scan; res: update::kResFields u64, zeroed here,
+// of which the totals {A records, A units, B records, B units} and the
+// candidates' totals are final afterwards; work: update_plan_work_bytes(n_need)
+// bytes of scratch that launch_update_emit reads.  launch_update_emit
+// (p.scratch set, at least 16 res[kBUnits] bytes): have (ceil(n_need / 64) u64,
+// every word written) = the kept, direct and staged blocks, runs_a and runs_b =
+// the records of phase 1 and phase 2 in block order (none at or past cap_runs
+// is written), and the class counts added to res.  All on `s`.  Unchecked: bs
+// != 0, n_need < 2^32, the resident table sorted by address and disjoint.
+inline uint64_t update_plan_tiles(uint64_t n_need) { return (n_need + 63) / 64; }
+inline uint64_t update_plan_work_bytes(uint64_t n_need) { return 32 * update_plan_tiles(n_need) + 32; }
+hipError_t launch_update_count(const update::Plan& p, uint64_t* work, uint64_t* res, hipStream_t s);
+hipError_t launch_update_emit(const update::Plan& p, const uint64_t* work, uint64_t cap_runs,
+                              uint64_t* have, uint64_t* runs_a, uint64_t* runs_b, uint64_t* res,
+                              hipStream_t s);
 
 // nlanes x `lines` register-only compressions (diagnostic VALU ceiling).
 hipError_t launch_compress_only(uint64_t nlanes, uint32_t lines, uint8_t* out, hipStream_t s);

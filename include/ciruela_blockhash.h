@@ -805,8 +805,8 @@ int cir_copy_runs_dev(cir_ctx* ctx, const uint64_t* d_runs, uint64_t nruns, uint
  * resident buffer (its record in two tables), 68.4 bytes per block of the new index, and 40 bytes
  * per file entry of the new index (a run record and a destination).
  *
- * Updating an image in the buffers that hold it is out of scope: a block being overwritten may
- * be another block's source.  CIR_EINVAL, decided before any I/O and any device work: whatever
+ * Updating an image in the buffers that hold it is cir_update_blocks' (below), not this call's:
+ * a block being overwritten may be another block's source.  CIR_EINVAL, decided before any I/O and any device work: whatever
  * cir_load_blocks rejects; a null d_have or have_bytes with nhave > 0; more than 2^31 - 1
  * resident blocks; any destination range [d_data[i], d_data[i] + size_i) that overlaps any
  * resident range.
@@ -827,6 +827,69 @@ int cir_reload_blocks(cir_ctx* ctx, int dirfd, const char* dir, const uint8_t* i
                       void* stream, uint64_t** have_out, uint64_t* nblk_out, uint8_t** state_out,
                       int32_t** errno_out, size_t* nfiles_out,
                       uint64_t stats[CIR_RELOAD_STATS_FIELDS]);
+
+/* cir_reload_blocks without the overlap restriction: the next version of an image loaded in the
+ * buffers that hold the previous one.  The destinations d_data[i] may be the resident buffers
+ * themselves or overlap them in any way -- identical, shifted by whole blocks or by odd bytes,
+ * partly inside and partly outside -- or be fresh memory.  The reference has no counterpart.  The
+ * rule is ciruela_amd/csrc/update.hpp.
+ *
+ * Everything not said here is cir_reload_blocks': the root, index, d_data / ndata, the resident
+ * list, the outputs, the stream contract and the guarantee: bit g is 1 exactly when d_data[file]
+ * + j * block_size now holds bytes whose digest is the index's.  cir_index_memory_dev of a
+ * complete result is the new index.
+ *
+ * Every block g of the index whose file has a destination gets one class (dst = d_data[file] + j
+ * * block_size, len = min(block_size, size - j * block_size)).  KEPT: dst lies in a resident
+ * buffer at a multiple of block_size from its start, and that resident block has length len and
+ * g's digest; nothing is read or written.  This test comes first: a file full of equal blocks is
+ * kept, not moved onto itself.  Otherwise a block with a resident block of its digest and length
+ * is taken as in cir_reload_blocks: DIRECT when [dst, dst + len) overlaps no resident buffer,
+ * copied in phase 1; STAGED otherwise, copied to a scratch in phase 1 and from it to dst in phase
+ * 2.  Phase 1 is the last read of the resident buffers; phase 2 and the reads from the root write
+ * afterwards, in stream order, so swaps, cycles and shifts need no ordering of single copies.
+ *
+ * scratch_bytes caps the staging scratch: UINT64_MAX means whatever the staged blocks need, 0
+ * stages nothing.  STAGED candidates take ceil(len / 16) units of 16 bytes each, in block order;
+ * one is staged while the units of all candidates up to and including it fit in scratch_bytes /
+ * 16, and DEMOTED otherwise: not taken, bit 0 unless the root gives the block, read from the root
+ * like any missing block.  The cut is a prefix in block order, whatever the timing.
+ *
+ * Until the scratch is allocated -- min(scratch_bytes, 16 bytes per staged unit), after the plan
+ * -- no byte of any caller buffer has been written: CIR_ENOMEM from that allocation or any error
+ * before it leaves version N as it was.  After that the old version is gone as an image, and on a
+ * later error the bitmap, where one is returned, is the only truth about the buffers.  Bytes of
+ * blocks that were neither taken nor read are untouched, as in cir_reload_blocks.
+ *
+ * A non-empty file all of whose blocks are KEPT, DIRECT or STAGED is never opened: its state is
+ * CIR_FILE_COMPLETE | CIR_FILE_RESIDENT.
+ *
+ * Steps, on `stream`: cir_reload_blocks' descriptors, resident hash, digest upload and join; two
+ * plan kernels (classes and counts, their prefixes and the cut); one synchronise for the counts;
+ * the scratch; a third plan kernel (the bitmap and the two copy tables, in block order) and
+ * cir_copy_runs_dev's kernel twice.  Then cir_load_blocks' pipeline over the blocks the bitmap
+ * lacks.  Device scratch besides the staging scratch: cir_reload_blocks' plus 32.5 bytes per block
+ * of the new index (a second table, two more words per tile).
+ *
+ * CIR_EINVAL, decided before any I/O and any device work: whatever cir_reload_blocks rejects
+ * except a destination that overlaps a resident buffer; two resident buffers that overlap one
+ * another (the call writes into them); two destinations of non-empty entries that overlap one
+ * another.
+ *
+ * CIR_UPDATE=disk (read per call) ignores the resident list: the call is then cir_load_blocks
+ * into the same buffers (A/B measurement).  CIR_TRACE=1 prints one `cir update_blocks:` line with
+ * cir_reload_blocks' laps and the kept, copied, staged and demoted blocks.
+ *
+ * stats: [0..16] as cir_reload_blocks, [12] and [13] the DIRECT and staged blocks and their
+ * bytes; [17] blocks kept, [18] bytes kept, [19] blocks staged, [20] bytes of staging scratch
+ * allocated, [21] blocks demoted by the cap. */
+#define CIR_UPDATE_STATS_FIELDS 22
+int cir_update_blocks(cir_ctx* ctx, int dirfd, const char* dir, const uint8_t* index, size_t len,
+                      uint32_t threads, void* const* d_data, size_t ndata,
+                      const void* const* d_have, const uint64_t* have_bytes, size_t nhave,
+                      uint64_t scratch_bytes, void* stream, uint64_t** have_out,
+                      uint64_t* nblk_out, uint8_t** state_out, int32_t** errno_out,
+                      size_t* nfiles_out, uint64_t stats[CIR_UPDATE_STATS_FIELDS]);
 
 /* Slots the table of cir_match_digests_dev needs for n_pool digests: the smallest power of two
  * >= max(64, 2 * n_pool), so the table is never more than half full (0 when no u64 holds it:
